@@ -9,6 +9,10 @@ augmentation, on synthetic positions and random-init weights (no datasets or
 checkpoints are reachable offline).
 
 Single GPU:   python bench.py --steps 20 --warmup 5
+Outputs:      python bench.py --dump-outputs DIR   (what the last timed step computed, as DIR/*.npy)
+Everything:   python bench.py --full   (the plain run measures the headline figure only; measurements
+              that need runs of their own belong behind --full -- today there are none, every figure
+              of the result line comes from the one timed region)
 N GPUs:       python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
                   --master-addr 127.0.0.1 --master-port P bench.py --gpus N
           or    python bench.py --gpus N   (starts the N ranks itself, parallel/launch.py)
@@ -24,6 +28,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 PAPER_SL_POS_PER_S = 3000.0  # paper SL throughput, 50 GPUs aggregate (derived)
+DUMP_MAX_VALUES = 7 * 2 ** 20  # per --dump-outputs array (float32): the four files stay under 64 MB
 
 
 def teacher_pool_on_device(args, dev, rank):
@@ -42,6 +47,38 @@ def teacher_pool_on_device(args, dev, rank):
     if dev.type == "cuda":
         torch.cuda.empty_cache()
     return torch.from_numpy(planes).to(dev), torch.from_numpy(tgt).to(dev)
+
+
+def trainer_state(trainer):
+    """Copy of what a step updates: fp32 master weights, optimizer moments, schedule position."""
+    return (trainer.fp.flat.clone(), [m.clone() for m in trainer.opt_state], trainer.sched.iterations)
+
+
+def restore_trainer_state(trainer, state):
+    flat, moments, iterations = state
+    trainer.fp.flat.copy_(flat)
+    for m, m0 in zip(trainer.opt_state, moments):
+        m.copy_(m0)
+    trainer.sched.iterations = iterations
+    if hasattr(trainer, "repack"):  # HIP trainers: the device copies of the weights the kernels read
+        trainer.repack()
+        if trainer.use_graph:
+            trainer.sync_schedule()
+
+
+def dump_outputs(path, trainer, last):
+    """What the last timed step handed back: its loss and metric sums, the master weights it updated
+    and the gradients it applied (flat fp32 buffers, ~3.9 M values each at the default size)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": last[0].reshape(1), "correct": last[1].reshape(1),
+              "params": trainer.fp.flat[:trainer.fp.numel], "grads": trainer.fp.grad[:trainer.fp.numel]}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_VALUES:  # a larger net: the same seeded sample of its values in every run
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_VALUES, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def main():
@@ -88,6 +125,14 @@ def main():
                          "per layer (default: engine default)")
     ap.add_argument("--profile", default=None,
                     help="after the timed run, profile 6 more steps (torch.profiler + roctx ranges) into DIR")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (float32: loss, "
+                         "correct, params, grads).  The timed steps then start from the initial weights and a "
+                         "re-seeded batch stream, whatever the number of warmup steps, so two runs with the same "
+                         "arguments compute the same steps (top1_acc / mean_loss are those of the first --steps "
+                         "steps of training)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (none today: the plain run is the whole benchmark)")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` without torchrun: this process only supervises N ranks started by
@@ -120,6 +165,7 @@ def main():
     trainer = make_policy_trainer(net, args.batch, args.lr, 0.0, backend=args.backend, device=dev, **kw)
     if args.graph:
         trainer.enable_graphs()
+    start_state = trainer_state(trainer) if args.dump_outputs else None
 
     # synthetic dataset, resident in HBM (uint8 one-hot planes + move targets), built before the clock
     g = torch.Generator(device=dev)
@@ -149,6 +195,8 @@ def main():
     loss_sum = torch.zeros((), device=dev)
     corr_sum = torch.zeros((), device=dev)
 
+    last = [None, None]  # (loss, metric) of the latest step, as the trainer returned them
+
     def run(n):
         # The warmup runs this exact loop body too: every kernel of the timed region (including the
         # metric accumulation) is loaded before the clock starts.  On a fresh box the first launch of
@@ -157,7 +205,7 @@ def main():
         # GPU work measured as 21.1 ms/step (profiles/r2_fresh_box_diagnosis.md).
         for _ in range(n):
             bargs, bkw = batch()
-            l, c = trainer.step(*bargs, **bkw)
+            l, c = last[:] = trainer.step(*bargs, **bkw)
             loss_sum.add_(l)
             corr_sum.add_(c)
 
@@ -173,6 +221,9 @@ def main():
             break
         run(10)
         warm_steps += 10
+    if start_state is not None:  # the timed steps are the same steps in every run
+        restore_trainer_state(trainer, start_state)
+        g.manual_seed(1099 + env.rank)
     loss_sum.zero_()
     corr_sum.zero_()
     if hasattr(trainer, "comm_events") and (env.distributed or getattr(trainer, "_proxy", None) is not None):
@@ -205,6 +256,8 @@ def main():
     agdist.all_reduce_sum_(stats)
     positions = args.batch * n * args.steps
     value = positions / dt
+    if args.dump_outputs and env.is_main:
+        dump_outputs(args.dump_outputs, trainer, last)
     if env.is_main:
         out = {
             "metric": "SL-policy positions/sec (whole node) + top-1 move acc, 19x19 12-layer net",
@@ -232,6 +285,7 @@ def main():
             "allreduce_exposed_ms_per_step": None if comm is None else round(comm, 3),
             "pool_build_s": round(pool_s, 1),
             "hbm_peak_gib_per_rank": round(hbm_gib, 2),
+            "full": bool(args.full),
             "config": {
                 "model": "SL policy net (%d-layer, %d filters, %d planes)" % (args.layers, args.filters, args.planes),
                 "global_batch": args.batch * n,

@@ -62,7 +62,8 @@ def gpu_featurizer(states, B=1024, iters=50):
 
 
 def main():
-    sgf_dir = sys.argv[1] if len(sys.argv) > 1 else "/root/reference/tests/test_data/sgf"
+    sgf_dir = sys.argv[1] if len(sys.argv) > 1 else os.path.join(
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "reference_data", "sgf")
     if not os.path.isdir(sgf_dir):  # synthetic fallback: random games
         import random
         states, gs, rnd = [], go.GameState(), random.Random(0)

@@ -15,7 +15,8 @@ import torch  # noqa: E402
 from alphago_amd.models.policy import CNNPolicy  # noqa: E402
 from alphago_amd.train.sl import run_training  # noqa: E402
 
-FIXTURE = "/root/reference/tests/test_data/hdf5/alphago-vs-lee-sedol-features.hdf5"
+FIXTURE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden",
+                       "reference_data", "hdf5", "alphago-vs-lee-sedol-features.hdf5")
 
 
 def main():

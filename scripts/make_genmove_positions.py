@@ -10,7 +10,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from alphago_amd.utils.gorecords import sgf_iter_states  # noqa: E402
 
-src = sys.argv[1] if len(sys.argv) > 1 else "/root/reference/tests/test_data/sgf"
+src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                                         "tests", "golden", "reference_data", "sgf")
 out = []
 for path in sorted(glob.glob(os.path.join(src, "*Lee-Sedol*.sgf"))):
     moves = []

@@ -39,9 +39,10 @@ def _real_games(out, features):
     from alphago_amd.data.convert import GameConverter
     here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
     pre = (os.path.join(here, "lee_sedol_train.h5"), os.path.join(here, "lee_sedol_heldout.h5"))
-    if all(os.path.exists(p) for p in pre):  # converted in-tree (the reference checkout is not on the GPU box)
+    if all(os.path.exists(p) for p in pre):  # converted in-tree
         return pre[0], pre[1], "Lee-Sedol-vs-AlphaGo-20160315.sgf"
-    sgf_dir = "/root/reference/tests/test_data/sgf"
+    sgf_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden",
+                           "reference_data", "sgf")
     games = sorted(os.path.join(sgf_dir, f) for f in os.listdir(sgf_dir) if "Lee" in f) if os.path.isdir(sgf_dir) \
         else []
     if len(games) < 2:

@@ -1,21 +1,21 @@
-"""Load the reference implementation as a *test oracle* (differential tests).
+"""Load the reference implementation as an oracle for scripts/make_reference_traces.py.
 
-The reference (/root/reference, Python 2 + Keras 1) is imported read-only from
-its own files at test time, with minimal textual Python-3 shims applied in
-memory (filter -> list, np.int -> int).  Nothing from it is copied into this
-repository.  Tests that use it are skipped where the reference is absent
-(e.g. on the GPU box).
+The reference (Python 2 + Keras 1; a checkout named by ALPHAGO_REFERENCE) is imported read-only
+from its own files, with minimal textual Python-3 shims applied in memory (filter -> list,
+np.int -> int).  Nothing from it is copied into this repository: the script records moves and
+digests of its behaviour under tests/golden/reference_traces/, and the differential tests replay
+those (tests/reftrace.py), so the suite itself never needs the checkout.
 """
 import os
 import types
 
 import numpy as np
 
-REF = os.environ.get("ALPHAGO_REFERENCE", "/root/reference")
+REF = os.environ.get("ALPHAGO_REFERENCE", "")
 
 
 def available():
-    return os.path.exists(os.path.join(REF, "AlphaGo", "go.py"))
+    return bool(REF) and os.path.exists(os.path.join(REF, "AlphaGo", "go.py"))
 
 
 def _load(name, relpath, extra_globals=None, shims=()):

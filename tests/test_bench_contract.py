@@ -79,6 +79,69 @@ def test_bench_plain_launch_starts_the_ranks():
     assert len(out["rank_ms_per_step"]) == 4
 
 
+def test_bench_dump_outputs_repeat_and_full(tmp_path):
+    """--dump-outputs DIR writes the last timed step's loss, metric, weights and gradients as float32
+    .npy files, identical from run to run whatever the (time-based) number of warmup steps; --full is
+    accepted and leaves the result line's headline keys in place."""
+    import numpy as np
+
+    dumps = []
+    for name, extra in (("a", ["--min-warmup-s", "0.0"]), ("b", ["--full"])):
+        d = str(tmp_path / name)
+        p = _plain_bench(["--gpus", "1", "--backend", "torch", "--dump-outputs", d] + extra)
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["full"] is (name == "b")
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert key in out
+        assert sorted(os.listdir(d)) == ["correct.npy", "grads.npy", "loss.npy", "params.npy"]
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    a, b = dumps
+    assert out["warmup_steps_run"] > 1  # run b warmed up for 0.5 s, run a for one step
+    for f, x in a.items():
+        assert x.dtype == np.float32 and np.isfinite(x).all()
+        assert np.array_equal(x, b[f]), f
+    assert a["params"].shape == a["grads"].shape and a["params"].size > 1000 and a["loss"].shape == (1,)
+    assert np.abs(a["grads"]).max() > 0
+
+
+@pytest.mark.gpu
+def test_bench_restore_state_repeats_hip_steps(cuda_device):
+    """What --dump-outputs relies on: after bench.restore_trainer_state the HIP trainer repeats the steps
+    it took from the saved state bit for bit (master weights, their bf16 packs, schedule position)."""
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from alphago_amd.models.nets import PolicyNet
+    from alphago_amd.train.engine import make_policy_trainer
+
+    torch.manual_seed(0)
+    B = 16
+    tr = make_policy_trainer(PolicyNet(48, board=19, filters_per_layer=64, layers=3), B, 0.03, 1e-3,
+                             backend="hip", device=cuda_device)
+    g = torch.Generator(device=cuda_device)
+    g.manual_seed(5)
+    batches = [(torch.randint(0, 2, (B, 48, 19, 19), device=cuda_device, dtype=torch.uint8, generator=g),
+                torch.randint(0, 361, (B,), device=cuda_device, dtype=torch.int32, generator=g),
+                torch.randint(0, 8, (B,), device=cuda_device, dtype=torch.int32, generator=g)) for _ in range(3)]
+
+    def steps():
+        for b in batches:
+            loss, corr = tr.step(*b)
+        return loss.clone(), corr.clone(), tr.fp.flat.clone(), tr.fp.grad.clone()
+
+    state = bench.trainer_state(tr)
+    first = steps()
+    later = steps()  # training goes on: different weights
+    assert not torch.equal(first[2], later[2])
+    bench.restore_trainer_state(tr, state)
+    again = steps()
+    for a, b in zip(first, again):
+        assert torch.equal(a, b)
+    assert tr.sched.iterations == 3
+
+
 def test_bench_refuses_world_mismatch():
     """--gpus 2 inside a 4-rank torchrun world is refused (non-zero exit, no JSON line)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",

@@ -11,8 +11,8 @@ from alphago_amd.io.h5lite import H5File
 from alphago_amd.io.sgf import SGFParseError, parse
 from alphago_amd.utils.gorecords import flatten_idx, gamestate_to_sgf, sgf_iter_states, sgf_to_gamestate, unflatten_idx
 
-REF = "/root/reference/tests/test_data"
-HAVE_REF = os.path.exists(REF)
+# the reference's test data (SGF records, its converter's HDF5 output), stored with the suite
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data")
 
 
 def test_sgf_parser_basics():
@@ -38,14 +38,12 @@ def test_sgf_roundtrip():
     assert np.array_equal(gs.board, gs2.board) and gs2.history == gs.history
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference fixtures absent")
 def test_ab_aw_setup():
     with open(os.path.join(REF, "sgf", "ab_aw.sgf")) as f:
         gs = sgf_to_gamestate(f.read())
     assert gs.size == 19 and np.count_nonzero(gs.board) > 0
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference fixtures absent")
 def test_conversion_matches_reference_fixture(tmp_path):
     """The reference fixture was produced by the reference converter with
     features board, ones, turns_since (12 planes); ours must be bit-identical."""
@@ -62,7 +60,6 @@ def test_conversion_matches_reference_fixture(tmp_path):
         assert np.array_equal(planes, states[start:start + n]), key
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference fixtures absent")
 def test_converter_cli(tmp_path):
     out = str(tmp_path / "out.h5")
     n = run_game_converter(["--features", "board,ones,turns_since,liberties,sensibleness", "-o", out,
@@ -78,7 +75,6 @@ def test_converter_cli(tmp_path):
     assert run_game_converter(["-o", out2, "-d", REF, "-R"]) == n * 1 or os.path.exists(out2)
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference fixtures absent")
 def test_converter_writes_reference_layout_and_matches_fixture(tmp_path):
     """Converter output uses the reference's storage layout (states chunked
     (64,F,S,S) + LZF, actions chunked (1024,2) + LZF, game_converter.py:71-86),

@@ -1,86 +1,55 @@
-"""Differential test: native engine + featurizer vs the reference Python
-implementation (loaded read-only as an oracle, see refshim.py) on random games."""
-import random
-
+"""Differential test: native engine + featurizer vs the reference Python implementation on random
+games.  The reference's side is recorded (moves, state and feature-plane digests, see reftrace.py and
+scripts/make_reference_traces.py); the native engine replays the moves and must give the same digests."""
 import numpy as np
 import pytest
 
-import refshim
+import reftrace
 from alphago_amd import go
 from alphago_amd.features import ALL_NO_LADDER_FEATURES, Preprocess
-
-pytestmark = pytest.mark.skipif(not refshim.available(), reason="reference checkout not present")
-
-
-def _random_game_pairs(size, n_moves, seed):
-    rg = refshim.ref_go()
-    rnd = random.Random(seed)
-    ours, ref = go.GameState(size), rg.GameState(size)
-    for _ in range(n_moves):
-        legal = ref.get_legal_moves()
-        if not legal or rnd.random() < 0.03:
-            mv = None
-        else:
-            mv = rnd.choice(legal)
-        ref.do_move(mv)
-        ours.do_move(mv)
-        if ref.is_end_of_game:
-            break
-        yield ours, ref
 
 
 @pytest.mark.parametrize("size,seed", [(7, 0), (9, 1), (9, 2), (13, 3), (19, 4)])
 def test_rules_match_reference(size, seed):
-    rg = refshim.ref_go()
-    n = {7: 120, 9: 200, 13: 300, 19: 350}[size]
-    checked = 0
-    for ours, ref in _random_game_pairs(size, n, seed):
-        assert np.array_equal(ours.board, ref.board)
-        assert np.array_equal(ours.liberty_counts, ref.liberty_counts)
-        assert ours.ko == ref.ko
-        assert ours.current_player == ref.current_player
-        assert (ours.num_black_prisoners, ours.num_white_prisoners) == (ref.num_black_prisoners, ref.num_white_prisoners)
-        assert ours.get_legal_moves() == ref.get_legal_moves()
-        assert ours.get_winner() == ref.get_winner()
+    """Board, liberty counts, ko, side to move, prisoners, legal moves and winner after every move; is_eye
+    of every empty point for both colours at every 7th position."""
+    tr = reftrace.load("rules_%d_%d" % (size, seed))
+    ours = go.GameState(size)
+    checked = eyes = 0
+    for i, row in enumerate(tr["moves"]):
+        ours.do_move(reftrace.to_move(row))
+        if i >= len(tr["state"]):  # the move that ended the reference's game
+            assert ours.is_end_of_game
+            break
+        assert not ours.is_end_of_game
+        assert reftrace.state_digest(ours) == tr["state"][i], "state differs after move %d" % i
         if checked % 7 == 0:
-            for x in range(size):
-                for y in range(size):
-                    if ref.board[x, y] == rg.EMPTY:
-                        for c in (rg.BLACK, rg.WHITE):
-                            assert ours.is_eye((x, y), c) == ref.is_eye((x, y), c)
+            assert reftrace.eye_digest(ours) == tr["eyes"][eyes], "is_eye differs after move %d" % i
+            eyes += 1
         checked += 1
+    assert checked == len(tr["state"]) and eyes == len(tr["eyes"])
     assert checked > 20
 
 
 @pytest.mark.parametrize("size,seed", [(9, 5), (19, 6)])
 def test_features_match_reference(size, seed):
-    rpp = refshim.ref_preprocessing().Preprocess(ALL_NO_LADDER_FEATURES)
+    tr = reftrace.load("features_%d_%d" % (size, seed))
     pp = Preprocess(ALL_NO_LADDER_FEATURES)
-    for i, (ours, ref) in enumerate(_random_game_pairs(size, 260, seed)):
+    ours = go.GameState(size)
+    done = 0
+    for i, row in enumerate(tr["moves"]):
+        ours.do_move(reftrace.to_move(row))
+        if ours.is_end_of_game:
+            break
         if i % 5:
             continue
-        a = pp.state_to_uint8(ours)
-        b = rpp.state_to_tensor(ref)[0]
+        a = reftrace.plane_digests(pp.state_to_uint8(ours))
+        b = tr["planes"][done]
         assert a.shape == b.shape
-        bad = np.argwhere(a != b)
-        assert bad.size == 0, "plane mismatch at %s (move %d)" % (bad[:5], i)
-
-
-def _sweep_positions(size, n_positions, seed):
-    """Random games (restarted at game end) yielding (ours, ref) after every move."""
-    rg = refshim.ref_go()
-    rnd = random.Random(seed)
-    ours, ref = go.GameState(size), rg.GameState(size)
-    done = 0
-    while done < n_positions:
-        legal = ref.get_legal_moves()
-        mv = None if (not legal or rnd.random() < 0.03) else rnd.choice(legal)
-        ref.do_move(mv)
-        ours.do_move(mv)
+        bad = np.nonzero(a != b)[0]
+        assert bad.size == 0, "planes %s differ (move %d)" % (bad[:5].tolist(), i)
         done += 1
-        yield ours, ref
-        if ref.is_end_of_game or len(ref.history) > 3 * size * size:
-            ours, ref = go.GameState(size), rg.GameState(size)
+    assert done == len(tr["planes"]) and done > 10
 
 
 def test_rules_and_features_10k_positions():
@@ -88,51 +57,36 @@ def test_rules_and_features_10k_positions():
     19x19) -- rules state (board, liberties, ko, side to move, prisoners, legal
     moves, winner) after every move and all 46 reference feature planes of every
     position equal the reference implementation's."""
-    rpp = refshim.ref_preprocessing().Preprocess(ALL_NO_LADDER_FEATURES)
     pp = Preprocess(ALL_NO_LADDER_FEATURES)
     total = 0
     for size, n, seed in ((9, 6000, 101), (13, 2500, 102), (19, 1500, 103)):
-        for ours, ref in _sweep_positions(size, n, seed):
-            assert np.array_equal(ours.board, ref.board)
-            assert np.array_equal(ours.liberty_counts, ref.liberty_counts)
-            assert ours.ko == ref.ko and ours.current_player == ref.current_player
-            assert (ours.num_black_prisoners, ours.num_white_prisoners) == \
-                (ref.num_black_prisoners, ref.num_white_prisoners)
-            assert ours.get_legal_moves() == ref.get_legal_moves()
-            assert ours.get_winner() == ref.get_winner()
-            a = pp.state_to_uint8(ours)
-            b = rpp.state_to_tensor(ref)[0]
-            if not np.array_equal(a, b):
-                bad = np.argwhere(a != b)
-                raise AssertionError("size %d position %d: plane mismatch at %s" % (size, total, bad[:5].tolist()))
+        tr = reftrace.load("sweep_%d_%d" % (size, seed))
+        assert len(tr["moves"]) == n
+        ours = go.GameState(size)
+        for i in range(n):
+            ours.do_move(reftrace.to_move(tr["moves"][i]))
+            assert reftrace.state_digest(ours) == tr["state"][i], "size %d position %d: state differs" % (size, i)
+            assert reftrace.planes_digest(pp.state_to_uint8(ours)) == tr["planes"][i], \
+                "size %d position %d: plane mismatch" % (size, i)
             total += 1
+            new = bool(ours.is_end_of_game or len(ours.history) > 3 * size * size)
+            assert new == bool(tr["restart"][i])
+            if new:
+                ours = go.GameState(size)
     assert total >= 10000
 
 
-try:
-    from hypothesis import given, settings, strategies as st
-
-    @settings(max_examples=60, deadline=None, derandomize=True)
-    @given(size=st.sampled_from([5, 7, 9]), picks=st.lists(st.integers(0, 1 << 20), min_size=1, max_size=150))
-    def test_rules_property_random_move_sequences(size, picks):
-        """Property test (hypothesis): any sequence of choices among the legal
-        moves (pick % (n_legal + 1) == n_legal means pass) keeps the native
-        engine and the reference in the same state, including captures, ko and
-        the reference's end-of-game rule (Q9)."""
-        rg = refshim.ref_go()
-        ours, ref = go.GameState(size), rg.GameState(size)
-        for p in picks:
-            legal = ref.get_legal_moves()
-            k = p % (len(legal) + 1)
-            mv = None if k == len(legal) else legal[k]
-            ref.do_move(mv)
-            ours.do_move(mv)
-            assert np.array_equal(ours.board, ref.board)
-            assert np.array_equal(ours.liberty_counts, ref.liberty_counts)
-            assert ours.ko == ref.ko and ours.is_end_of_game == ref.is_end_of_game
-            assert ours.get_legal_moves() == ref.get_legal_moves()
-            if ref.is_end_of_game:
-                break
-        assert ours.get_winner() == ref.get_winner()
-except ImportError:  # pragma: no cover
-    pass
+def test_rules_property_random_move_sequences():
+    """Seeded move sequences (board 5 / 7 / 9, up to 150 choices among the legal moves or a pass,
+    recorded on the reference) keep the native engine and the reference in the same state, including
+    captures, ko and the reference's end-of-game rule (Q9)."""
+    tr = reftrace.load("property_sequences")
+    assert len(tr["sizes"]) == 60
+    for e, size in enumerate(tr["sizes"]):
+        ours = go.GameState(int(size))
+        lo, hi = int(tr["starts"][e]), int(tr["starts"][e + 1])
+        assert hi > lo
+        for i in range(lo, hi):
+            assert not ours.is_end_of_game
+            ours.do_move(reftrace.to_move(tr["moves"][i]))
+            assert reftrace.state_digest(ours) == tr["state"][i], "example %d, move %d" % (e, i - lo)

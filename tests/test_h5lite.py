@@ -2,14 +2,13 @@
 import os
 
 import numpy as np
-import pytest
 
 from alphago_amd.io.h5lite import H5File, H5Writer
 
-FIXTURE = "/root/reference/tests/test_data/hdf5/alphago-vs-lee-sedol-features.hdf5"
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data", "hdf5",
+                       "alphago-vs-lee-sedol-features.hdf5")
 
 
-@pytest.mark.skipif(not os.path.exists(FIXTURE), reason="reference fixture absent")
 def test_reads_reference_fixture():
     with H5File(FIXTURE) as f:
         assert sorted(f.keys()) == ["actions", "file_offsets", "states"]

@@ -17,7 +17,7 @@ from alphago_amd.search.players import GreedyPolicyPlayer, MCTSPlayer, Probabili
 
 CPU = torch.device("cpu")
 FEATS = ["board", "ones", "turns_since"]
-REF_MINI = "/root/reference/tests/test_data/minimodel.json"
+REF_MINI = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data", "minimodel.json")
 
 
 def small_policy(board=19):
@@ -66,7 +66,6 @@ def test_kernel_flip_convention(tmp_path):
     assert np.allclose(k, ours[:, :, ::-1, ::-1])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_MINI), reason="reference fixture absent")
 def test_load_reference_keras_spec():
     p = CNNPolicy.load_model(REF_MINI, device=CPU)
     assert p.preprocessor.output_dim == 12

@@ -10,21 +10,12 @@ from alphago_amd.data.convert import GameConverter
 from alphago_amd.models.policy import CNNPolicy
 from alphago_amd.train.sl import run_training
 
-REF = "/root/reference/tests/test_data"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data")
 FIXTURE = os.path.join(REF, "hdf5", "alphago-vs-lee-sedol-features.hdf5")
 
 
 def _data(tmp_path):
-    if os.path.exists(FIXTURE):
-        return FIXTURE
-    # no reference checkout: synthesise a small file in the same schema
-    from alphago_amd.io.h5lite import H5Writer
-    p = str(tmp_path / "synth.h5")
-    rng = np.random.default_rng(0)
-    with H5Writer(p) as f:
-        f["states"] = rng.integers(0, 2, (200, 12, 19, 19), dtype=np.uint8)
-        f["actions"] = rng.integers(0, 19, (200, 2), dtype=np.uint8)
-    return p
+    return FIXTURE
 
 
 def _model(tmp_path, device):
@@ -140,8 +131,6 @@ def test_chunk_cache_threaded_gather_matches_reads(tmp_path):
 def test_streamed_chunked_data_with_validation_cpu(tmp_path):
     """--resident no on an LZF-chunked file with a validation split: the prefetch worker decodes
     ahead while the epoch-end validation reads the same chunk cache."""
-    if not os.path.exists(FIXTURE):
-        pytest.skip("reference fixture not present")
     out = str(tmp_path / "out")
     meta = run_training([_model(tmp_path, "cpu"), FIXTURE, out, "--epochs", "2", "-l", "256", "-B", "16",
                          "--backend", "torch", "--resident", "no"])
