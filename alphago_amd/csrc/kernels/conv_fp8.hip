@@ -888,8 +888,24 @@ void launch_pack_weights_fp8_multi(const Fp8PackArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(pack_weights_fp8_multi_kernel, dim3(64, a.n), dim3(256), 0, st, a);
 }
 
+// floor(log2(fmt_max / m)) of an amax for the three scale kernels below; the caller subtracts its
+// margin and clamps to [lo, its upper clamp].  No float that is not finite reaches the float -> int
+// conversion (undefined there):
+//   * m == 0 (nothing seen; NaN bits fail m > 0 too): 0, the multiplier 1;
+//   * m == +Inf (a bf16 overflow after a loss spike: fmaxf keeps it and atomicMax on the float bits
+//     stores it): `lo`, so that the SMALLEST multiplier is selected.  Converting log2f(fmt_max / Inf)
+//     = -Inf saturated to INT_MIN, and INT_MIN - margin wrapped round to the largest multiplier;
+//   * a subnormal m, whose quotient overflows to +Inf: the floor is bounded before the conversion
+//     (+-256 lies beyond every clamp and every margin).
+__device__ __forceinline__ int fp8_scale_floor_log2(float m, float fmt_max, int lo) {
+  if (!(m > 0.f)) return 0;
+  if (!(m <= 3.402823466e+38f)) return lo;
+  return (int)fminf(fmaxf(floorf(log2f(fmt_max / m)), -256.f), 256.f);
+}
+
 // Per-layer weight scales, one workgroup per layer: e = floor(log2(448 / amax|w|)),
 // wscale[l] = 2^e (for packing) and the MFMA E8M0 exponent scales8[l][1] = 127 - e.
+// A layer that holds +Inf gets the lower clamp, e = -60 (the smallest multiplier).
 __global__ __launch_bounds__(1024) void fp8_weight_scales_kernel(Fp8WeightScalesArgs a) {
   __shared__ float red[16];
   const int l = blockIdx.x;
@@ -920,7 +936,7 @@ __global__ __launch_bounds__(1024) void fp8_weight_scales_kernel(Fp8WeightScales
   if (threadIdx.x == 0) {
     for (int i = 1; i < 16; ++i) m = fmaxf(m, red[i]);
     m = fmaxf(m, red[0]);
-    int e = (m > 0.f) ? (int)floorf(log2f(448.f / m)) : 0;
+    int e = fp8_scale_floor_log2(m, 448.f, -60);
     e = e < -60 ? -60 : (e > 60 ? 60 : e);
     a.wscale[l] = exp2f((float)e);
     a.scales8[2 * l + 1] = 127 - e;
@@ -940,13 +956,16 @@ void launch_fp8_weight_scales(const Fp8WeightScalesArgs& a, int L, hipStream_t s
 // and the trunk died (SL at lr 0.05, 1 seed of 3, profiles/r5/README.md).  Under the guard the outliers
 // saturate at +-448 (a clip) while the scale follows at max_drop binades per step; a falling amax
 // (growing exponent) is followed at once.  max_drop 0: the plain one-step delayed scale.
+// An infinite amax yields the smallest multiplier, e = -60 (fp8_scale_floor_log2); the guard then
+// applies to it as to any other falling exponent.
 __global__ void fp8_act_scales_kernel(unsigned* amax, int* scales8, float* osc, int L, int margin, int max_drop) {
   const int l = threadIdx.x;
   if (l >= L) return;
   unsigned mu = 0u;
   for (int k = 0; k < kFp8AmaxSlots; ++k) mu = max(mu, amax[l * kFp8AmaxSlots + k]);
   const float m = __uint_as_float(mu);
-  int e = (m > 0.f) ? (int)floorf(log2f(448.f / m)) - margin : 0;
+  int e = fp8_scale_floor_log2(m, 448.f, -60);
+  if (m > 0.f) e -= margin;
   if (max_drop > 0 && l + 1 < L) {
     const int e_prev = 127 - scales8[2 * (l + 1)];
     if (e < e_prev - max_drop) e = e_prev - max_drop;
@@ -966,13 +985,15 @@ void launch_fp8_act_scales(unsigned* amax, int* scales8, float* osc, int L, int 
 // Delayed gradient scaling for the fp8 dgrad chain: from this step's amax of dZ_l set the next
 // step's e5m2 exponent of dZ_l (gosc[l] = 2^e multiplies before conversion, gscales8[l][0] =
 // 127 - e is the MFMA's E8M0 dequantisation), `margin` bits of headroom; clears the amax.
+// An infinite amax yields the smallest multiplier, e = -100.
 __global__ void fp8_grad_scales_kernel(unsigned* amax, int* gscales8, float* gosc, int L, int margin) {
   const int l = threadIdx.x;
   if (l >= L) return;
   unsigned mu = 0u;
   for (int k = 0; k < kFp8AmaxSlots; ++k) mu = max(mu, amax[l * kFp8AmaxSlots + k]);
   const float m = __uint_as_float(mu);
-  int e = (m > 0.f) ? (int)floorf(log2f(57344.f / m)) - margin : 0;
+  int e = fp8_scale_floor_log2(m, 57344.f, -100);
+  if (m > 0.f) e -= margin;
   e = e < -100 ? -100 : (e > 100 ? 100 : e);
   gosc[l] = exp2f((float)e);
   gscales8[2 * l] = 127 - e;

@@ -468,7 +468,10 @@ def fp8_amax_buffer(L: int, device) -> torch.Tensor:
 
 
 def fp8_exponent(amax: float, margin: int = 1) -> int:
-    """Power-of-two scale exponent e so that amax * 2^e fits e4m3 with `margin` bits of headroom."""
+    """Power-of-two scale exponent e so that amax * 2^e fits e4m3 with `margin` bits of headroom.
+    Host helper for initial values only.  It returns 0 for a non-finite amax, and there it differs
+    from the device: fp8_weight_scales / fp8_act_scales / fp8_grad_scales turn an infinite amax into
+    their lower clamp (-60 / -60 / -100, the smallest multiplier); nor does it clamp to +-60."""
     import math
 
     if not amax or amax <= 0 or not math.isfinite(amax):
@@ -594,7 +597,9 @@ def conv_dgrad_fp8_bf16(dz, w8t, mbits, scales, in_scale, K: int, S: int, dx, am
 
 
 def fp8_grad_scales(amax, gscales8, gosc, margin: int = 1):
-    """Delayed e5m2 gradient scaling: gosc[l] = 2^e, gscales8[l, 0] = 127 - e from amax[l] (cleared)."""
+    """Delayed e5m2 gradient scaling: gosc[l] = 2^e, gscales8[l, 0] = 127 - e from amax[l] (cleared),
+    e = clamp(floor(log2(57344 / amax)) - margin, -100, 100).  amax 0 gives e = 0; an infinite amax
+    yields the smallest multiplier, e = -100."""
     _ops().fp8_grad_scales(amax, gscales8, gosc, margin)
 
 
@@ -624,7 +629,10 @@ def fp8_weight_scales(ws, wscale, scales8):
 def fp8_act_scales(amax, scales8, osc, margin: int = 1, max_drop: int = 0):
     """Delayed activation scaling from the per-layer output amax (also clears amax).  ``max_drop`` > 0:
     underflow guard -- each layer's exponent falls by at most that many binades per step (outliers of a
-    sudden amax rise saturate instead of flushing the bulk of the activations to zero)."""
+    sudden amax rise saturate instead of flushing the bulk of the activations to zero).
+    e = clamp(floor(log2(448 / amax)) - margin, -60, 60) for the input of layer l + 1 (osc[l] = 2^e,
+    scales8[l + 1, 0] = 127 - e); amax 0 gives e = 0.  An infinite amax (a bf16 overflow) yields the
+    smallest multiplier, e = -60, and the guard applies to it as to any other falling exponent."""
     _ops().fp8_act_scales(amax, scales8, osc, margin, max_drop)
 
 
