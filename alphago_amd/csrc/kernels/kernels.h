@@ -114,6 +114,11 @@ struct PolicyHeadArgs {
   float grad_scale;    // d(mean loss)/d(logit) scale = 1/global_batch
   float inv_temp;
   int loss_kind;       // 0 = categorical CE (SL / REINFORCE), 1 = reference RL binary CE on the softmax
+  // Regularised head (the REG kernel variants; all null / 0 launches the plain kernels):
+  //   L_b = -w_b log p_t - ent_coef * H(p) + kl_coef * KL(q || p)
+  const float* ref_probs;  // [B][S*S] anchor distribution q per board, or null
+  float* stats;            // [B][3] per-board H(p), KL(q || p) (0 without q), max |logit|, or null
+  float ent_coef, kl_coef;  // >= 0; loss_kind 0 only; neither is multiplied by weight[b]
 };
 
 struct ValueOutArgs {

@@ -174,8 +174,10 @@ void conv_wgrad_reduce_multi(const std::vector<Tensor>& slabs, const std::vector
 void policy_head(const Tensor& y, const Tensor& w, const Tensor& b, const c10::optional<Tensor>& target,
                  const c10::optional<Tensor>& legal, const c10::optional<Tensor>& weight, const c10::optional<Tensor>& dz, const c10::optional<Tensor>& loss,
                  const c10::optional<Tensor>& correct, const c10::optional<Tensor>& dhead,
-                 const c10::optional<Tensor>& probs, int64_t S, double grad_scale, double temperature, int64_t loss_kind) {
-  check_dev("policy_head", y, w, b, target, legal, weight, dz, loss, correct, dhead, probs);
+                 const c10::optional<Tensor>& probs, int64_t S, double grad_scale, double temperature, int64_t loss_kind,
+                 const c10::optional<Tensor>& ref_probs, const c10::optional<Tensor>& stats, double ent_coef,
+                 double kl_coef) {
+  check_dev("policy_head", y, w, b, target, legal, weight, dz, loss, correct, dhead, probs, ref_probs, stats);
   CHECK_BF16(y); CHECK_CONTIG(y); CHECK_F32(w); CHECK_F32(b);
   const int64_t B = y.size(0), C = y.size(3);
   TORCH_CHECK(y.size(1) == S + 2, "head input must have pad 1");
@@ -216,6 +218,23 @@ void policy_head(const Tensor& y, const Tensor& w, const Tensor& b, const c10::o
     TORCH_CHECK(probs->numel() == B * S * S, "probs must be (B, S*S)");
     a.probs = probs->data_ptr<float>();
   }
+  // entropy bonus / KL anchor / per-board diagnostics (the regularised kernel variants)
+  TORCH_CHECK(ent_coef >= 0.0 && kl_coef >= 0.0, "ent_coef and kl_coef must be >= 0");
+  TORCH_CHECK(kl_coef == 0.0 || ref_probs.has_value(), "kl_coef > 0 needs ref_probs");
+  TORCH_CHECK((ent_coef == 0.0 && kl_coef == 0.0) || (train && loss_kind == 0),
+              "ent_coef / kl_coef need a target and loss_kind 0 (CE)");
+  if (ref_probs.has_value()) {
+    CHECK_F32(*ref_probs); CHECK_CONTIG(*ref_probs);
+    TORCH_CHECK(ref_probs->numel() == B * S * S, "ref_probs must be (B, S*S)");
+    a.ref_probs = ref_probs->data_ptr<float>();
+  }
+  if (stats.has_value()) {
+    CHECK_F32(*stats); CHECK_CONTIG(*stats);
+    TORCH_CHECK(stats->numel() == B * 3, "stats must be (B, 3)");
+    a.stats = stats->data_ptr<float>();
+  }
+  a.ent_coef = (float)ent_coef;
+  a.kl_coef = (float)kl_coef;
   if (B == 0) return;
   agk::launch_policy_head(a, train, cur_stream());
   launch_check("policy_head");
@@ -855,7 +874,7 @@ TORCH_LIBRARY(alphago_amd, m) {
   m.def(
       "policy_head(Tensor y, Tensor w, Tensor b, Tensor? target, Tensor? legal, Tensor? weight, Tensor(a!)? dz, Tensor(b!)? loss, "
       "Tensor(c!)? correct, Tensor(d!)? dhead, Tensor(e!)? probs, int S, float grad_scale, float temperature, "
-      "int loss_kind=0) -> ()");
+      "int loss_kind=0, Tensor? ref_probs=None, Tensor(f!)? stats=None, float ent_coef=0.0, float kl_coef=0.0) -> ()");
   m.def("head_logits(Tensor y, Tensor w, Tensor b, Tensor(a!) z, int S) -> ()");
   m.def("head_backward(Tensor y, Tensor w, Tensor dlogits, Tensor(a!) dz, Tensor(b!) dhead, int S, "
         "Tensor(c!)? dz8=None, Tensor? dz8_scale=None, Tensor(d!)? dz8_amax=None) -> ()");

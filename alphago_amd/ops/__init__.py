@@ -277,11 +277,18 @@ def wgrad_direct_supported(cout_p: int, cin_p: int, cin_real: int, K: int) -> bo
 
 
 def policy_head_train(y, w, b, target, dz, loss, correct, dhead, S: int, grad_scale: float, weight=None,
-                      bce: bool = False):
+                      bce: bool = False, ref_probs=None, stats=None, ent_coef: float = 0.0, kl_coef: float = 0.0,
+                      probs=None):
     """Fused policy head training step; ``bce`` selects the reference RL loss
-    (binary CE on the softmax, reinforcement_policy_trainer.py:109) instead of CE."""
-    _ops().policy_head(y, w, b, target, None, weight, dz, loss, correct, dhead, None, S, grad_scale, 1.0,
-                       1 if bce else 0)
+    (binary CE on the softmax, reinforcement_policy_trainer.py:109) instead of CE.
+
+    ``ent_coef`` (beta) and ``kl_coef`` (kappa, needs the anchor distribution ``ref_probs`` (B, S*S))
+    add -beta H(p) + kappa KL(ref_probs || p) per board to the CE objective (not with ``bce``; neither
+    is multiplied by ``weight``).  ``stats`` (B, 3) receives per board H(p), KL(ref_probs || p) (0
+    without ``ref_probs``) and max |logit|; ``probs`` (B, S*S) the softmax itself.  With all of them
+    left out the plain kernels run."""
+    _ops().policy_head(y, w, b, target, None, weight, dz, loss, correct, dhead, probs, S, grad_scale, 1.0,
+                       1 if bce else 0, ref_probs, stats, float(ent_coef), float(kl_coef))
 
 
 def head_grad_sums(dhead, loss, correct, grad, sums):
@@ -289,8 +296,11 @@ def head_grad_sums(dhead, loss, correct, grad, sums):
     _ops().head_grad_sums(dhead, loss, correct, grad, sums)
 
 
-def policy_head_probs(y, w, b, probs, S: int, legal=None, temperature: float = 1.0):
-    _ops().policy_head(y, w, b, None, legal, None, None, None, None, None, probs, S, 0.0, temperature)
+def policy_head_probs(y, w, b, probs, S: int, legal=None, temperature: float = 1.0, ref_probs=None, stats=None):
+    """Softmax of the head (renormalised over ``legal``); ``stats`` (B, 3): per-board entropy,
+    KL(ref_probs || p) and max |logit| as in ``policy_head_train``."""
+    _ops().policy_head(y, w, b, None, legal, None, None, None, None, None, probs, S, 0.0, temperature, 0,
+                       ref_probs, stats)
     return probs
 
 

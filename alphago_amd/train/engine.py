@@ -939,11 +939,45 @@ class HipPolicyTrainer(HipConvTrainer):
 
     policy_loss = "ce"  # or "bce": the reference RL loss (binary CE on the softmax)
 
+    # Regularised objective of the fused head (policy_loss "ce" only), per board
+    #   L_b = -w_b log p_t - ent_coef * H(p) + kl_coef * KL(ref_probs || p),
+    # each divided by the global batch like the CE term.  All off (the defaults): the plain head
+    # kernels run and nothing below is allocated.
+    ent_coef = 0.0
+    kl_coef = 0.0
+    ref_probs = None        # (batch, S*S) f32 anchor distribution, filled by the caller
+    collect_stats = False   # head_stats (batch, 3) <- H(p), KL(ref_probs || p), max |logit| per board on
+    head_stats = None       # every compute_grads / evaluate
+    collect_probs = False   # head_probs (batch, S*S) <- p of the last compute_grads
+    head_probs = None
+
+    def _head_extras(self, train: bool) -> dict:
+        """Keyword arguments of the regularised head ({}: the plain kernels, today's call);
+        ``train=False`` (evaluate): the diagnostics only."""
+        if not (self.collect_stats or (train and (self.ent_coef or self.kl_coef or self.collect_probs))):
+            return {}
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the captured SL step runs the plain head: leave ent_coef, kl_coef and "
+                               "collect_* off in graph mode")
+        kw = {"ref_probs": self.ref_probs}
+        if self.collect_stats:
+            if self.head_stats is None:
+                self.head_stats = torch.zeros(self.batch, 3, device=self.device)
+            kw["stats"] = self.head_stats
+        if train:
+            kw.update(ent_coef=self.ent_coef, kl_coef=self.kl_coef)
+            if self.collect_probs:
+                if self.head_probs is None:
+                    self.head_probs = torch.zeros(self.batch, self.S * self.S, device=self.device)
+                kw["probs"] = self.head_probs
+        return kw
+
     def _head_train(self, targets, gscale, weight):
         hw = self.fp.views["head_w"].view(-1)
         hb = self.fp.views["head_b"]
         ops.policy_head_train(self.Y[-1], hw, hb, self.tgt, self.DZ[-1], self.loss, self.correct, self.dhead,
-                              self.S, gscale, weight=weight, bce=self.policy_loss == "bce")
+                              self.S, gscale, weight=weight, bce=self.policy_loss == "bce",
+                              **self._head_extras(True))
         ho, hn = self.fp.segments["head_w"]
         # head gradient and the step's two metric sums in one launch (a fresh 2-vector per step, so
         # the returned scalars stay valid after the next step)
@@ -959,8 +993,21 @@ class HipPolicyTrainer(HipConvTrainer):
         self.forward_trunk(planes, None, targets, self.tgt)
         hw = self.fp.views["head_w"].view(-1)
         ops.policy_head_train(self.Y[-1], hw, self.fp.views["head_b"], self.tgt, self.DZ[-1], self.loss,
-                              self.correct, self.dhead, self.S, 0.0)
+                              self.correct, self.dhead, self.S, 0.0, **self._head_extras(False))
         return self.loss.sum(), self.correct.sum()
+
+    @torch.no_grad()
+    def policy_stats(self, planes: torch.Tensor, ref_probs: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(batch, 3) per board: entropy H(p), KL(ref_probs || p) (0 without ``ref_probs``) and
+        max |logit| of the current weights.  Forward only (the trunk, then the head in its inference
+        form): neither the gradient nor the schedule is touched."""
+        if planes.shape[0] != self.batch:
+            raise ValueError("batch %d != configured %d" % (planes.shape[0], self.batch))
+        self.forward_trunk(planes)
+        out = torch.empty(self.batch, 3, device=self.device)
+        ops.policy_head_probs(self.Y[-1], self.fp.views["head_w"].view(-1), self.fp.views["head_b"], None, self.S,
+                              ref_probs=ref_probs, stats=out)
+        return out
 
 
 class HipValueTrainer(HipConvTrainer):
@@ -1126,19 +1173,67 @@ class TorchPolicyTrainer(_TorchTrainerBase):
         correct = ((logits.argmax(1) == t) & valid).float()
         w = valid.float() if weight is None else valid.float() * weight
         norm = planes.shape[0] * self.env.world_size
+        regularised = bool(self.ent_coef or self.kl_coef)
         if self.policy_loss == "bce":
+            if regularised:
+                raise ValueError("ent_coef / kl_coef go with the CE loss, not the reference binary CE")
             # reference RL loss: Keras binary_crossentropy on the softmax output,
             # mean over the S*S outputs, clipped probabilities
             prob = torch.softmax(logits, 1).clamp(1e-7, 1 - 1e-7)
             y = torch.nn.functional.one_hot(t.clamp_min(0), logits.shape[1]).to(prob.dtype)
             per = -(y * prob.log() + (1 - y) * (1 - prob).log()).mean(1) * valid
+            if self.collect_stats:
+                self._policy_stats(logits.detach(), self.ref_probs, store=True)
             return (per * w).sum() / norm, per, correct
         logp = torch.log_softmax(logits, 1)
         lt = logp.gather(1, t.clamp_min(0).unsqueeze(1)).squeeze(1)
         per = -torch.clamp(lt, min=math.log(1e-7), max=math.log(1 - 1e-7)) * valid
         # gradient of mean CE (unclipped, see kernels/head.hip); optional per-board weights (REINFORCE)
         obj = (-(lt * w)).sum() / norm
+        if regularised:
+            # - ent_coef * H(p) + kl_coef * KL(ref_probs || p) per board with a target, under the same
+            # 1 / norm as the CE term and not multiplied by the reward weight
+            p = logp.exp()
+            if self.ent_coef:
+                obj = obj + self.ent_coef * ((p * logp).sum(1) * valid).sum() / norm
+            if self.kl_coef:
+                if self.ref_probs is None:
+                    raise ValueError("kl_coef > 0 needs ref_probs")
+                q = self.ref_probs.to(logp.dtype)
+                obj = obj + self.kl_coef * ((torch.xlogy(q, q) - q * logp).sum(1) * valid).sum() / norm
+        if self.collect_stats:
+            self._policy_stats(logits.detach(), self.ref_probs, store=True)
+        if self.collect_probs and torch.is_grad_enabled():  # compute_grads, not evaluate
+            self.head_probs = logp.detach().exp()
         return obj, per, correct
+
+    ent_coef = 0.0   # the surface of HipPolicyTrainer (see there)
+    kl_coef = 0.0
+    ref_probs = None
+    collect_stats = False
+    head_stats = None
+    collect_probs = False
+    head_probs = None
+
+    def _policy_stats(self, logits, ref_probs, store: bool = False) -> torch.Tensor:
+        logp = torch.log_softmax(logits, 1)
+        p = logp.exp()
+        ent = -(p * logp).sum(1)
+        if ref_probs is None:
+            kl = torch.zeros_like(ent)
+        else:
+            q = ref_probs.to(logp.dtype)
+            kl = (torch.xlogy(q, q) - q * logp).sum(1)
+        out = torch.stack([ent, kl, logits.abs().amax(1)], 1).float()
+        if store:
+            self.head_stats = out
+        return out
+
+    @torch.no_grad()
+    def policy_stats(self, planes, ref_probs=None) -> torch.Tensor:
+        """(batch, 3) per board: H(p), KL(ref_probs || p) (0 without ``ref_probs``), max |logit|;
+        forward only."""
+        return self._policy_stats(self.net.logits_torch(planes.to(self.dtype)), ref_probs)
 
 
 class TorchValueTrainer(_TorchTrainerBase):

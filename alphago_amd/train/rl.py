@@ -52,7 +52,8 @@ from .engine import make_policy_trainer
 
 
 def rl_update(trainer, records, B: int, device, loss: str = "reinforce", baseline: str = "mean",
-              clip_grad_norm: float = 0.0, weight_decay: float = 0.0) -> dict:
+              clip_grad_norm: float = 0.0, weight_decay: float = 0.0, entropy_coef: float = 0.0,
+              kl_coef: float = 0.0, anchor=None, max_kl: float = 0.0, stats: bool = False) -> dict:
     """One policy-gradient step over all learner positions of a batch of games
     (``loss="reference"``: the reference's per-game binary-CE steps instead).
 
@@ -67,9 +68,30 @@ def rl_update(trainer, records, B: int, device, loss: str = "reinforce", baselin
     gradient norm stayed at 2-6 for 22 iterations, then grew to 65, 373 and 1.6e5 and the weights
     diverged (profiles/r6/README.md).  ``weight_decay``: L2 term wd * w added to the gradient (before the
     clip): the ReLU trunk has no normalisation, and a sharpening policy grows its weights and with them
-    the gradient norm (2 -> 100 over 60 iterations at lr 0.003, profiles/r6/README.md)."""
+    the gradient norm (2 -> 100 over 60 iterations at lr 0.003, profiles/r6/README.md).
+
+    The three above bound the size of a gradient; the next three bound the policy itself (all off by
+    default, computed inside the fused head).  ``entropy_coef`` (beta) and ``kl_coef`` (kappa) add
+        - beta * mean H(p(.|s)) + kappa * mean KL(anchor(.|s) || p(.|s))
+    over the iteration's learner positions to the objective; ``anchor`` is a callable
+    ``planes -> (len, S*S)`` probabilities (no legal mask) of a frozen policy.  ``max_kl`` > 0 (plain
+    SGD only) halves the applied step, at most 8 times, until the mean KL(p_old || p_new) over this
+    rank's first chunk (all-reduced) is at most ``max_kl``, and restores the old weights if it never
+    is; the result reports ``kl_step``, ``kl_backtracks`` and ``step_scale`` (0.5^k, 0 after a restore
+    or a skipped update).  ``stats`` or any of these options adds the iteration's ``entropy`` (mean),
+    ``kl_anchor`` (mean, with an anchor) and ``max_abs_logit`` (max) to the result."""
     if loss == "reference":
+        if entropy_coef or kl_coef or max_kl or stats:
+            raise ValueError("entropy_coef, kl_coef, max_kl and stats go with loss='reinforce'")
         return _reference_bce_update(trainer, records, B, device)
+    if entropy_coef < 0 or kl_coef < 0 or max_kl < 0:
+        raise ValueError("entropy_coef, kl_coef and max_kl must be >= 0")
+    if kl_coef > 0 and anchor is None:
+        raise ValueError("kl_coef > 0 needs an anchor policy")
+    if max_kl > 0 and trainer.sched.optimizer != "sgd":
+        raise ValueError("max_kl scales the applied step: plain SGD only (optimizer %r keeps moments)"
+                         % trainer.sched.optimizer)
+    diag = bool(stats or entropy_coef or kl_coef or max_kl)
     X, T, Z = [], [], []
     for planes, moves, w, c in zip(records.planes, records.moves, records.winners, records.learner_colors):
         if len(moves) == 0:
@@ -98,7 +120,25 @@ def rl_update(trainer, records, B: int, device, loss: str = "reinforce", baselin
     elif baseline != "none":
         raise ValueError("baseline must be 'mean' or 'none'")
     scale = float(B) / max(1, n)
-    _accumulate_grads(trainer, X, T, (Z - b) * scale, B, device, n_chunks)
+    if not diag:
+        _accumulate_grads(trainer, X, T, (Z - b) * scale, B, device, n_chunks)
+    else:
+        # per chunk coef * B / n: the regularisers are means over the n positions like the REINFORCE term
+        # (padding boards have target -1 and get none)
+        acc = {"sum": torch.zeros(2, dtype=torch.float64, device=device), "count": 0,
+               "max": torch.zeros((), device=device), "probe": None}
+        prev = (trainer.ent_coef, trainer.kl_coef, trainer.collect_stats, trainer.collect_probs, trainer.ref_probs)
+        trainer.ent_coef, trainer.kl_coef = entropy_coef * scale, kl_coef * scale
+        trainer.collect_stats, trainer.collect_probs = True, max_kl > 0
+        if anchor is None:
+            trainer.ref_probs = None
+        try:
+            _accumulate_grads(trainer, X, T, (Z - b) * scale, B, device, n_chunks, anchor=anchor, diag=acc)
+        finally:
+            (trainer.ent_coef, trainer.kl_coef, trainer.collect_stats, trainer.collect_probs) = prev[:4]
+            if anchor is None:
+                trainer.ref_probs = prev[4]
+        w0 = trainer.fp.flat.clone() if max_kl > 0 else None
     if weight_decay > 0:
         trainer.fp.grad.add_(trainer.fp.flat, alpha=weight_decay)
     gnorm = float(trainer.fp.grad.norm())
@@ -109,13 +149,65 @@ def rl_update(trainer, records, B: int, device, loss: str = "reinforce", baselin
         trainer.fp.grad.mul_(clip_grad_norm / gnorm)
     if not skipped:
         trainer.apply_update()
-    return {"positions": n, "mean_reward": mean_reward, "baseline": b, "grad_norm": gnorm, "skipped": skipped}
+    info = {"positions": n, "mean_reward": mean_reward, "baseline": b, "grad_norm": gnorm, "skipped": skipped}
+    if diag:
+        # sums and counts over all ranks, as the baseline's
+        tot = torch.cat([acc["sum"], torch.tensor([float(acc["count"])], dtype=torch.float64, device=device)])
+        if agdist.env().backend != "nccl":
+            tot = tot.cpu()
+        agdist.all_reduce_sum_(tot)
+        cnt = max(1.0, float(tot[2]))
+        info["entropy"] = float(tot[0]) / cnt
+        if anchor is not None:
+            info["kl_anchor"] = float(tot[1]) / cnt
+        info["max_abs_logit"] = float(agdist.all_reduce_max(float(acc["max"])))
+        if max_kl > 0:
+            if skipped:
+                info.update(kl_step=0.0, kl_backtracks=0, step_scale=0.0)
+            else:
+                info.update(_bound_step_kl(trainer, w0, acc["probe"], max_kl, device))
+    return info
 
 
-def _accumulate_grads(trainer, X, T, W, B, device, n_chunks) -> None:
+def _bound_step_kl(trainer, w0, probe, max_kl: float, device) -> dict:
+    """After ``apply_update``: halve the step w - w0 (at most 8 times) until the mean KL(p_old || p_new)
+    over the probe chunk's real positions, all-reduced, is at most ``max_kl``; restore w0 if it never is.
+    Every rank takes the same decisions (they depend on all-reduced values only)."""
+    planes, q_old, real = probe
+
+    def measure() -> float:
+        kl = trainer.policy_stats(planes, q_old)[:real, 1]
+        tot = torch.stack([kl.sum().double(), torch.tensor(float(real), dtype=torch.float64, device=kl.device)])
+        if agdist.env().backend != "nccl":
+            tot = tot.cpu()
+        agdist.all_reduce_sum_(tot)
+        return float(tot[0] / tot[1]) if float(tot[1]) > 0 else 0.0
+
+    def set_weights(fn) -> None:
+        with torch.no_grad():
+            fn(trainer.fp.flat)
+        if hasattr(trainer, "repack"):  # the HIP trainer's device copies of the master weights
+            trainer.repack()
+
+    k, kl = 0, measure()
+    while not kl <= max_kl and k < 8:  # a NaN KL counts as over the bound
+        set_weights(lambda flat: flat.sub_(w0).mul_(0.5).add_(w0))
+        k += 1
+        kl = measure()
+    if not kl <= max_kl:
+        set_weights(lambda flat: flat.copy_(w0))
+        return {"kl_step": 0.0, "kl_backtracks": k, "step_scale": 0.0}
+    return {"kl_step": kl, "kl_backtracks": k, "step_scale": 0.5 ** k}
+
+
+def _accumulate_grads(trainer, X, T, W, B, device, n_chunks, anchor=None, diag=None) -> None:
     """trainer.fp.grad <- sum over B-sized chunks of the weighted-loss gradients
     (padding boards carry target -1 and weight 0).  Chunks accumulate locally
-    (``compute_grads(reduce=False)``); the sum is all-reduced ONCE."""
+    (``compute_grads(reduce=False)``); the sum is all-reduced ONCE.
+
+    ``anchor``: ``trainer.ref_probs`` is filled with the anchor's distribution of every chunk.
+    ``diag`` (rl_update's accumulator): sums of the real boards' ``trainer.head_stats`` columns, and the
+    first chunk's (planes, ``head_probs``, real boards) as the KL-bounded step's probe."""
     C, S = trainer.net.trunk.in_planes, trainer.net.board
     n_chunks = max(1, n_chunks)
     acc = torch.zeros_like(trainer.fp.grad) if n_chunks > 1 else None
@@ -132,8 +224,21 @@ def _accumulate_grads(trainer, X, T, W, B, device, n_chunks) -> None:
             tb = np.concatenate([tb, np.full(pad, -1, np.int32)])
             wb = np.concatenate([wb, np.zeros(pad, np.float32)])
         xt = xb.to(device) if on_dev else torch.from_numpy(xb).to(device)
+        if anchor is not None:
+            if trainer.ref_probs is None:
+                trainer.ref_probs = torch.zeros(B, S * S, device=device)
+            trainer.ref_probs.copy_(torch.as_tensor(anchor(xt)).detach())
         trainer.compute_grads(xt, torch.from_numpy(tb).to(device), None,
                               torch.from_numpy(wb.astype(np.float32)).to(device), reduce=False)
+        if diag is not None:
+            real = B - pad
+            st = trainer.head_stats[:real]
+            if real:
+                diag["sum"] += st[:, :2].sum(0).double()
+                diag["max"] = torch.maximum(diag["max"], st[:, 2].max())
+            diag["count"] += real
+            if c == 0 and trainer.collect_probs:
+                diag["probe"] = (xt, trainer.head_probs.clone(), real)
         if acc is not None:
             acc += trainer.fp.grad
     if acc is not None:
@@ -206,6 +311,19 @@ def _parser():
                    help="reinforce: scale each update's gradient to at most this L2 norm and skip non-finite "
                         "updates (0: off)")
     p.add_argument("--weight-decay", type=float, default=0.0, help="reinforce: L2 weight decay added to the gradient")
+    p.add_argument("--entropy-coef", type=float, default=0.0,
+                   help="reinforce: entropy bonus, -coef * mean H(p) added to the objective (0: off; 0.01 is a "
+                        "conventional starting point, not measured on this net)")
+    p.add_argument("--kl-coef", type=float, default=0.0,
+                   help="reinforce: coef * mean KL(initial policy || p) added to the objective, the anchor being "
+                        "the frozen initial weights (0: off; 0.1 is a conventional starting point, not measured)")
+    p.add_argument("--max-kl", type=float, default=0.0,
+                   help="reinforce: halve each update (at most 8 times) until the mean KL(old || new) over the first "
+                        "chunk is at most this, else drop it (0: off; 0.01 is a conventional starting point, not "
+                        "measured)")
+    p.add_argument("--log-policy-stats", action="store_true",
+                   help="record per iteration the mean policy entropy, the mean KL from the initial policy and the "
+                        "largest |logit| over the learner's positions (one more inference pass per chunk)")
     p.add_argument("--eval-every", type=int, default=0,
                    help="every N iterations play --eval-games games against the initial weights (recorded as "
                         "eval_win_rate); the best snapshot is kept as model_folder/best.hdf5 (0: off)")
@@ -242,8 +360,13 @@ def run(cmd_line_args: Optional[List[str]] = None) -> dict:
     opponent = BatchedSampler(opp_pol, args.temperature, seed=args.seed * 37 + env.rank + 1)
     ref_pol = ev_learner = ev_ref = None
     best = {"eval_win_rate": -1.0, "iteration": -1, "path": None}
-    if args.eval_every > 0:  # the fixed reference: the initial weights, with evaluation samplers of their own
+    # the fixed reference: the initial weights (evaluation opponent; anchor of --kl-coef and of the logged KL).
+    # It is reloaded from its path on resume and holds no state.
+    want_anchor = args.loss == "reinforce" and (args.kl_coef > 0 or args.log_policy_stats)
+    if args.eval_every > 0 or want_anchor:
         ref_pol = CNNPolicy.load_model(args.initial_json, device=dev, weights_file=args.initial_weights)
+    anchor = (lambda planes: ref_pol.engine.evaluate(planes, None)) if want_anchor else None
+    if args.eval_every > 0:  # evaluation samplers of their own
         ev_learner = BatchedSampler(learner_pol, args.temperature, seed=args.seed * 41 + env.rank + 7)
         ev_ref = BatchedSampler(ref_pol, args.temperature, seed=args.seed * 43 + env.rank + 9)
     pool: List[Optional[str]] = [None]  # None = the initial weights
@@ -299,7 +422,8 @@ def run(cmd_line_args: Optional[List[str]] = None) -> dict:
         rec = play_games(learner, opponent, args.game_batch_size, size=size, max_moves=args.max_moves, rng=rng,
                          standard_two_pass=args.standard_two_pass)
         info = rl_update(trainer, rec, args.minibatch, dev, args.loss, args.baseline, args.clip_grad_norm,
-                         args.weight_decay)
+                         args.weight_decay, entropy_coef=args.entropy_coef, kl_coef=args.kl_coef, anchor=anchor,
+                         max_kl=args.max_kl, stats=args.log_policy_stats)
         learner_pol.refresh()
         wins = sum(1 for w, c in zip(rec.winners, rec.learner_colors) if w == c)
         tot = torch.tensor([float(wins), float(len(rec.winners)), float(sum(rec.lengths))], dtype=torch.float64,
