@@ -61,12 +61,12 @@ class HipTrunkInference:
         self.fp8_min_batch = int(os.environ.get("ALPHAGO_AMD_FP8_MIN_BATCH", "256"))
         dev = self.device
         # packed on the engine's device whatever device the module's parameters are on
-        self.wf = [ops.packed_weight_like(tr.weights[l], self.C0p if l == 0 else self.Fp, self.Fp, device=dev)
-                   for l in range(self.L)]
-        # weight-stationary copies (tile 40, small buckets) of the layers that kernel covers
-        self.wf_ws = [ops.ws_packed_like(self.wf[l]) if ops.conv_ws_supported(self.Fp, self.C0p if l == 0 else self.Fp,
-                                                                              self.K[l]) else None
-                      for l in range(self.L)]
+        self.cin_p = [self.C0p] + [self.Fp] * (self.L - 1)  # padded input channels of each layer
+        self.wf = [ops.packed_weight_like(tr.weights[l], self.cin_p[l], self.Fp, device=dev) for l in range(self.L)]
+        # weight-stationary copies (tile 40, small buckets) of the layers that kernel covers, whatever
+        # buckets come later
+        self.wf_ws = [ops.ws_packed_like(self.wf[l]) if ops.conv_ws_supported(self.Fp, self.cin_p[l], self.K[l])
+                      else None for l in range(self.L)]
         self.bias_p = [torch.zeros(self.Fp, device=dev) for _ in range(self.L)]
         self.head_w = torch.zeros(self.F, device=dev)
         self.head_b = torch.zeros(1, device=dev)
@@ -116,7 +116,7 @@ class HipTrunkInference:
         self.head_b.copy_(self.net.head_b.detach().view(-1))
         if self.precision == "fp8":
             for l in range(self.L):
-                self.w8[l], self.ew[l] = ops.pack_weights_fp8(ws[l], self.Fp, self.C0p if l == 0 else self.Fp)
+                self.w8[l], self.ew[l] = ops.pack_weights_fp8(ws[l], self.Fp, self.cin_p[l])
                 self.scales8[l, 1] = 127 - self.ew[l]
             self.calibrated = False  # activation ranges change with the weights
         self._after_sync()
@@ -138,16 +138,14 @@ class HipTrunkInference:
         bk.legal = torch.ones((B, S * S), dtype=torch.uint8, device=dev)
         bk.X0 = ops.padded_empty(B, S, self.P0, self.C0p, dev)
         bk.Y = [ops.padded_empty(B, S, 1, self.Fp, dev) for _ in range(2)]
-        # small buckets: the split-K 32-pixel conv (ops.conv_fwd_splitk), fp32 partials in bk.ws
+        # small buckets (ops.plan_conv): the weight-stationary kernel (tile 40) where it applies, else the
+        # split-K 32-pixel conv (ops.conv_fwd_splitk), fp32 partials in bk.ws; not the buckets an fp8
+        # engine runs in fp8 (their bf16 calibration forward runs the plain tiles)
         M = B * S * S
-        bk.sk = [1 if (self.precision == "fp8" and B >= self.fp8_min_batch) else
-                 ops.splitk_nsplit(M, self.Fp, self.C0p if l == 0 else self.Fp, self.K[l]) for l in range(self.L)]
-        # ... or the weight-stationary kernel (tile 40) where it applies (it replaces split-K there)
-        bk.wst = [self.precision != "fp8" or B < self.fp8_min_batch for _ in range(self.L)]
-        bk.wst = [bk.wst[l] and self.wf_ws[l] is not None and
-                  ops.ws_applies(M, self.Fp, self.C0p if l == 0 else self.Fp, self.K[l]) for l in range(self.L)]
-        bk.sk = [1 if bk.wst[l] else bk.sk[l] for l in range(self.L)]
-        bk.ws = torch.empty(max(bk.sk) * M * self.Fp, device=dev) if max(bk.sk) > 1 else None
+        small = self.precision != "fp8" or B < self.fp8_min_batch
+        bk.plan = [ops.plan_conv(M, self.Fp, c, K, small=small) for c, K in zip(self.cin_p, self.K)]
+        n = ops.splitk_workspace_numel(bk.plan, M, self.Fp)
+        bk.ws = torch.empty(n, device=dev) if n else None
         if self.precision == "fp8":
             bk.X08 = torch.zeros(bk.X0.shape, dtype=torch.uint8, device=dev)
             bk.Y8 = [torch.zeros(bk.Y[0].shape, dtype=torch.uint8, device=dev) for _ in range(2)]
@@ -192,13 +190,8 @@ class HipTrunkInference:
         x, pin = bk.X0, self.P0
         for l in range(self.L):
             y = bk.Y[l % 2]
-            if bk.wst[l]:
-                ops.conv_fwd(x, self.wf_ws[l], self.bias_p[l], y, self.K[l], self.S, pin, 1, tile=40)
-            elif bk.sk[l] > 1:
-                ops.conv_fwd_splitk(x, self.wf[l], self.bias_p[l], y, self.K[l], self.S, pin, 1, ops.MODE_BIAS_RELU,
-                                    None, bk.ws, bk.sk[l])
-            else:
-                ops.conv_fwd(x, self.wf[l], self.bias_p[l], y, self.K[l], self.S, pin, 1)
+            ops.conv_planned(bk.plan[l], x, self.wf[l], self.wf_ws[l], self.bias_p[l], y, self.K[l], self.S, pin,
+                             sk_ws=bk.ws)
             if getattr(self, "_calibrating", False):
                 self._cal_amax[l] = max(self._cal_amax[l], float(y.amax()))
             x, pin = y, 1

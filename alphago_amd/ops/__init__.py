@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import os
 import threading
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -197,6 +197,47 @@ def conv_fwd_splitk(x, w_packed, bias, y, K: int, S: int, Pin: int, Po: int, mod
     partials in ``ws``, >= nsplit * M * Cout floats) and one finishing pass: modes 0 (bias + ReLU,
     optional bitmask), 2 (none), 3 (bitmask dgrad)."""
     _ops().conv_fwd_splitk(x, w_packed, bias, y, K, S, Pin, Po, mode, mbits, ws, nsplit)
+    return y
+
+
+class ConvPlan(NamedTuple):
+    """Which kernel runs one bf16 conv layer (forward or bitmask dgrad) at one batch: ``plan_conv``."""
+    kind: str    # "ws" (weight-stationary, tile 40), "splitk" (32-pixel tile, K loop split) or "tile"
+    nsplit: int  # split count of "splitk", otherwise 1
+    tile: int    # conv_fwd's tile argument ("tile": 0 = the library chooses)
+
+
+def plan_conv(M: int, cout_p: int, cin_p: int, K: int, *, training: bool = False, tile: int = 0,
+              small: bool = True) -> ConvPlan:
+    """The one place that picks the kernel of a bf16 conv layer with M output pixels: the weight-stationary
+    tile where ``ws_applies``, else the split-K tile where ``splitk_nsplit`` is above 1, else the library's
+    tile -- the only outcome with an explicit ``tile`` or ``small=False`` (fp8 engines, kernel-lab runs).
+    Kind "tile" with tile 0 means the library chooses among its own tiles (conv.hip launch_fwd_t).
+    ALPHAGO_AMD_WS and ALPHAGO_AMD_SPLITK are read at every call."""
+    if tile == 0 and small:
+        if ws_applies(M, cout_p, cin_p, K, training=training):
+            return ConvPlan("ws", 1, 40)
+        ns = splitk_nsplit(M, cout_p, cin_p, K)
+        if ns > 1:
+            return ConvPlan("splitk", ns, 38)
+    return ConvPlan("tile", 1, tile)
+
+
+def splitk_workspace_numel(plans, M: int, cout_p: int) -> int:
+    """Floats of the fp32 partials workspace the split-K plans among ``plans`` (None entries skipped)
+    share: the largest ``nsplit * M * cout_p``; 0 when none splits."""
+    return max([p.nsplit * M * cout_p for p in plans if p is not None and p.kind == "splitk"], default=0)
+
+
+def conv_planned(plan: ConvPlan, x, w, w_ws, bias, y, K: int, S: int, pin: int, mode: int = MODE_BIAS_RELU,
+                 mbits=None, sk_ws=None):
+    """The one launch of a planned conv layer into ``y`` (output border 1).  ``w``: the standard pack,
+    ``w_ws``: its weight-stationary copy ("ws" plans only), ``sk_ws``: the split-K workspace.  The bitmask
+    dgrad is ``mode=MODE_MASKBITS`` on the transposed packs without bias."""
+    if plan.kind == "splitk":
+        _ops().conv_fwd_splitk(x, w, bias, y, K, S, pin, 1, mode, mbits, sk_ws, plan.nsplit)
+    else:
+        _ops().conv_fwd(x, w_ws if plan.kind == "ws" else w, bias, None, y, K, S, pin, 1, mode, mbits, plan.tile)
     return y
 
 

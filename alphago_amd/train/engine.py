@@ -30,7 +30,7 @@ from __future__ import annotations
 
 import os
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -187,6 +187,19 @@ WGRAD_DIRECT_MAX_PIXELS = 4 * 361
 MERGED_REDUCE_MAX_PIXELS = 0
 
 
+def _trunk_named(tr) -> List[Tuple[str, torch.nn.Parameter]]:
+    """(name, parameter) of a ConvStack in flat-buffer order: w0, b0, w1, b1, ..."""
+    return [(n % l, p[l]) for l in range(tr.layers) for n, p in (("w%d", tr.weights), ("b%d", tr.biases))]
+
+
+class _Layer(NamedTuple):
+    """Shape of a trunk layer as the conv kernels take it (HipConvTrainer._layers; its input buffer and
+    border: _layer_in)."""
+    K: int         # kernel width
+    cin_p: int     # padded input channels
+    cin_real: int  # input planes the wgrad kernels read, 0 = all (only layer 0 has fewer than cin_p)
+
+
 class HipConvTrainer:
     """MFMA conv-trunk training engine; subclasses provide the head."""
 
@@ -240,6 +253,27 @@ class HipConvTrainer:
                        and os.environ.get("ALPHAGO_AMD_OVERLAP", "auto") != "0")
         self.overlap = overlap
         self.comm_events = None  # list: record the all-reduce wait of each backward as (start, end) events
+        self._init_buffers(net)
+        self._init_plans(wgrad_target_wgs, wgrad_direct, reduce_stream)
+        self.wgrad_ksub = int(wgrad_ksub)
+        self._init_streams(reduce_stream, wgrad_priority)
+        self._init_buckets(bucket_mb, merged_reduce)
+        self.fp8_wgrad = False
+        self._w8layers = set()
+        if precision == "fp8":
+            self._init_fp8(fp8_dgrad, fp8_wgrad)
+        # Keras-SGD schedule mirrored on the device (float64 {lr0, decay, iterations, lr}) so that
+        # the SGD step reads its learning rate from memory: the whole step is graph-capturable
+        self._sched_dev = torch.zeros(8, dtype=torch.float64, device=self.device)
+        # fused SGD + bf16 packs (ops.sgd_pack); ALPHAGO_AMD_FUSED_UPDATE=0: sgd_update + pack_weights
+        self._fused_update = os.environ.get("ALPHAGO_AMD_FUSED_UPDATE", "1") == "1"
+        self._pack_plan = None
+        self.enable_graphs(False)
+        self._init_head()
+        self.repack()
+
+    def _init_buffers(self, net) -> None:
+        """Trunk geometry, the flat master parameters, the weight packs and the activation buffers."""
         tr = net.trunk
         self.S = net.board
         self.L = tr.layers
@@ -252,29 +286,26 @@ class HipConvTrainer:
         if self.F > 256:
             raise ValueError("head kernels support up to 256 filters")
         self.P0 = self.K[0] // 2
-        named = []
-        for l in range(self.L):
-            named.append(("w%d" % l, tr.weights[l]))
-            named.append(("b%d" % l, tr.biases[l]))
+        self._M = self.batch * self.S * self.S  # output pixels of a layer
+        self._layers = [_Layer(self.K[0], self.C0p, self.C0)] + [_Layer(K, self.Fp, 0) for K in self.K[1:]]
         head = self._head_named_params()
         self.head_names = [n for n, _ in head]
-        self.fp = FlatParams(named + head, self.device)
+        self.fp = FlatParams(_trunk_named(tr) + head, self.device)
         if self.env.distributed:
             agdist.broadcast_(self.fp.flat, 0)
         # optimizer state (momentum velocity / Adam moments), flat fp32 like the master weights
         self.opt_state = [torch.zeros_like(self.fp.flat) for _ in range(self.sched.n_moments)]
-        dev, B, S = self.device, batch, self.S
+        dev, B, S = self.device, self.batch, self.S
         # unpadded filters: the kernels read the biases straight from the flat
         # master parameters (no per-step copies); padded: zero-tailed copies
         self._bias_alias = self.Fp == self.F
         self.bias_p = ([self.fp.views["b%d" % l] for l in range(self.L)] if self._bias_alias
                        else [torch.zeros(self.Fp, device=dev) for _ in range(self.L)])
         self.wf, self.wd = [], []
-        for l in range(self.L):
-            cin_p = self.C0p if l == 0 else self.Fp
+        for l, ly in enumerate(self._layers):
             w = self.fp.views["w%d" % l]
-            self.wf.append(ops.packed_weight_like(w, cin_p, self.Fp))
-            self.wd.append(ops.packed_weight_like(w, cin_p, self.Fp, transposed=True) if l > 0
+            self.wf.append(ops.packed_weight_like(w, ly.cin_p, self.Fp))
+            self.wd.append(ops.packed_weight_like(w, ly.cin_p, self.Fp, transposed=True) if l > 0
                            else torch.empty(0, device=dev, dtype=torch.bfloat16))
         # activations / gradients (zero borders are never written)
         self.X0 = ops.padded_empty(B, S, self.P0, self.C0p, dev)
@@ -286,65 +317,50 @@ class HipConvTrainer:
         self.MBITS = [torch.zeros(hw, dtype=torch.int32, device=dev) for _ in range(self.L - 1)]
         self.loss = torch.zeros(B, device=dev)
         self.correct = torch.zeros(B, device=dev)
-        M = B * S * S
-        self.nsplit = []
-        self.wgrad_var = []
-        slab_max, db_max = 0, 0
-        for l in range(self.L):
-            cin_p = self.C0p if l == 0 else self.Fp
-            T = self.K[l] ** 2
-            # one resident round of wgrad workgroups (the kernel's own occupancy, ops.wgrad_plan); small
-            # batches: the LDS-ring variant with longer splits (ops.wgrad_config)
-            var, ns = ops.wgrad_config(M, self.Fp, cin_p, self.K[l], self.C0 if l == 0 else 0, wgrad_target_wgs,
-                                       self._num_cus(), self.wgrad_variant)
-            self.nsplit.append(ns)
-            self.wgrad_var.append(var)
-            slab_max = max(slab_max, ns * T * self.Fp * cin_p)
-            db_max = max(db_max, ns * self.Fp)
+
+    def _init_plans(self, wgrad_target_wgs: int, wgrad_direct: Optional[bool], reduce_stream: bool) -> None:
+        """Per-layer kernel choices (wgrad variant and split, forward / dgrad plans) and what they need."""
+        M = self._M
+        # one resident round of wgrad workgroups (the kernel's own occupancy, ops.wgrad_plan); small
+        # batches: the LDS-ring variant with longer splits (ops.wgrad_config)
+        cfg = [ops.wgrad_config(M, self.Fp, ly.cin_p, ly.K, ly.cin_real, wgrad_target_wgs, self._num_cus(),
+                                self.wgrad_variant) for ly in self._layers]
+        self.wgrad_var = [var for var, _ in cfg]
+        self.nsplit = [ns for _, ns in cfg]
         # split-free wgrad (ops.conv_wgrad_direct: whole pixel range per workgroup, OIHW gradient written
         # in the kernel, no slab and no reduce launch); automatic up to WGRAD_DIRECT_MAX_PIXELS, off with
         # the reduce stream (its slabs are the point) and for kernel-lab wgrad variants
         if wgrad_direct is None:
             wgrad_direct = M <= WGRAD_DIRECT_MAX_PIXELS
-        self.wgrad_ksub = int(wgrad_ksub)
         self.wgrad_direct = [bool(wgrad_direct) and not reduce_stream and self.wgrad_variant in (0, ops.WGRAD_SMALL)
-                             and ops.wgrad_direct_supported(self.Fp, self.C0p if l == 0 else self.Fp,
-                                                            self.C0 if l == 0 else self.Fp, self.K[l])
-                             for l in range(self.L)]
-        # small batches (B <= 8, ops.SPLITK_MAX_M): forward and bitmask dgrad on the split-K 32-pixel tile
-        # (ops.conv_fwd_splitk: the K loop of a tile over several workgroups, one finishing pass);
-        # bf16 path with the automatic tiling only
-        self.sk_fwd = [1] * self.L
-        self.sk_dg = [1] * self.L
-        if conv_tile == 0 and self.precision == "bf16" and not self.lab_tile:
-            for l in range(self.L):
-                cin_p = self.C0p if l == 0 else self.Fp
-                self.sk_fwd[l] = ops.splitk_nsplit(M, self.Fp, cin_p, self.K[l])
-                if l > 0:
-                    self.sk_dg[l] = ops.splitk_nsplit(M, self.Fp, self.Fp, self.K[l])
-        # small batches: the weight-stationary kernel (tile 40) where it applies, instead of split-K
-        self.ws_fwd = [False] * self.L
-        self.ws_dg = [False] * self.L
-        if conv_tile == 0 and self.precision == "bf16" and not self.lab_tile:
-            for l in range(self.L):
-                cin_p = self.C0p if l == 0 else self.Fp
-                if ops.ws_applies(M, self.Fp, cin_p, self.K[l], training=True):
-                    self.ws_fwd[l], self.sk_fwd[l] = True, 1
-                if l > 0 and ops.ws_applies(M, self.Fp, self.Fp, self.K[l], training=True):
-                    self.ws_dg[l], self.sk_dg[l] = True, 1
+                             and ops.wgrad_direct_supported(self.Fp, ly.cin_p, ly.cin_real or ly.cin_p, ly.K)
+                             for ly in self._layers]
+        # forward and bitmask dgrad (ops.plan_conv).  Small batches, bf16 path with the automatic tiling
+        # only: the weight-stationary kernel (tile 40) where it applies, else (B <= 8, ops.SPLITK_MAX_M)
+        # the split-K 32-pixel tile (ops.conv_fwd_splitk: the K loop of a tile over several workgroups,
+        # one finishing pass)
+        small = self.conv_tile == 0 and self.precision == "bf16" and not self.lab_tile
+        self.fwd_plan = [ops.plan_conv(M, self.Fp, ly.cin_p, ly.K, training=True, tile=self.conv_tile, small=small)
+                         for ly in self._layers]
+        self.dg_plan = [None] + self.fwd_plan[1:]  # the dgrad of a layer >= 1 is a conv of its forward's shape
         # their weights in the weight-stationary order (ops.ws_pack after every update, repack())
-        self.wf_ws = [ops.ws_packed_like(self.wf[l]) if self.ws_fwd[l] else None for l in range(self.L)]
-        self.wd_ws = [ops.ws_packed_like(self.wd[l]) if self.ws_dg[l] else None for l in range(self.L)]
-        sk_max = max(self.sk_fwd + self.sk_dg)
-        self._sk_ws = torch.empty(sk_max * M * self.Fp, device=dev) if sk_max > 1 else None
+        self.wf_ws = [ops.ws_packed_like(w) if p.kind == "ws" else None for w, p in zip(self.wf, self.fwd_plan)]
+        self.wd_ws = [ops.ws_packed_like(w) if p is not None and p.kind == "ws" else None
+                      for w, p in zip(self.wd, self.dg_plan)]
+        n = ops.splitk_workspace_numel(self.fwd_plan + self.dg_plan, M, self.Fp)
+        self._sk_ws = torch.empty(n, device=self.device) if n else None
+
+    def _init_streams(self, reduce_stream: bool, wgrad_priority: Optional[int]) -> None:
+        """The reduce and wgrad side streams and the wgrad split slabs."""
         # Split-K reduce on a side stream (serial backward only): the memory-bound reduce of
         # layer l runs beside dgrad(l) instead of between the two big conv kernels.  The
         # slabs are double-buffered by layer parity, so wgrad(l-1) never waits for
         # reduce(l); wgrad(l-2) waits for reduce(l) through an event.
-        self.s_r = (torch.cuda.Stream(device=dev, priority=-1) if reduce_stream and not overlap else None)
+        self.s_r = (torch.cuda.Stream(device=self.device, priority=-1) if reduce_stream and not self.overlap else None)
         nslab = 2 if self.s_r is not None else 1
-        self._slabs = [torch.empty(slab_max, device=dev) for _ in range(nslab)]
-        self._dbslabs = [torch.zeros(db_max, device=dev) for _ in range(nslab)]
+        slab_max = max(ns * ly.K ** 2 * self.Fp * ly.cin_p for ns, ly in zip(self.nsplit, self._layers))
+        self._slabs = [torch.empty(slab_max, device=self.device) for _ in range(nslab)]
+        self._dbslabs = [torch.zeros(max(self.nsplit) * self.Fp, device=self.device) for _ in range(nslab)]
         self._slab_free = [None] * nslab  # event: the reduce that last read slab i has finished
         # wgrad stream at high priority (-1): its workgroups are dispatched ahead of the
         # concurrent dgrad's, so the wgrad/reduce/all-reduce chain of a layer finishes
@@ -352,22 +368,21 @@ class HipConvTrainer:
         # 3 alternating A/B pairs of 100 steps; ALPHAGO_AMD_WGRAD_PRIO=0 restores equal priority)
         if wgrad_priority is None:
             wgrad_priority = int(os.environ.get("ALPHAGO_AMD_WGRAD_PRIO", "-1"))
-        self.s_w = torch.cuda.Stream(device=dev, priority=wgrad_priority) if overlap else None
+        self.s_w = torch.cuda.Stream(device=self.device, priority=wgrad_priority) if self.overlap else None
+
+    def _init_buckets(self, bucket_mb: float, merged_reduce: Optional[bool]) -> None:
+        """Gradient buckets and their all-reducer, and the merged split-K reduce."""
         # buckets over the flat grad, segments in backward order (head first)
         h0 = self.fp.segments[self.head_names[0]][0]
         h1 = sum(self.fp.segments[n][1] for n in self.head_names)
         segs = [(h0, h1)]
-        self._seg_layer = [None]
+        self._seg_layer = [-1] + list(reversed(range(self.L)))  # -1: the head
         for l in reversed(range(self.L)):
             ow, nw = self.fp.segments["w%d" % l]
             _, nb = self.fp.segments["b%d" % l]
             segs.append((ow, nw + nb))
-            self._seg_layer.append(l)
         self.buckets = agdist.make_buckets(segs, int(bucket_mb * (1 << 20)), last_alone=True)
-        self._bucket_after_layer = {}
-        for bi, (_, _, ids) in enumerate(self.buckets):
-            last = ids[-1]
-            self._bucket_after_layer[self._seg_layer[last] if self._seg_layer[last] is not None else -1] = bi
+        self._bucket_after_layer = {self._seg_layer[ids[-1]]: bi for bi, (_, _, ids) in enumerate(self.buckets)}
         self.reducer = agdist.BucketAllReducer(self.fp.grad, self.buckets)
         # one-GPU contention proxy of the overlapped all-reduce (ALPHAGO_AMD_COMM_PROXY, world 1 only)
         self._proxy = agdist.CommProxy.from_env(self.fp.grad, self.buckets) if not self.env.distributed else None
@@ -378,7 +393,7 @@ class HipConvTrainer:
         # element as the per-layer reduce, so bitwise equal) instead of a reduce launch per layer.  Without
         # a gradient all-reduce to overlap nothing waits for an early reduce.
         if merged_reduce is None:
-            merged_reduce = M <= MERGED_REDUCE_MAX_PIXELS
+            merged_reduce = self._M <= MERGED_REDUCE_MAX_PIXELS
         self.merged_reduce = (bool(merged_reduce) and not self.env.distributed and self._proxy is None
                               and self.s_r is None and self.L <= 16)
         self._mslabs = [None] * self.L  # per-layer (slab, dbias slab), allocated at first use
@@ -386,84 +401,71 @@ class HipConvTrainer:
         # ALPHAGO_AMD_DEFER_ALLREDUCE=1: launch every bucket after the backward instead of at its bucket
         # point (no overlap, no CU contention with the dgrad / wgrad kernels)
         self.defer_allreduce = os.environ.get("ALPHAGO_AMD_DEFER_ALLREDUCE", "0") == "1"
-        if precision == "fp8":
-            # fp8 forward (block-scaled MFMA) with bf16 activations kept for the
-            # backward; per-tensor power-of-two scales, all device-side:
-            # weights from their amax at every repack, activations delayed by
-            # one step from the amax the fp8 kernels accumulate.
-            L = self.L
-            self.w8 = [torch.zeros(ops.fp8_weight_shape(self.K[l], self.C0p if l == 0 else self.Fp, self.Fp),
-                                   dtype=torch.uint8, device=dev) for l in range(L)]
-            self.wscale8 = torch.ones(L, device=dev)
-            self.scales8 = torch.full((L, 2), 127, dtype=torch.int32, device=dev)
-            # this step's activation exponents, kept for the fp8 wgrad: X8[l] was quantised with
-            # them, while scales8[:, 0] already holds the next step's delayed exponents by then
-            self.xscale8 = torch.full((L, 1), 127, dtype=torch.int32, device=dev)
-            self.osc8 = torch.ones(L, device=dev)
-            self.amax8 = ops.fp8_amax_buffer(L, dev)
-            # ALPHAGO_AMD_FP8_SR=1: the training forward rounds its e4m3 activations stochastically
-            # (v_cvt_sr_fp8_f32; a device seed advanced every step); evaluation keeps round-to-nearest
-            self.fp8_sr = os.environ.get("ALPHAGO_AMD_FP8_SR", "0") == "1"
-            self._sr_seed = torch.zeros(1, dtype=torch.int32, device=dev)
-            self._train_fwd = False
-            self.X08 = torch.zeros(self.X0.shape, dtype=torch.uint8, device=dev)
-            self.Y8 = [torch.zeros(self.Y[0].shape, dtype=torch.uint8, device=dev) for _ in range(2)]
-            self._fp8_calibrated = False
-            # fp8 dgrad (opt-in): e5m2 gradients x transposed e4m3 weights; per-layer delayed
-            # gradient scales from the max |dZ| of the previous step (the first step runs bf16
-            # dgrads and calibrates them).  Round 3: the kernel reads the bf16 dZ and converts it to
-            # e5m2 in registers (no quantisation pass, no e5m2 tensor), takes ReLU' from the
-            # forward's bitmask, and the transposed packs ride the one batched repack launch.
-            self.fp8_dgrad = bool(fp8_dgrad)  # resolved below once fp8_wgrad is known
-            self.wd8 = [None] + [torch.zeros(ops.fp8_weight_shape(self.K[l], self.Fp, self.Fp), dtype=torch.uint8,
-                                             device=dev) for l in range(1, L)]
-            self.gscales8 = torch.full((L, 2), 127, dtype=torch.int32, device=dev)
-            self.gosc8 = torch.ones(L, device=dev)
-            self.gamax8 = ops.fp8_amax_buffer(L, dev)
-            self._g8_calibrated = False
-            # fp8 wgrad (160 -> 160 3x3 layers, conv_wgrad_fp8.hip): e4m3 inputs kept per layer (the
-            # forward's e4m3 outputs instead of a two-buffer ring), e5m2 output gradients written by
-            # the bitmask dgrad's epilogue (the head's by one quantise pass), delayed gradient scales
-            # as the fp8 dgrad's.  Layer 0 (49 planes) keeps the bf16 wgrad.  On by default where it
-            # applies (value net: 143 vs 201 us per layer at B = 1024, profiles/r3_fp8_wgrad.md);
-            # ALPHAGO_AMD_FP8_WGRAD=0 keeps the bf16 wgrad.
-            if fp8_wgrad is None:
-                fp8_wgrad = os.environ.get("ALPHAGO_AMD_FP8_WGRAD", "1") == "1"
-            self.fp8_wgrad = bool(fp8_wgrad) and all(
-                ops.wgrad_fp8_supported(self.Fp, self.Fp, self.K[l]) for l in range(1, L))
-            # per-layer precision: the layers in fp8_bf16_layers run their forward, dgrad and wgrad in bf16
-            # (their weights are never quantised); the others stay on the fp8 kernels
-            self._w8layers = (set(range(1, L)) - self.fp8_bf16_layers) if self.fp8_wgrad else set()
-            # With the fp8 wgrad the dgrad reads the same e5m2 dZ copy and writes e5m2 for the layer
-            # below (conv_dgrad_fp8_bits): the all-fp8 backward is the default there (value 12 x 152,
-            # B = 1024: 156.3k -> 179.9k positions/s, profiles/r3_fp8_wgrad.md);
-            # ALPHAGO_AMD_FP8_DGRAD=0 keeps the bf16 dgrad.  Elsewhere fp8 dgrad stays opt-in.
-            if fp8_dgrad is None:
-                fp8_dgrad = self.fp8_wgrad and os.environ.get("ALPHAGO_AMD_FP8_DGRAD", "1") == "1"
-            self.fp8_dgrad = bool(fp8_dgrad)
-            if self.fp8_wgrad:
-                self.X8 = [None] + [torch.zeros(self.Y[0].shape, dtype=torch.uint8, device=dev) for _ in range(1, L)]
-                self.DZ8 = [None] + [torch.zeros(self.DZ[0].shape, dtype=torch.uint8, device=dev) for _ in range(1, L)]
-                self.nsplit8 = ops.wgrad_fp8_nsplit(M, 3)
-                need = self.nsplit8 * 9 * self.Fp * self.Fp
-                if need > self._slabs[0].numel():
-                    self._slabs = [torch.empty(need, device=dev) for _ in self._slabs]
-                if self.nsplit8 * self.Fp > self._dbslabs[0].numel():
-                    self._dbslabs = [torch.zeros(self.nsplit8 * self.Fp, device=dev) for _ in self._dbslabs]
-        else:
-            self.fp8_wgrad = False
-            self._w8layers = set()
-        # Keras-SGD schedule mirrored on the device (float64 {lr0, decay, iterations, lr}) so that
-        # the SGD step reads its learning rate from memory: the whole step is graph-capturable
-        self._sched_dev = torch.zeros(8, dtype=torch.float64, device=dev)
-        # fused SGD + bf16 packs (ops.sgd_pack); ALPHAGO_AMD_FUSED_UPDATE=0: sgd_update + pack_weights
-        self._fused_update = os.environ.get("ALPHAGO_AMD_FUSED_UPDATE", "1") == "1"
-        self._pack_plan = None
-        self.use_graph = False
-        self._graphs = None
-        self._g_in = None
-        self._init_head()
-        self.repack()
+
+    def _init_fp8(self, fp8_dgrad: Optional[bool], fp8_wgrad: Optional[bool]) -> None:
+        """Packs, scales and buffers of the fp8 trunk (precision "fp8")."""
+        # fp8 forward (block-scaled MFMA) with bf16 activations kept for the
+        # backward; per-tensor power-of-two scales, all device-side:
+        # weights from their amax at every repack, activations delayed by
+        # one step from the amax the fp8 kernels accumulate.
+        dev, L = self.device, self.L
+        self.w8 = [torch.zeros(ops.fp8_weight_shape(ly.K, ly.cin_p, self.Fp), dtype=torch.uint8, device=dev)
+                   for ly in self._layers]
+        self.wscale8 = torch.ones(L, device=dev)
+        self.scales8 = torch.full((L, 2), 127, dtype=torch.int32, device=dev)
+        # this step's activation exponents, kept for the fp8 wgrad: X8[l] was quantised with
+        # them, while scales8[:, 0] already holds the next step's delayed exponents by then
+        self.xscale8 = torch.full((L, 1), 127, dtype=torch.int32, device=dev)
+        self.osc8 = torch.ones(L, device=dev)
+        self.amax8 = ops.fp8_amax_buffer(L, dev)
+        # ALPHAGO_AMD_FP8_SR=1: the training forward rounds its e4m3 activations stochastically
+        # (v_cvt_sr_fp8_f32; a device seed advanced every step); evaluation keeps round-to-nearest
+        self.fp8_sr = os.environ.get("ALPHAGO_AMD_FP8_SR", "0") == "1"
+        self._sr_seed = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._train_fwd = False
+        self.X08 = torch.zeros(self.X0.shape, dtype=torch.uint8, device=dev)
+        self.Y8 = [torch.zeros(self.Y[0].shape, dtype=torch.uint8, device=dev) for _ in range(2)]
+        self._fp8_calibrated = False
+        # fp8 dgrad (opt-in): e5m2 gradients x transposed e4m3 weights; per-layer delayed
+        # gradient scales from the max |dZ| of the previous step (the first step runs bf16
+        # dgrads and calibrates them).  Round 3: the kernel reads the bf16 dZ and converts it to
+        # e5m2 in registers (no quantisation pass, no e5m2 tensor), takes ReLU' from the
+        # forward's bitmask, and the transposed packs ride the one batched repack launch.
+        self.wd8 = [None] + [torch.zeros(ops.fp8_weight_shape(self.K[l], self.Fp, self.Fp), dtype=torch.uint8,
+                                         device=dev) for l in range(1, L)]
+        self.gscales8 = torch.full((L, 2), 127, dtype=torch.int32, device=dev)
+        self.gosc8 = torch.ones(L, device=dev)
+        self.gamax8 = ops.fp8_amax_buffer(L, dev)
+        self._g8_calibrated = False
+        # fp8 wgrad (160 -> 160 3x3 layers, conv_wgrad_fp8.hip): e4m3 inputs kept per layer (the
+        # forward's e4m3 outputs instead of a two-buffer ring), e5m2 output gradients written by
+        # the bitmask dgrad's epilogue (the head's by one quantise pass), delayed gradient scales
+        # as the fp8 dgrad's.  Layer 0 (49 planes) keeps the bf16 wgrad.  On by default where it
+        # applies (value net: 143 vs 201 us per layer at B = 1024, profiles/r3_fp8_wgrad.md);
+        # ALPHAGO_AMD_FP8_WGRAD=0 keeps the bf16 wgrad.
+        if fp8_wgrad is None:
+            fp8_wgrad = os.environ.get("ALPHAGO_AMD_FP8_WGRAD", "1") == "1"
+        self.fp8_wgrad = bool(fp8_wgrad) and all(
+            ops.wgrad_fp8_supported(self.Fp, self.Fp, self.K[l]) for l in range(1, L))
+        # per-layer precision: the layers in fp8_bf16_layers run their forward, dgrad and wgrad in bf16
+        # (their weights are never quantised); the others stay on the fp8 kernels
+        self._w8layers = (set(range(1, L)) - self.fp8_bf16_layers) if self.fp8_wgrad else set()
+        # With the fp8 wgrad the dgrad reads the same e5m2 dZ copy and writes e5m2 for the layer
+        # below (conv_dgrad_fp8_bits): the all-fp8 backward is the default there (value 12 x 152,
+        # B = 1024: 156.3k -> 179.9k positions/s, profiles/r3_fp8_wgrad.md);
+        # ALPHAGO_AMD_FP8_DGRAD=0 keeps the bf16 dgrad.  Elsewhere fp8 dgrad stays opt-in.
+        if fp8_dgrad is None:
+            fp8_dgrad = self.fp8_wgrad and os.environ.get("ALPHAGO_AMD_FP8_DGRAD", "1") == "1"
+        self.fp8_dgrad = bool(fp8_dgrad)
+        if self.fp8_wgrad:
+            self.X8 = [None] + [torch.zeros(self.Y[0].shape, dtype=torch.uint8, device=dev) for _ in range(1, L)]
+            self.DZ8 = [None] + [torch.zeros(self.DZ[0].shape, dtype=torch.uint8, device=dev) for _ in range(1, L)]
+            self.nsplit8 = ops.wgrad_fp8_nsplit(self._M, 3)
+            need = self.nsplit8 * 9 * self.Fp * self.Fp
+            if need > self._slabs[0].numel():
+                self._slabs = [torch.empty(need, device=dev) for _ in self._slabs]
+            if self.nsplit8 * self.Fp > self._dbslabs[0].numel():
+                self._dbslabs = [torch.zeros(self.nsplit8 * self.Fp, device=dev) for _ in self._dbslabs]
 
     # ------------------------------------------------------------------ schedule / graphs
     def sync_schedule(self) -> None:
@@ -509,9 +511,8 @@ class HipConvTrainer:
         if bf16:
             ops.pack_weights(ws, self.wf, self.wd)
         # the weight-stationary copies of the small-batch layers (from the bf16 packs, however written)
-        src = [self.wf[l] for l in range(self.L) if self.wf_ws[l] is not None]
-        src += [self.wd[l] for l in range(self.L) if self.wd_ws[l] is not None]
-        ops.ws_pack(src, [w for w in self.wf_ws + self.wd_ws if w is not None])
+        pairs = [(w, c) for w, c in zip(self.wf + self.wd, self.wf_ws + self.wd_ws) if c is not None]
+        ops.ws_pack([w for w, _ in pairs], [c for _, c in pairs])
         if self.precision == "fp8":
             ops.fp8_weight_scales(ws, self.wscale8, self.scales8)
             # every e4m3 pack of the step (forward, and the transposed dgrad packs) in ONE launch
@@ -552,15 +553,9 @@ class HipConvTrainer:
         if self.lab_tile and self.K[l] == 3:
             ops.lab().conv_fwd(x, self.wf[l], self.bias_p[l], None, self.Y[l], 3, self.S, pin, 1, 0, mbits,
                                self.lab_tile)
-        elif self.ws_fwd[l]:
-            ops.conv_fwd(x, self.wf_ws[l], self.bias_p[l], self.Y[l], self.K[l], self.S, pin, 1, mbits=mbits,
-                         tile=40)
-        elif self.sk_fwd[l] > 1:
-            ops.conv_fwd_splitk(x, self.wf[l], self.bias_p[l], self.Y[l], self.K[l], self.S, pin, 1,
-                                ops.MODE_BIAS_RELU, mbits, self._sk_ws, self.sk_fwd[l])
         else:
-            ops.conv_fwd(x, self.wf[l], self.bias_p[l], self.Y[l], self.K[l], self.S, pin, 1, mbits=mbits,
-                         tile=self.conv_tile)
+            ops.conv_planned(self.fwd_plan[l], x, self.wf[l], self.wf_ws[l], self.bias_p[l], self.Y[l], self.K[l],
+                             self.S, pin, ops.MODE_BIAS_RELU, mbits, self._sk_ws)
 
     def _forward_fp8(self) -> None:
         x8, pin = self.X08, self.P0  # e4m3 input written by forward_trunk's pack_input (exact: 0/1 planes)
@@ -613,60 +608,87 @@ class HipConvTrainer:
         the async all-reduce of a completed bucket when ``red``).  With the reduce stream the
         reduce and the all-reduce launch run there; the caller's stream goes on to dgrad(l)."""
         x, pin = self._layer_in(l)
-        T = self.K[l] ** 2
-        cin_p = x.shape[3]
+        ly = self._layers[l]
         f8 = l in self._w8layers and self._g8_calibrated
+        direct = self.wgrad_direct[l] and not f8
+        merged = self.merged_reduce and not direct
         ns = self.nsplit8 if f8 else self.nsplit[l]
+        nw, nb = ns * ly.K ** 2 * self.Fp * ly.cin_p, ns * self.Fp
         i = l % len(self._slabs)
-        slab = self._slabs[i][:ns * T * self.Fp * cin_p].view(ns, T, self.Fp, cin_p)
-        dbs = self._dbslabs[i][:ns * self.Fp].view(ns, self.Fp)
+        sl, db = self._slabs[i], self._dbslabs[i]
+        if merged:  # this layer's own slab; the reduce waits for the merged launch after the backward
+            if self._mslabs[l] is None or self._mslabs[l][0].numel() < nw:
+                self._mslabs[l] = (torch.empty(nw, device=self.device), torch.zeros(nb, device=self.device))
+            sl, db = self._mslabs[l]
+        slab = sl[:nw].view(ns, ly.K ** 2, self.Fp, ly.cin_p)
+        dbs = db[:nb].view(ns, self.Fp)
+        gw, gb = self.fp.grad_views["w%d" % l], self.fp.grad_views["b%d" % l]
         sr = self.s_r
         if sr is not None and self._slab_free[i] is not None:
             torch.cuda.current_stream(self.device).wait_event(self._slab_free[i])
-        if self.merged_reduce and not (self.wgrad_direct[l] and not f8):
-            # this layer's own slab; the reduce waits for the merged launch after the backward
-            if self._mslabs[l] is None or self._mslabs[l][0].numel() < ns * T * self.Fp * cin_p:
-                self._mslabs[l] = (torch.empty(ns * T * self.Fp * cin_p, device=self.device),
-                                   torch.zeros(ns * self.Fp, device=self.device))
-            sl, db = self._mslabs[l]
-            slab = sl[:ns * T * self.Fp * cin_p].view(ns, T, self.Fp, cin_p)
-            dbs = db[:ns * self.Fp].view(ns, self.Fp)
-            if f8:
-                ops.conv_wgrad_fp8(self.X8[l], self.DZ8[l], slab, dbs, self.xscale8[l], self.gscales8[l, 0:1],
-                                   self.gosc8[l:l + 1], self.K[l], self.S, pin, 1,
-                                   amax=self.gamax8[l] if l < self.L - 1 else None)
-            else:
-                ops.conv_wgrad(x, self.DZ[l], slab, dbs, self.K[l], self.S, pin, 1,
-                               cin_real=self.C0 if l == 0 else 0, variant=self.wgrad_var[l])
-            self._pending_reduce.append((slab, dbs, l))
-            return
-        if self.wgrad_direct[l] and not f8:  # split-free: the OIHW gradient straight from the kernel
-            ops.conv_wgrad_direct(x, self.DZ[l], self.fp.grad_views["w%d" % l], self.fp.grad_views["b%d" % l],
-                                  self.K[l], self.S, pin, 1, 1.0, 0.0, self.wgrad_ksub)
-            if red and not self.defer_allreduce and l in self._bucket_after_layer:
-                self.reducer.launch(self._bucket_after_layer[l])
-            return
         if f8:  # e5m2 dZ x e4m3 X, dequantised by the MFMA's block scales
             # (its tap-0 workgroups also fold max |dZ| into the delayed-scale slots of layer l)
             ops.conv_wgrad_fp8(self.X8[l], self.DZ8[l], slab, dbs, self.xscale8[l], self.gscales8[l, 0:1],
-                               self.gosc8[l:l + 1], self.K[l], self.S, pin, 1,
+                               self.gosc8[l:l + 1], ly.K, self.S, pin, 1,
                                amax=self.gamax8[l] if l < self.L - 1 else None)
+        elif direct:  # split-free: the OIHW gradient straight from the kernel
+            ops.conv_wgrad_direct(x, self.DZ[l], gw, gb, ly.K, self.S, pin, 1, 1.0, 0.0, self.wgrad_ksub)
         else:
-            ops.conv_wgrad(x, self.DZ[l], slab, dbs, self.K[l], self.S, pin, 1, cin_real=self.C0 if l == 0 else 0,
+            ops.conv_wgrad(x, self.DZ[l], slab, dbs, ly.K, self.S, pin, 1, cin_real=ly.cin_real,
                            variant=self.wgrad_var[l])
+        if direct:
+            self._launch_bucket_after(l, red)
+        elif merged:
+            self._pending_reduce.append((slab, dbs, l))
+        elif sr is None:
+            ops.conv_wgrad_reduce(slab, dbs, gw, gb, 1.0, 0.0)
+            self._launch_bucket_after(l, red)
+        else:
+            sr.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(sr):
+                ops.conv_wgrad_reduce(slab, dbs, gw, gb, 1.0, 0.0)
+                self._launch_bucket_after(l, red)
+                self._slab_free[i] = sr.record_event()
 
-        def reduce():
-            ops.conv_wgrad_reduce(slab, dbs, self.fp.grad_views["w%d" % l], self.fp.grad_views["b%d" % l], 1.0, 0.0)
-            if red and not self.defer_allreduce and l in self._bucket_after_layer:
-                self.reducer.launch(self._bucket_after_layer[l])
+    def _launch_bucket_after(self, l: int, red: bool) -> None:
+        """Start the all-reduce of the bucket that layer l's gradient completes (-1: the head's)."""
+        if red and not self.defer_allreduce and l in self._bucket_after_layer:
+            self.reducer.launch(self._bucket_after_layer[l])
 
-        if sr is None:
-            reduce()
-            return
-        sr.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(sr):
-            reduce()
-            self._slab_free[i] = sr.record_event()
+    def _dgrad_layer(self, l: int) -> None:
+        """dgrad of layer l >= 1: DZ[l] (or its e5m2 copy) into DZ[l-1], ReLU' of Y[l-1] fused."""
+        w8 = self.fp8_wgrad and self._g8_calibrated
+        if w8 and self.fp8_dgrad and l in self._w8layers:
+            # all-fp8 backward: the e5m2 dZ copy wgrad(l) read is also this dgrad's operand;
+            # the output goes out as e5m2 (wgrad(l-1) and dgrad(l-1) read it) and as bf16 only
+            # for the first layer's bf16 wgrad; its max |dx| comes from wgrad(l-1)'s bytes
+            f8out = l - 1 in self._w8layers
+            ops.conv_dgrad_fp8_bits(self.DZ8[l], self.wd8[l], self.MBITS[l - 1], self.gscales8[l],
+                                    self.gosc8[l - 1:l], self.K[l], self.S,
+                                    y_bf16=None if f8out else self.DZ[l - 1],
+                                    y_fp8=self.DZ8[l - 1] if f8out else None,
+                                    amax=None if f8out else self.gamax8[l - 1])
+        elif w8 and l - 1 in self._w8layers:  # bitmask dgrad + the e5m2 copy wgrad(l-1) reads
+            ops.conv_dgrad_bits_bf8(self.DZ[l], self.wd[l], self.DZ[l - 1], self.MBITS[l - 1],
+                                    self.DZ8[l - 1], self.gosc8[l - 1:l], self.K[l], self.S,
+                                    tile=self.conv_tile)
+        elif (self.precision == "fp8" and self.fp8_dgrad and self._g8_calibrated
+              and l not in self.fp8_bf16_layers):
+            # fp8 dgrad straight from the bf16 dZ: converted to e5m2 in the kernel's registers
+            # (delayed per-layer scale gosc8[l]), ReLU' from the forward's bitmask, bf16 dx
+            # whose max |dx| sets the next step's scale of layer l-1
+            if l == self.L - 1:  # the head's dZ: its max |dZ| for the next step's scale
+                ops.absmax_bf16(self.DZ[l], self.gamax8[l])
+            ops.conv_dgrad_fp8_bf16(self.DZ[l], self.wd8[l], self.MBITS[l - 1], self.gscales8[l],
+                                    self.gosc8[l:l + 1], self.K[l], self.S, self.DZ[l - 1],
+                                    amax=self.gamax8[l - 1])
+        elif self.lab_tile and self.K[l] == 3:  # kernel-lab A/B (see __init__)
+            ops.lab().conv_fwd(self.DZ[l], self.wd[l], None, None, self.DZ[l - 1], 3, self.S, 1, 1,
+                               ops.MODE_MASKBITS, self.MBITS[l - 1], self.lab_tile)
+        else:  # ReLU' bitmask from the forward epilogue (bf16 and fp8 forwards write it); small batches
+            # on the weight-stationary or the split-K tile (dg_plan)
+            ops.conv_planned(self.dg_plan[l], self.DZ[l], self.wd[l], self.wd_ws[l], None, self.DZ[l - 1],
+                             self.K[l], self.S, 1, ops.MODE_MASKBITS, self.MBITS[l - 1], self._sk_ws)
 
     def backward_trunk(self, reduce: bool = True) -> None:
         """dZ[L-1] (and head grads) must be ready on the current stream.
@@ -674,12 +696,10 @@ class HipConvTrainer:
         caller all-reduces the sum once)."""
         main = torch.cuda.current_stream(self.device)
         red = reduce and (self.env.distributed or self._proxy is not None)
-        if red and not self.defer_allreduce and -1 in self._bucket_after_layer:
-            self.reducer.launch(self._bucket_after_layer[-1])
-        w8 = self.fp8_wgrad and self._g8_calibrated
-        if w8 and self.L - 1 in self._w8layers and not self._head_wrote_e5m2:
+        self._launch_bucket_after(-1, red)
+        top = self.L - 1
+        if self.fp8_wgrad and self._g8_calibrated and top in self._w8layers and not self._head_wrote_e5m2:
             # the head's dZ in e5m2 for wgrad(L-1), and its max |dZ| (the value head writes it itself)
-            top = self.L - 1
             ops.quantize_bf8(self.DZ[top], self.DZ8[top], self.gosc8[top:top + 1], self.gamax8[top])
         for l in reversed(range(self.L)):
             if self.s_w is not None:
@@ -690,42 +710,7 @@ class HipConvTrainer:
             else:
                 self._wgrad_layer(l, red)
             if l > 0:
-                if w8 and self.fp8_dgrad and l in self._w8layers:
-                    # all-fp8 backward: the e5m2 dZ copy wgrad(l) read is also this dgrad's operand;
-                    # the output goes out as e5m2 (wgrad(l-1) and dgrad(l-1) read it) and as bf16 only
-                    # for the first layer's bf16 wgrad; its max |dx| comes from wgrad(l-1)'s bytes
-                    f8out = l - 1 in self._w8layers
-                    ops.conv_dgrad_fp8_bits(self.DZ8[l], self.wd8[l], self.MBITS[l - 1], self.gscales8[l],
-                                            self.gosc8[l - 1:l], self.K[l], self.S,
-                                            y_bf16=None if f8out else self.DZ[l - 1],
-                                            y_fp8=self.DZ8[l - 1] if f8out else None,
-                                            amax=None if f8out else self.gamax8[l - 1])
-                elif w8 and l - 1 in self._w8layers:  # bitmask dgrad + the e5m2 copy wgrad(l-1) reads
-                    ops.conv_dgrad_bits_bf8(self.DZ[l], self.wd[l], self.DZ[l - 1], self.MBITS[l - 1],
-                                            self.DZ8[l - 1], self.gosc8[l - 1:l], self.K[l], self.S,
-                                            tile=self.conv_tile)
-                elif (self.precision == "fp8" and self.fp8_dgrad and self._g8_calibrated
-                      and l not in self.fp8_bf16_layers):
-                    # fp8 dgrad straight from the bf16 dZ: converted to e5m2 in the kernel's registers
-                    # (delayed per-layer scale gosc8[l]), ReLU' from the forward's bitmask, bf16 dx
-                    # whose max |dx| sets the next step's scale of layer l-1
-                    if l == self.L - 1:  # the head's dZ: its max |dZ| for the next step's scale
-                        ops.absmax_bf16(self.DZ[l], self.gamax8[l])
-                    ops.conv_dgrad_fp8_bf16(self.DZ[l], self.wd8[l], self.MBITS[l - 1], self.gscales8[l],
-                                            self.gosc8[l:l + 1], self.K[l], self.S, self.DZ[l - 1],
-                                            amax=self.gamax8[l - 1])
-                elif self.lab_tile and self.K[l] == 3:  # kernel-lab A/B (see __init__)
-                    ops.lab().conv_fwd(self.DZ[l], self.wd[l], None, None, self.DZ[l - 1], 3, self.S, 1, 1,
-                                       ops.MODE_MASKBITS, self.MBITS[l - 1], self.lab_tile)
-                elif self.ws_dg[l]:  # small batches: weight-stationary bitmask dgrad
-                    ops.conv_fwd(self.DZ[l], self.wd_ws[l], None, self.DZ[l - 1], self.K[l], self.S, 1, 1,
-                                 mode=ops.MODE_MASKBITS, mbits=self.MBITS[l - 1], tile=40)
-                elif self.sk_dg[l] > 1:  # small batches: split-K bitmask dgrad
-                    ops.conv_fwd_splitk(self.DZ[l], self.wd[l], None, self.DZ[l - 1], self.K[l], self.S, 1, 1,
-                                        ops.MODE_MASKBITS, self.MBITS[l - 1], self._sk_ws, self.sk_dg[l])
-                else:  # ReLU' bitmask from the forward epilogue (bf16 and fp8 forwards write it)
-                    ops.conv_fwd(self.DZ[l], self.wd[l], None, self.DZ[l - 1], self.K[l], self.S, 1, 1,
-                                 mode=ops.MODE_MASKBITS, mbits=self.MBITS[l - 1], tile=self.conv_tile)
+                self._dgrad_layer(l)
         # join the side streams first: the fp8 wgrads still running there read gscales8 / gosc8
         # and fold max |dZ| into gamax8, which the scale update below rewrites and clears
         if self.s_w is not None:
@@ -1155,12 +1140,7 @@ class TorchPolicyTrainer(_TorchTrainerBase):
     def __init__(self, net: PolicyNet, batch: int, lr: float = 0.003, decay: float = 0.0, device=None,
                  dtype=torch.float32, iterations: int = 0, optimizer: str = "sgd", momentum: float = 0.0,
                  nesterov: bool = False):
-        named = []
-        tr = net.trunk
-        for l in range(tr.layers):
-            named.append(("w%d" % l, tr.weights[l]))
-            named.append(("b%d" % l, tr.biases[l]))
-        named += [("head_w", net.head_w), ("head_b", net.head_b)]
+        named = _trunk_named(net.trunk) + [("head_w", net.head_w), ("head_b", net.head_b)]
         self._setup(net, batch, lr, decay, device, dtype, iterations, named, optimizer, momentum, nesterov)
 
     def _loss(self, planes, targets, sym, weight):
@@ -1240,13 +1220,8 @@ class TorchValueTrainer(_TorchTrainerBase):
     def __init__(self, net: ValueNet, batch: int, lr: float = 0.003, decay: float = 0.0, device=None,
                  dtype=torch.float32, iterations: int = 0, optimizer: str = "sgd", momentum: float = 0.0,
                  nesterov: bool = False):
-        named = []
-        tr = net.trunk
-        for l in range(tr.layers):
-            named.append(("w%d" % l, tr.weights[l]))
-            named.append(("b%d" % l, tr.biases[l]))
-        named += [("head_w", net.head_w), ("head_b", net.head_b), ("fc1_w", net.fc1_w), ("fc1_b", net.fc1_b),
-                  ("fc2_w", net.fc2_w), ("fc2_b", net.fc2_b)]
+        named = _trunk_named(net.trunk) + [("head_w", net.head_w), ("head_b", net.head_b), ("fc1_w", net.fc1_w),
+                                           ("fc1_b", net.fc1_b), ("fc2_w", net.fc2_w), ("fc2_b", net.fc2_b)]
         self._setup(net, batch, lr, decay, device, dtype, iterations, named, optimizer, momentum, nesterov)
 
     def _loss(self, planes, targets, sym, weight):

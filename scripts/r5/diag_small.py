@@ -34,5 +34,5 @@ for B in (8, 16, 32):
                 cos[name] = round(torch.nn.functional.cosine_similarity(a, b, dim=0).item(), 5)
             allc = torch.nn.functional.cosine_similarity(hip.fp.grad.double(), ref.fp.grad.double(), dim=0).item()
             print("B=%d splitk=%s overlap=%s(%s) sk_fwd=%s all=%.5f min=%.5f %s" % (
-                B, splitk, overlap, hip.overlap, hip.sk_fwd[1], allc, min(cos.values()),
+                B, splitk, overlap, hip.overlap, hip.fwd_plan[1].nsplit, allc, min(cos.values()),
                 " ".join("%s:%.4f" % kv for kv in cos.items())), flush=True)

@@ -321,7 +321,13 @@ def test_splitk_small_batch_trainer_matches(cuda_device, monkeypatch, B, kind):
     for sk in ("1", "0"):
         monkeypatch.setenv("ALPHAGO_AMD_SPLITK", sk)
         trs.append(cls(copy.deepcopy(net), B, lr=0.05, device=cuda_device))
-    assert max(trs[0].sk_fwd) > 1 and max(trs[0].sk_dg) > 1 and max(trs[1].sk_fwd + trs[1].sk_dg) == 1
+    def split(plans):
+        return [p.kind == "splitk" and p.nsplit > 1 for p in plans if p is not None]
+
+    assert trs[0].dg_plan[0] is None and trs[1].dg_plan[0] is None
+    assert any(split(trs[0].fwd_plan)) and any(split(trs[0].dg_plan))
+    assert not any(split(trs[1].fwd_plan + trs[1].dg_plan))
+    assert all(p.nsplit == 1 for p in trs[1].fwd_plan + trs[1].dg_plan[1:])
     planes = torch.randint(0, 2, (B, C, 19, 19), dtype=torch.uint8, device=cuda_device)
     if kind == "policy":
         tgt = torch.randint(0, 361, (B,), dtype=torch.int32, device=cuda_device)
@@ -407,7 +413,11 @@ def test_weight_stationary_trainer_matches(cuda_device, monkeypatch, B, kind):
         monkeypatch.setenv("ALPHAGO_AMD_WS", ws)
         monkeypatch.setenv("ALPHAGO_AMD_SPLITK", ws)
         trs.append(cls(copy.deepcopy(net), B, lr=0.05, device=cuda_device))
-    assert all(trs[0].ws_fwd[1:]) and all(trs[0].ws_dg[1:]) and not any(trs[1].ws_fwd + trs[1].ws_dg)
+    assert all(p.kind == "ws" for p in trs[0].fwd_plan[1:] + trs[0].dg_plan[1:])
+    assert not any(p.kind == "ws" for p in trs[1].fwd_plan + trs[1].dg_plan[1:])
+    for t in trs:  # the weight-stationary copies exist exactly where the plan reads them
+        assert [w is not None for w in t.wf_ws] == [p.kind == "ws" for p in t.fwd_plan]
+        assert [w is not None for w in t.wd_ws] == [p is not None and p.kind == "ws" for p in t.dg_plan]
     planes = torch.randint(0, 2, (B, C, 19, 19), dtype=torch.uint8, device=cuda_device)
     if kind == "policy":
         tgt = torch.randint(0, 361, (B,), dtype=torch.int32, device=cuda_device)
