@@ -624,7 +624,13 @@ def test_debug_build_bounds_checks(cuda_device, tmp_path):
                                                    (361, 256, 2176, True, False, False, 0.0),
                                                    (2176, 361, 256, False, True, False, 0.0),
                                                    (37, 70, 5, False, False, True, 0.5),
-                                                   (81, 16, 9, True, True, False, 1.0)])
+                                                   (81, 16, 9, True, True, False, 1.0),
+                                                   # the batch sizes of inference and of self-play with 16 boards
+                                                   (1, 256, 361, False, False, True, 0.0),
+                                                   (16, 256, 361, False, False, True, 0.0),
+                                                   (361, 256, 1, True, False, False, 0.0),
+                                                   (361, 256, 16, True, False, False, 0.0),
+                                                   (16, 361, 256, False, True, False, 0.0)])
 def test_dense_f32_vs_torch(ops, cuda_device, M, N, K, ta, tb, bias, beta):
     """Value-head dense GEMM (fp32 MFMA) vs fp64 torch: the three shapes of the
     value head (forward, dW1 = z^T dh, dz = dh W1^T) and ragged/transposed ones."""
@@ -644,6 +650,33 @@ def test_dense_f32_vs_torch(ops, cuda_device, M, N, K, ta, tb, bias, beta):
     C2 = C0.clone()
     ops.dense_f32(A, B, C2, bias=b, trans_a=ta, trans_b=tb, beta=beta)
     assert torch.equal(C, C2)  # deterministic
+
+
+@pytest.mark.parametrize("ta,tb", [(False, False), (True, False), (False, True), (True, True)])
+@pytest.mark.parametrize("M,N,K,beta", [(16, 256, 361, 0.0), (70, 100, 300, 0.5)])
+def test_dense_f32_strided_operands(ops, cuda_device, M, N, K, ta, tb, beta):
+    """A, B and C as column slices of wider tensors (row stride > row length; (70, 100, 300) splits K
+    through the workspace): test_dense_f32_vs_torch's bound and determinism check, and the columns of
+    the wide C on either side of the slice stay untouched."""
+    torch.manual_seed(10)
+    ar, ac = (K, M) if ta else (M, K)
+    br, bc = (N, K) if tb else (K, N)
+    A = torch.randn(ar, ac + 7, device=cuda_device)[:, 3:3 + ac]
+    B = torch.randn(br, bc + 5, device=cuda_device)[:, 5:]
+    b = torch.randn(N, device=cuda_device)
+    W0 = torch.randn(M, N + 9, device=cuda_device)
+    W = W0.clone()
+    C = W[:, 4:4 + N]
+    assert A.stride(0) > ac and B.stride(0) > bc and C.stride(0) > N
+    ops.dense_f32(A, B, C, bias=b, trans_a=ta, trans_b=tb, beta=beta)
+    ref = (A.double().t() if ta else A.double()) @ (B.double().t() if tb else B.double()) + b.double()
+    ref = ref + beta * W0[:, 4:4 + N].double()
+    torch.cuda.synchronize()
+    assert (C.double() - ref).abs().max().item() < 1e-5 * max(1.0, K ** 0.5) * ref.abs().max().item()
+    assert torch.equal(W[:, :4], W0[:, :4]) and torch.equal(W[:, 4 + N:], W0[:, 4 + N:])
+    W2 = W0.clone()
+    ops.dense_f32(A, B, W2[:, 4:4 + N], bias=b, trans_a=ta, trans_b=tb, beta=beta)
+    assert torch.equal(W, W2)  # deterministic
 
 
 @pytest.mark.gpu
