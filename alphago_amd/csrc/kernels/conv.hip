@@ -45,7 +45,7 @@ template <int MODE, bool STR>
 static void launch_fwd_160(const ConvFwdArgs& a, int bm, hipStream_t st) {
   if (bm == 384) launch_fwd_bm<160, MODE, 384, 6, false, false, false, false, STR>(a, st);
   else if (bm == 385) launch_fwd_bm<160, MODE, 384, 6, false, false, false, true, STR>(a, st);
-  else if (bm == 386) launch_fwd_bm<160, MODE, 384, 6, false, false, false, true, STR, true>(a, st);
+  else if (bm == 386 || bm == 388) launch_fwd_bm<160, MODE, 384, 6, false, false, false, true, STR, true>(a, st);  // 388: not covered
   else if (bm == 387) launch_fwd_bm<160, MODE, 384, 6, false, false, false, false, STR, true>(a, st);
   else if (bm == 256) launch_fwd_bm<160, MODE, 256, 4, true, true, false, false, STR>(a, st);
   else if (bm == 128) launch_fwd_bm<160, MODE, 128, 4, true, true, false, false, STR>(a, st);
@@ -78,6 +78,14 @@ static void launch_fwd_t(const ConvFwdArgs& a, hipStream_t st) {
   // Small batches (round 3): below 128 x 256 pixels (B < 91 at 19 x 19) a 64-pixel tile on 4 waves
   // (32 x BN/2 per wave) -- B = 16 fills 91 workgroups instead of 46 (profiles/r3_small_batch.md)
   if (bm == 0) bm = (a.M >= 384 * 512) ? 386 : (a.M >= 256 * 512) ? 256 : (a.M >= 128 * 256) ? 128 : 64;
+  // 388 = 386 with the pixel rows staged once per 64-channel chunk (conv_fwd_halo384_kernel): 4 DMA
+  // pieces per wave and K-step instead of 9, bit-identical outputs.  Shapes it does not cover (not 3x3,
+  // S > 19, BN != 192, other epilogues) run 386.
+  // automatic (round 8) where 386 was: 10 s power-limited runs at B = 2176, 3x3 forward 484 -> 465 us,
+  // bitmask dgrad 468 -> 449 us; bench, three alternating pairs against the parent commit on one box,
+  // 126.7-127.0k -> 129.5-129.9k positions/s (+2.3 %, profiles/r8/README.md).  tile 386 keeps the old kernel.
+  if (a.tile == 0 && bm == 386 && halo384_covers<BN, MODE>(a)) bm = 388;
+  if (bm == 388 && !halo384_covers<BN, MODE>(a)) bm = 386;
   // round 4: below 64 x 256 pixels (B <= 45 at 19 x 19) the 32-pixel tile on 4 waves (tile 36) -- twice
   // the workgroups of the 64 tile; SL step at B = 16: 18.6k -> 19.7k positions/s (profiles/r4/README.md)
   if (BN != 160 && a.tile == 0 && a.M < 64 * 256) bm = 36;
@@ -113,6 +121,7 @@ static void launch_fwd_t(const ConvFwdArgs& a, hipStream_t st) {
     // 386 / 387: 385 / 384 with the chunk-outer K order (CO above)
     else if (bm == 386) launch_fwd_bm<BN, MODE, 384, 6, false, false, false, true, false, true>(a, st);
     else if (bm == 387) launch_fwd_bm<BN, MODE, 384, 6, false, false, false, false, false, true>(a, st);
+    else if (bm == 388) launch_fwd_halo384<BN, MODE>(a, st);
 #ifdef AGK_KERNEL_LAB
     // kernel-lab tile codes (conv_lab.hip, profiles/r1_fwd_kernel_experiments.md)
     else if (launch_conv_fwd_lab(bm, a, BN, MODE, st)) return;

@@ -453,6 +453,252 @@ static void launch_fwd_bm(const ConvFwdArgs& a, hipStream_t st) {
                      dim3(BM / MBW * 8), smem, st, a);
 }
 
+// ----------------------------------------------------------------- forward, compact-halo 384 tile (code 388)
+// The production 384-pixel loop (96 x 96 per wave, chunk-outer K order, one vmcnt(0) + barrier per
+// K-step, DMA spread through the first k-half's MFMAs) with the pixel operand staged ONCE per
+// 64-channel chunk instead of once per tap.  The nine taps of a chunk read the same pixel rows, only
+// shifted: tile 386 gathers 9 x 48 KB of them from L2 per chunk where 384 + 2 (S + 1) rows (53 KB at
+// S = 19) are distinct.  Here a K-step's DMA is the 24 KB weight tile (3 pieces per wave) plus, in the
+// first seven taps of a chunk, one piece per wave of the NEXT chunk's halo: 4 pieces per wave and step
+// instead of 9.
+// Halo rows are compact pixel indices: row r of a halo buffer holds interior pixel m0 - (S + 1) + r
+// (clamped into [0, M)), so the 16 pixels of an MFMA block are 16 consecutive rows for every tap; a
+// tap that leaves the board reads one of the 8 zero rows behind the data rows (the zero border of the
+// padded layout).  Inside a 16-pixel block the lanes take even pixels (lanes 0-3, 12-15) and odd
+// pixels (lanes 4-11), which keeps ds_read_b128 conflict-free at every row alignment the tap shifts
+// produce (conv_fwd_hpp_kernel, kernel-lab tile 5, measured this layout).
+// Every accumulator sees tile 386's MFMA sequence with the same operands (chunks outer, taps
+// ascending, k-halves ascending; zero rows for the zero border), so the outputs are bit-identical.
+// The nine taps are unrolled: tap offsets, the border test and the DMA schedule of a step are
+// compile-time, and the MFMA stream has no branch.  LDS: 2 halo buffers + 2 weight slots.
+constexpr int H384_BM = 384;
+constexpr int H384_SMAX = 19;                                          // largest board side covered
+constexpr int H384_DATA = (H384_BM + 2 * (H384_SMAX + 1) + 7) / 8 * 8;  // data rows (whole 1-KB pieces): 424
+constexpr int H384_ROWS = H384_DATA + 8;                               // + 8 zero rows
+constexpr int H384_PIECES = H384_DATA / 8;                             // 53
+
+template <int V>
+struct IntC {
+  static constexpr int value = V;
+};
+
+template <int BN, int MODE>
+__global__ __launch_bounds__(512, 1) void conv_fwd_halo384_kernel(ConvFwdArgs a) {
+  constexpr int BM = H384_BM, MB = 6, NW = 8;
+  constexpr int NB = BN / 32;
+  constexpr int NMF = NB * MB;
+  constexpr int H_BYTES = H384_ROWS * 128;
+  constexpr int W_BYTES = BN * 128;
+  constexpr int WP = BN / 8 / NW;                      // weight pieces per wave and step
+  constexpr int HPW = (H384_PIECES + NW - 1) / NW;     // halo pieces per wave and chunk
+  static_assert(BN % 64 == 0 && BM == NW / 2 * 16 * MB, "tile geometry");
+  static_assert(2 * H_BYTES + 2 * W_BYTES <= 160 * 1024, "LDS: two halo buffers and two weight slots, S <= 19");
+  static_assert(HPW <= 7, "the next chunk's halo is issued in the first seven taps");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const hbuf = smem;
+  char* const wbuf = smem + 2 * H_BYTES;
+
+  const int lane = threadIdx.x & 63;
+  const int wave = wave_id();
+  const int wm = wave >> 1, wn = wave & 1;
+  const int m0 = blockIdx.x * BM;
+  const int n0 = blockIdx.y * BN;
+  const int S = a.S;
+  const int SS = S * S;
+  const int CC = a.Cin >> 6;
+  const int G = S + 1;  // largest |tap shift| in the compact pixel index
+  const int Pc = a.offi + 1;
+
+  // --- DMA sources.  Halo piece i of a wave is piece min(8 i + wave, last) of the chunk (the waves
+  // past the last piece re-issue it: same bytes to the same rows); the padded-NHWC address of a row's
+  // pixel does not depend on the chunk, so it is computed once.
+  int hoff[HPW];
+#pragma unroll
+  for (int i = 0; i < HPW; ++i) {
+    const int k = i * NW + wave < H384_PIECES ? i * NW + wave : H384_PIECES - 1;
+    const int r = k * 8 + (lane >> 3);
+    int m = m0 - G + r;
+    m = m < 0 ? 0 : (m >= a.M ? a.M - 1 : m);
+    const int b = fdiv(m, a.divSS);
+    const int rem = m - b * SS;
+    const int ii = fdiv(rem, a.divS);
+    const int q = (b * a.HPi + ii + Pc) * a.HPi + (rem - ii * S) + Pc;
+    hoff[i] = q * a.Cin + (((lane & 7) ^ ((r >> 1) & 7)) << 3);
+  }
+  auto halo_piece = [&](int i, int c, int buf) {
+    const int k = i * NW + wave < H384_PIECES ? i * NW + wave : H384_PIECES - 1;
+    const int xo = hoff[i] + c * 64;
+#ifdef AGK_DEBUG
+    const bool ok = AGK_DCHECK(xo >= 0 && (long long)xo + 8 <= a.x_elems, DBG_FWD_X);
+    glds16(a.x + (ok ? xo : 0), hbuf + buf * H_BYTES + k * 1024);
+#else
+    glds16(a.x + xo, hbuf + buf * H_BYTES + k * 1024);
+#endif
+  };
+  int wrow[WP];
+#pragma unroll
+  for (int i = 0; i < WP; ++i) {
+    const int r = (wave * WP + i) * 8 + (lane >> 3);
+    wrow[i] = (n0 + r) * a.Cin + (((lane & 7) ^ ((r >> 1) & 7)) << 3);
+  }
+  const int wtap = a.Cout * a.Cin;  // 32-bit weight offsets (the launcher checks 9 taps fit)
+  auto w_piece = [&](int i, int wo, int slot) {  // wo: (tap, chunk) offset of the step
+    const int o = wo + wrow[i];
+#ifdef AGK_DEBUG
+    const bool ok = AGK_DCHECK((long long)o + 8 <= a.w_elems, DBG_FWD_W);
+    glds16(ok ? a.w + o : a.w, wbuf + slot * W_BYTES + (wave * WP + i) * 1024);
+#else
+    glds16(a.w + o, wbuf + slot * W_BYTES + (wave * WP + i) * 1024);
+#endif
+  };
+
+  // --- the lane's pixels: block j holds pixel m0 + 96 wm + 16 j + pix16; bit 6 t + j of okm (taps 0-4
+  // in word 0, 5-8 in word 1) = tap t of block j stays on the board.  Pixels past M (last tile) read
+  // in-range rows and are not stored.
+  const int li = lane & 15;
+  const int pix16 = li < 4 ? 2 * li : (li < 12 ? 2 * (li - 4) + 1 : 2 * (li - 12) + 8);
+  const int prel0 = G + wm * 16 * MB + pix16;  // halo row of block 0's pixel at the centre tap
+  int okm[2] = {0, 0};
+#pragma unroll
+  for (int j = 0; j < MB; ++j) {
+    int m = m0 + wm * 16 * MB + j * 16 + pix16;
+    m = m < a.M ? m : a.M - 1;
+    const int b = fdiv(m, a.divSS);
+    const int rem = m - b * SS;
+    const int py = fdiv(rem, a.divS);
+    const int px = rem - py * S;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const bool ok = (unsigned)(py + t / 3 - 1) < (unsigned)S && (unsigned)(px + t % 3 - 1) < (unsigned)S;
+      okm[t / 5] |= ok ? 1 << ((t % 5) * MB + j) : 0;
+    }
+  }
+
+  f32x4 acc[NB][MB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i)
+#pragma unroll
+    for (int j = 0; j < MB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int kq = lane >> 4;  // the lane's 16-B chunk of a k-half
+  const int wfrag0 = (wn * (BN / 2) + (lane & 15)) * 128 + ((kq ^ ((lane & 15) >> 1)) << 4);
+  bf16x8 xa[MB], wa[NB];
+  auto mfma_range = [&](int f0, int f1) {
+#pragma unroll
+    for (int f = 0; f < NMF; ++f)
+      if (f >= f0 && f < f1) acc[f / MB][f % MB] = mfma16x16x32(wa[f / MB], xa[f % MB], acc[f / MB][f % MB]);
+  };
+
+  // prologue: the zero rows of both halo buffers, chunk 0's halo, W(tap 0, chunk 0)
+  if (wave < 2) *(uint4*)(hbuf + wave * H_BYTES + H384_DATA * 128 + lane * 16) = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+  for (int i = 0; i < HPW; ++i) halo_piece(i, 0, 0);
+#pragma unroll
+  for (int i = 0; i < WP; ++i) w_piece(i, 0, 0);
+  wait_vmcnt0();
+  __syncthreads();
+
+  int ws = 0;  // weight slot of the current step
+  // one K-step: tap T of chunk c.  NEXT: chunk c + 1 exists (its halo is prefetched; tap 8 stages its W).
+  auto step = [&](auto tc, auto nc, int c) {
+    constexpr int T = decltype(tc)::value;
+    constexpr bool NEXT = decltype(nc)::value != 0;
+    constexpr int NWP = (T < 8 || NEXT) ? WP : 0;       // weight pieces of the next step
+    constexpr int NHP = (NEXT && T < HPW) ? 1 : 0;      // halo piece of the next chunk
+    constexpr int NDMA = NWP + NHP;
+    constexpr int MPD = NMF / (NDMA + 1);
+    const char* hb = hbuf + (c & 1) * H_BYTES;
+    const char* wb = wbuf + ws * W_BYTES + wfrag0;
+    const int toff = (T / 3 - 1) * S + (T % 3 - 1);
+    // The fragment offsets of a tap do not depend on the chunk: left alone, the compiler hoists all
+    // 9 x 6 x 2 of them (and 54 lane masks of the border test) out of the chunk loop and spills.  The
+    // empty asm makes them per-step values.
+    int pr = prel0, om = okm[T / 5];
+    asm volatile("" : "+v"(pr), "+v"(om));
+    int xo[MB];
+#pragma unroll
+    for (int j = 0; j < MB; ++j) {
+      const int r = pr + j * 16 + toff;
+      // a tap off the board: the zero row with the lane's (row parity, chunk) bank slot
+      const int row = (om & (1 << ((T % 5) * MB + j))) ? r : H384_DATA + (r & 7);
+      xo[j] = row * 128 + ((kq ^ ((r >> 1) & 7)) << 4);
+    }
+#pragma unroll
+    for (int j = 0; j < MB; ++j) xa[j] = *(const bf16x8*)(hb + xo[j]);
+#pragma unroll
+    for (int i = 0; i < NB; ++i) wa[i] = *(const bf16x8*)(wb + i * 16 * 128);
+    int wo = T < 8 ? (T + 1) * wtap + c * 64 : (c + 1) * 64;
+    asm volatile("" : "+s"(wo));  // likewise: no per-tap 64-bit lane addresses hoisted out of the chunk loop
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int d = 0; d < NDMA; ++d) {
+      mfma_range(d * MPD, (d + 1) * MPD);
+      __builtin_amdgcn_sched_barrier(0);
+      if (d < NWP) w_piece(d, wo, ws ^ 1);
+      else halo_piece(T, c + 1, (c + 1) & 1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    mfma_range(NDMA * MPD, NMF);
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
+    // second k-half: chunk index ^ 4 = byte offset ^ 64
+#pragma unroll
+    for (int j = 0; j < MB; ++j) xa[j] = *(const bf16x8*)(hb + (xo[j] ^ 64));
+#pragma unroll
+    for (int i = 0; i < NB; ++i) wa[i] = *(const bf16x8*)(wbuf + ws * W_BYTES + (wfrag0 ^ 64) + i * 16 * 128);
+    __builtin_amdgcn_s_setprio(1);
+    mfma_range(0, NMF);
+    __builtin_amdgcn_s_setprio(0);
+    wait_vmcnt0();
+    __syncthreads();
+    ws ^= 1;
+  };
+  auto chunk = [&](auto nc, int c) {
+    step(IntC<0>{}, nc, c);
+    step(IntC<1>{}, nc, c);
+    step(IntC<2>{}, nc, c);
+    step(IntC<3>{}, nc, c);
+    step(IntC<4>{}, nc, c);
+    step(IntC<5>{}, nc, c);
+    step(IntC<6>{}, nc, c);
+    step(IntC<7>{}, nc, c);
+    step(IntC<8>{}, nc, c);
+  };
+  for (int c = 0; c + 1 < CC; ++c) chunk(IntC<1>{}, c);
+  chunk(IntC<0>{}, CC - 1);
+
+  // (opaque: the epilogue's pixel addresses share the border test's divisions; computed before the
+  // loop they would be spilled across it)
+  int ep_mrow = m0 + wm * 16 * MB + pix16;
+  asm volatile("" : "+v"(ep_mrow));
+  const int ep_nbase = n0 + wn * (BN / 2) + ((lane >> 4) << 2);
+  ConvEpilogue<NB, MB, MODE> ep;
+  ep.load(a, ep_mrow, ep_nbase, wn);
+  ep.store(a, acc, ep_mrow);
+}
+
+// tile code 388: covers 3x3, Cin % 64 == 0, S <= 19 at BN = 192 in the bias + ReLU forward and the bitmask dgrad
+template <int BN, int MODE>
+static bool halo384_covers(const ConvFwdArgs& a) {
+  return BN == 192 && (MODE == MODE_BIAS_RELU || MODE == MODE_MASKBITS) && a.K == 3 && a.Cin % 64 == 0 &&
+         a.Cin >= 64 && a.S <= H384_SMAX && a.offi >= 0 && 9ll * a.Cout * a.Cin < (1ll << 31);
+}
+
+template <int BN, int MODE>
+static void launch_fwd_halo384(const ConvFwdArgs& a, hipStream_t st) {
+  if constexpr (BN == 192 && (MODE == MODE_BIAS_RELU || MODE == MODE_MASKBITS)) {
+    constexpr int smem = 2 * H384_ROWS * 128 + 2 * BN * 128;
+    static const hipError_t attr = hipFuncSetAttribute((const void*)conv_fwd_halo384_kernel<BN, MODE>,
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
+    dim3 grid((a.M + H384_BM - 1) / H384_BM, a.Cout / BN);
+    hipLaunchKernelGGL((conv_fwd_halo384_kernel<BN, MODE>), grid, dim3(512), smem, st, a);
+  } else {
+    throw std::invalid_argument("conv_fwd: tile 388 is the 192-wide forward / bitmask dgrad");
+  }
+}
+
 // Split-K finish: one thread per (pixel, bitmask word); word w of a pixel covers the channels
 // tn * BN + wn * BN/2 + 4 q + 16 i + r (tn = w / 8, wn = (w / 4) % 2, q = w % 4; i < NB = BN / 32,
 // r < 4) -- the channels one lane of the conv epilogue owns, so the bitmask layout is the tile's.

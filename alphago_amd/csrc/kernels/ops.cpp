@@ -13,10 +13,11 @@ void conv_fwd(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bia
               const c10::optional<Tensor>& mbits, int64_t tile) {
   check_dev("conv_fwd", x, w, bias, mask, y, mbits);
   // production tilings only: 0 = automatic, or a fixed 64 / 128 / 256 / 384-pixel tile (385: 384 with the
-  // LDS-DMA issue spread through the MFMAs; 386 / 387: 385 / 384 with the chunk-outer K order)
+  // LDS-DMA issue spread through the MFMAs; 386 / 387: 385 / 384 with the chunk-outer K order; 388: 386 with
+  // the pixel rows staged once per 64-channel chunk, 386 where it does not apply)
   TORCH_CHECK(tile == 0 || tile == 36 || tile == 37 || tile == 40 || tile == 64 || tile == 128 || tile == 256 ||
-                  tile == 384 || tile == 385 || tile == 386 || tile == 387,
-              "conv_fwd tile ", tile, " is not a production tiling (0, 36, 37, 40, 64, 128, 256, 384-387); kernel-lab "
+                  tile == 384 || tile == 385 || tile == 386 || tile == 387 || tile == 388,
+              "conv_fwd tile ", tile, " is not a production tiling (0, 36, 37, 40, 64, 128, 256, 384-388); kernel-lab "
               "variants are in torch.ops.alphago_amd_lab (alphago_amd.ops.lab())");
   conv_fwd_impl(x, w, bias, mask, y, K, S, Pin, Po, mode, mbits, (int)tile);
 }
@@ -69,7 +70,7 @@ void conv_wgrad(const Tensor& x, const Tensor& dz, const Tensor& slab, const Ten
 void conv_dgrad_bits_bf8(const Tensor& dz, const Tensor& wd, const Tensor& dx, const Tensor& mbits, const Tensor& dx8,
                          const Tensor& scale, const c10::optional<Tensor>& amax, int64_t K, int64_t S, int64_t tile) {
   check_dev("conv_dgrad_bits_bf8", dz, wd, dx, mbits, dx8, scale, amax);
-  TORCH_CHECK(tile == 0 || tile == 64 || tile == 128 || tile == 256 || (tile >= 384 && tile <= 387),
+  TORCH_CHECK(tile == 0 || tile == 64 || tile == 128 || tile == 256 || (tile >= 384 && tile <= 388),
               "conv_dgrad_bits_bf8: production tile codes only");
   conv_fwd_impl(dz, wd, c10::nullopt, c10::nullopt, dx, K, S, 1, 1, agk::MODE_MASKBITS, mbits, (int)tile, nullptr, -1,
                 dx8, scale, amax);

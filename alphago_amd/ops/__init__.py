@@ -125,8 +125,11 @@ def conv_fwd(x, w_packed, bias, y, K: int, S: int, Pin: int, Po: int = 1, mode: 
              mbits=None, tile: int = 0):
     """Conv + epilogue.  mode 0: bias + ReLU (mbits: also write the ReLU' bitmask);
     1: dgrad masked by ``mask`` > 0; 3: dgrad masked by the ``mbits`` bitmask.
-    ``tile``: 0 = automatic, or a production tiling 128 / 256 / 384 / 385 (384 with the DMA issue
-    spread through the MFMAs; the automatic choice for large batches)."""
+    ``tile``: 0 = automatic, or a production tiling: 36 / 37 (32 pixels), 40 (weight-stationary), 64 /
+    128 / 256, 384 (96 x 96 per wave), 385 (384 with the DMA issue spread through the MFMAs), 386 / 387
+    (385 / 384 with the chunk-outer K order), 388 (386 with the pixel rows staged once per 64-channel
+    chunk -- the compact halo; 3x3, 192-wide output tile, S <= 19, bias + ReLU and bitmask dgrad, else it
+    runs 386; the automatic choice for large batches, bit-identical to 386)."""
     _ops().conv_fwd(x, w_packed, bias, mask, y, K, S, Pin, Po, mode, mbits, tile)
     return y
 

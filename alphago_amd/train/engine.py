@@ -221,7 +221,7 @@ class HipConvTrainer:
         # wgrad kernel: 0 = per-tap kernel (default), 5 = one-kernel-row wgrad (opt-in, slower so far)
         self.wgrad_variant = int(os.environ.get("ALPHAGO_AMD_WGRAD_VARIANT", "0")) if wgrad_variant is None \
             else int(wgrad_variant)
-        self.conv_tile = conv_tile  # forward/dgrad tiling: 0 = automatic, or 128 / 256 / 384 / 385
+        self.conv_tile = conv_tile  # forward/dgrad tiling: 0 = automatic, or a production code (ops.conv_fwd)
         # kernel-lab A/B only: the 3x3 forwards and dgrads on a lab tiling of the lab library
         # (torch.ops.alphago_amd_lab), e.g. 5 = compact halo + ping-pong (profiles/r3_chunk_outer.md)
         self.lab_tile = int(os.environ.get("ALPHAGO_AMD_LAB_TILE", "0"))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Power-limited steady-state A/B of conv kernels (10 s each, socket power sampled by amd-smi).
 # KERNELS="fwd:385 fwd:386 fwd:lab5 ..." (see scripts/probes/conv_power_probe.py)
-set -e
+set -e -o pipefail  # a probe that fails ends the run: nothing more is started on the GPU
 O=${OUT:-gpurun_out/cpab}
 mkdir -p $O
 export PYTHONPATH=$PWD

@@ -3,7 +3,7 @@ state); the caller samples socket power.  Usage: conv_power_probe.py KIND:TILE [
   KIND  fwd (3x3, 192 -> 192, bias + ReLU + bitmask), dgrad (3x3, bitmask ReLU'), fwd5 (5x5 layer 0,
         48 planes padded to 64), wgrad (3x3 split-K + reduce), wino (kernel-lab Winograd forward,
         bias + ReLU, PF counted as the direct conv's FLOPs)
-  TILE  a production tile code (0, 384-387) or labN for a kernel-lab tiling"""
+  TILE  a production tile code (0, 384-388; 388 = the compact-halo 384 tile) or labN for a kernel-lab tiling"""
 import json
 import sys
 import time
