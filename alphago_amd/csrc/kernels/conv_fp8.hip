@@ -673,11 +673,20 @@ static void launch_fp8_ga(const ConvFp8Args& a, hipStream_t st) {
   else launch_fp8_ga_cw<BN, MB, NPART, OB, OF, DG, DGB, DGBITS, 64, NW ? NW : 8, stg>(a, st);
 }
 
-// fp8 dgrad of the fp8-wgrad value step: e5m2 operand (the previous dgrad's copy), bitmask ReLU',
-// e5m2 and/or bf16 outputs; the 160-wide value tile only
-template <bool OB, bool OF>
+// fp8 dgrad of the all-fp8 backward: e5m2 operand (the previous dgrad's copy), bitmask ReLU',
+// e5m2 and/or bf16 outputs; the 160-wide value tile and the 192-wide policy tile (the tilings of the
+// plain fp8 dgrad at those widths)
+template <int BN, bool OB, bool OF>
 static void launch_fp8_dgrad_bits_t(const ConvFp8Args& a, hipStream_t st) {
-  launch_fp8_ga<160, 3, 5, OB, OF, true, false, true>(a, st);
+  if constexpr (BN == 160) launch_fp8_ga<160, 3, 5, OB, OF, true, false, true>(a, st);
+  else launch_fp8_ga<192, 3, 4, OB, OF, true, false, true>(a, st);
+}
+
+template <int BN>
+static void launch_fp8_dgrad_bits_bn(const ConvFp8Args& a, hipStream_t st) {
+  if (a.y_bf16 && a.y_fp8) launch_fp8_dgrad_bits_t<BN, true, true>(a, st);
+  else if (a.y_bf16) launch_fp8_dgrad_bits_t<BN, true, false>(a, st);
+  else launch_fp8_dgrad_bits_t<BN, false, true>(a, st);
 }
 
 // fp8 dgrad from the bf16 gradient (in-register e5m2 conversion, bitmask ReLU', bf16 output)
@@ -789,10 +798,10 @@ void launch_conv_fwd_fp8(const ConvFp8Args& a_in, hipStream_t st) {
     return;
   }
   if (a.dgrad && a.mbits_in) {
-    if (a.Cout != 160) throw std::invalid_argument("conv_dgrad_fp8_bits: 160-wide value layers only");
-    if (a.y_bf16 && a.y_fp8) launch_fp8_dgrad_bits_t<true, true>(a, st);
-    else if (a.y_bf16) launch_fp8_dgrad_bits_t<true, false>(a, st);
-    else launch_fp8_dgrad_bits_t<false, true>(a, st);
+    if (a.Cout == 160) launch_fp8_dgrad_bits_bn<160>(a, st);
+    else if (a.Cout == 192) launch_fp8_dgrad_bits_bn<192>(a, st);
+    else throw std::invalid_argument("conv_dgrad_fp8_bits: 160- and 192-wide layers only (got " +
+                                     std::to_string(a.Cout) + ")");
     return;
   }
   if (a.dgrad) {

@@ -25,6 +25,24 @@
 // saturated e5m2 value reads 57344 / 2^eg, so a scale that overflows shrinks by the margin every step
 // until it fits).
 // Borders: pixels past the batch read padded-pixel 0 of dZ (always zero).
+//
+// Widths.  The kernel is a template over the dZ row width WN (= Cout), the X row piece WC and the
+// waves per workgroup; 160 (value trunk) runs <160, 160, 4 waves> exactly as before.
+// 192 (policy trunk, 12 x 192): a 192 x 192 tile double-buffered is 98,304 B of LDS, one workgroup per
+// CU, so the production tile is 192 (n) x 96 (c): whole 192-byte dZ rows plus a 96-byte half of X's
+// rows, 2 x (24,576 + 12,288) = 73,728 B, two workgroups per CU as at 160, 4 waves of 96 x 48
+// (18 f32x4 accumulators), grid z = 2 (dZ is staged by both halves).  The rejected alternative, one
+// 8-wave 192 x 192 workgroup per CU (the same 96 x 48 per wave, dZ staged once), is kept in the
+// kernel-lab build as probe 16.  Compiler report: 192 x 96 222 VGPRs, 192 x 192 200 VGPRs, both no
+// scratch and 2 waves per SIMD.  Layer at B = 2176 with the reduce, three alternating rounds on one
+// MI355X: bf16 wgrad 557-560 us, 192 x 96 366-367 us, 192 x 192 390 us (profiles/r9/README.md).
+// Bank layout: ds_read_b64_tr_b8 serves 32 lanes (16 rows x 16 B) per LDS cycle.  At a 160- or 96-byte
+// pitch rows R and R + 8 share banks (8 x pitch is a multiple of 256 B) and the eight rows between
+// them do not: one chunk of rotation by (R >> 3) & 1.  At a 192-byte pitch 4 x 192 = 768 B is already
+// a multiple of 256, so rows R, R + 4, R + 8 and R + 12 share banks: the rotation there is
+// (R >> 2) & 3 chunks, which spreads the four rows over the 64-byte bank group they share, and the
+// wrap fix-up (rotated chunk index past the row's end -> minus one pitch) covers the last three
+// blocks of the last wave's range instead of the last one.
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
@@ -66,25 +84,48 @@ __device__ __forceinline__ float bf8_to_f32(unsigned byte) {
   return (float)__builtin_bit_cast(_Float16, (unsigned short)(byte << 8));
 }
 
-constexpr int kStepPx = 128;               // pixels per K-step (one 16x16x128 MFMA deep)
-constexpr int kImgBytes = kStepPx * 160;  // one operand image of a step: 128 pixel rows x 160 B
+constexpr int kStepPx = 128;  // pixels per K-step (one 16x16x128 MFMA deep)
 
-// WN x WC tile of one tap per workgroup, 4 waves as 2 (n) x 2 (c); each lane stages the same rows
-// of both operands, so one pixel decomposition serves a dz piece and an x piece.
+// chunk rotation of LDS row R at a row pitch of P bytes: (R >> rot_shift) & rot_mask (header comment)
+constexpr int rot_shift(int P) { return P % 64 == 0 && P % 128 != 0 ? 2 : 3; }
+constexpr int rot_mask(int P) { return P % 64 == 0 && P % 128 != 0 ? 3 : 1; }
+
+// one lane's 16-byte unit of a staged operand image: LDS row -> K position and source chunk
+template <int P>
+__device__ __forceinline__ void stage_unit(int idx, int& k, int& c16) {
+  constexpr int NCH = P / 16;
+  const int R = idx / NCH, pos = idx - R * NCH;
+  int c = pos - ((R >> rot_shift(P)) & rot_mask(P));
+  c = c < 0 ? c + NCH : c;  // source chunk (16 channels) of this LDS unit
+  k = 32 * ((R >> 3) & 3) + 8 * (R >> 5) + (R & 7);
+  c16 = c * 16;
+}
+
+// WN x WC tile of one tap per workgroup, NWV waves as 2 (n) x NWV/2 (c).  WN is the whole dZ row
+// (= Cout); WC is the staged piece of X's rows (Cin, or half of it).  With WN == WC each lane stages
+// the same rows of both operands, so one pixel decomposition serves a dz piece and an x piece.
 // PROBE (kernel-lab timing probes, wrong values): bit 1 no MFMA, 2 no staging loads, 4 no LDS
 // fragment reads, 8 no partial-tile stores
-template <int WN, int WC, int PROBE = 0>
-__global__ __launch_bounds__(256, 2) void conv_wgrad_fp8_kernel(ConvWgradFp8Args a) {
-  static_assert(WN == 160 && WC == 160, "line staging: whole 160-channel pixel rows");
-  constexpr int NBn = WN / 32;  // 16-blocks per wave (a wave covers WN/2 x WC/2)
-  constexpr int NBc = WC / 32;
-  constexpr int STAGE = 2 * kImgBytes;  // dz image, then x image
-  static_assert(WN % 32 == 0 && WC % 32 == 0, "two waves per dimension, 32-channel blocks");
+template <int WN, int WC, int NWV, int PROBE = 0>
+__global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv_wgrad_fp8_kernel(ConvWgradFp8Args a) {
+  static_assert((WN == 160 && WC == 160) || (WN == 192 && (WC == 192 || WC == 96)),
+                "line staging: whole 160- or 192-channel dZ rows, X rows whole or (192) in halves");
+  static_assert(NWV == 4 || NWV == 8, "4 waves (two workgroups per CU) or 8 (one)");
+  constexpr int NWC = NWV / 2;         // waves along c
+  constexpr int NBn = WN / 32;         // 16-blocks per wave (a wave covers WN/2 x WC/NWC)
+  constexpr int NBc = WC / (16 * NWC);
+  constexpr int kImgA = kStepPx * WN;  // dz image of a step: 128 pixel rows x WN B
+  constexpr int kImgB = kStepPx * WC;  // x image: 128 pixel rows x WC B
+  constexpr int STAGE = kImgA + kImgB;
+  constexpr bool SAME = WN == WC;
+  constexpr int MKA = rot_mask(WN), MKB = rot_mask(WC);
+  static_assert(WN % 32 == 0 && WC % (16 * NWC) == 0, "two waves along n, 16-channel blocks");
+  static_assert(MKA <= NBn && MKB <= NBc, "only the last wave's range wraps");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int lane = threadIdx.x & 63;
   const int wave = wave_id();
-  const int wn = wave >> 1, wc = wave & 1;
+  const int wn = wave / NWC, wc = wave % NWC;
   const int split = blockIdx.x;
   const int t = blockIdx.y;
   const int ncb = a.Cin / WC;
@@ -99,24 +140,27 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_fp8_kernel(ConvWgradFp8Args
   if (ks_end > nks_total) ks_end = nks_total;
   const int sa = *a.gscale, sb = *a.xscale;  // E8M0 exponents (dZ, X)
 
-  constexpr int NPAIR = kStepPx * WC / 4096;  // 1-KB pieces per operand image per wave
+  constexpr int NPA = kImgA / (NWV * 1024);  // 1-KB pieces per wave of the dz image
+  constexpr int NPB = kImgB / (NWV * 1024);  // ... of the x image
+  static_assert(kImgA % (NWV * 1024) == 0 && kImgB % (NWV * 1024) == 0, "whole 1-KB pieces per wave");
+  constexpr int NPX = SAME ? 1 : NPB;        // x pieces with a pixel decomposition of their own
   // Each lane's pixel of piece i advances by exactly 128 pixels per stage() call (consecutive steps),
   // so the (row, column) decomposition and both padded pixel indices are carried from step to step
   // with adds and selects: the per-step divisions and 32-bit multiplies of a fresh decomposition
   // (quarter-rate on CDNA: ~1300 of the SIMD's cycles per wave and step, more than the step's 25
   // MFMAs) are paid once here.  Past the batch: dz pixel 0 (a zero border) and x pixel 0.
-  int spx[NPAIR], sii[NPAIR], sjx[NPAIR], spo[NPAIR], spi[NPAIR], sc16[NPAIR];
+  // WN == WC: piece i of both images holds the same pixels (spi rides on the dz decomposition);
+  // otherwise the x pieces carry their own (xpx, xii, xjx).
+  int spx[NPA], sii[NPA], sjx[NPA], spo[NPA], sc16[NPA];
+  int spi[SAME ? NPA : NPB], xpx[NPX], xii[NPX], xjx[NPX], xc16[NPX];
   const int DB = kStepPx / SS, DI = (kStepPx % SS) / a.S, DJ = kStepPx % a.S;
   const int stepo = (DB * a.HPo + DI) * a.HPo + DJ, stepi = (DB * a.HPi + DI) * a.HPi + DJ;
   const int wjo = a.HPo - a.S, wjo_i = (a.HPo - a.S) * a.HPo;
   const int wji = a.HPi - a.S, wji_i = (a.HPi - a.S) * a.HPi;
 #pragma unroll
-  for (int i = 0; i < NPAIR; ++i) {
-    const int idx = (wave * NPAIR + i) * 64 + lane;  // 16-byte unit of the image
-    const int R = idx / 10, pos = idx - R * 10;
-    int c = pos - ((R >> 3) & 1);
-    c = c < 0 ? c + 10 : c;  // source chunk (16 channels) of this LDS unit
-    const int k = 32 * ((R >> 3) & 3) + 8 * (R >> 5) + (R & 7);
+  for (int i = 0; i < NPA; ++i) {
+    int k, c16;
+    stage_unit<WN>((wave * NPA + i) * 64 + lane, k, c16);  // 16-byte unit of the image
     const int px = ks_begin * kStepPx + k;
     const int b = fdiv(px, a.divSS);
     const int rem = px - b * SS;
@@ -126,35 +170,66 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_fp8_kernel(ConvWgradFp8Args
     sii[i] = ii;
     sjx[i] = jx;
     spo[i] = (b * a.HPo + ii + a.Po) * a.HPo + jx + a.Po;
-    spi[i] = (b * a.HPi + ii + a.offi) * a.HPi + jx + a.offi;
-    sc16[i] = c * 16;
+    if constexpr (SAME) spi[i] = (b * a.HPi + ii + a.offi) * a.HPi + jx + a.offi;
+    sc16[i] = c16;
   }
+  if constexpr (!SAME) {
+#pragma unroll
+    for (int i = 0; i < NPB; ++i) {
+      int k, c16;
+      stage_unit<WC>((wave * NPB + i) * 64 + lane, k, c16);
+      const int px = ks_begin * kStepPx + k;
+      const int b = fdiv(px, a.divSS);
+      const int rem = px - b * SS;
+      const int ii = fdiv(rem, a.divS);
+      const int jx = rem - ii * a.S;
+      xpx[i] = px;
+      xii[i] = ii;
+      xjx[i] = jx;
+      spi[i] = (b * a.HPi + ii + a.offi) * a.HPi + jx + a.offi;
+      xc16[i] = c16;
+    }
+  }
+  // the next step's pixel: (row, column) with carries; w1 / w2 = the column / row wrapped
+  auto advance = [&](int& px, int& ii_, int& jx_, bool& w1, bool& w2) {
+    px += kStepPx;
+    int jx = jx_ + DJ;
+    w1 = jx >= a.S;
+    jx = w1 ? jx - a.S : jx;
+    int ii = ii_ + DI + (w1 ? 1 : 0);
+    w2 = ii >= a.S;
+    ii = w2 ? ii - a.S : ii;
+    jx_ = jx;
+    ii_ = ii;
+  };
   auto stage = [&](int buf) {
     if constexpr ((PROBE & 2) != 0) return;
     char* base = smem + buf * STAGE;
-    int dzo[NPAIR], xo[NPAIR];
+    int dzo[NPA], xo[NPB];
 #pragma unroll
-    for (int i = 0; i < NPAIR; ++i) {
+    for (int i = 0; i < NPA; ++i) {
       const bool in = spx[i] < a.M;
       dzo[i] = (in ? (int)__umul24((unsigned)spo[i], (unsigned)a.Cout) : 0) + sc16[i];
-      xo[i] = (in ? (int)__umul24((unsigned)spi[i], (unsigned)a.Cin) : 0) + toff + sc16[i];
-      // advance to the next step's pixel
-      spx[i] += kStepPx;
-      int jx = sjx[i] + DJ;
-      const bool w1 = jx >= a.S;
-      jx = w1 ? jx - a.S : jx;
-      int ii = sii[i] + DI + (w1 ? 1 : 0);
-      const bool w2 = ii >= a.S;
-      ii = w2 ? ii - a.S : ii;
-      sjx[i] = jx;
-      sii[i] = ii;
+      if constexpr (SAME) xo[i] = (in ? (int)__umul24((unsigned)spi[i], (unsigned)a.Cin) : 0) + toff + sc16[i];
+      bool w1, w2;
+      advance(spx[i], sii[i], sjx[i], w1, w2);
       spo[i] += stepo + (w1 ? wjo : 0) + (w2 ? wjo_i : 0);
-      spi[i] += stepi + (w1 ? wji : 0) + (w2 ? wji_i : 0);
+      if constexpr (SAME) spi[i] += stepi + (w1 ? wji : 0) + (w2 ? wji_i : 0);
+    }
+    if constexpr (!SAME) {
+#pragma unroll
+      for (int i = 0; i < NPB; ++i) {
+        const bool in = xpx[i] < a.M;
+        xo[i] = (in ? (int)__umul24((unsigned)spi[i], (unsigned)a.Cin) : 0) + toff + xc16[i];
+        bool w1, w2;
+        advance(xpx[i], xii[i], xjx[i], w1, w2);
+        spi[i] += stepi + (w1 ? wji : 0) + (w2 ? wji_i : 0);
+      }
     }
 #pragma unroll
-    for (int i = 0; i < NPAIR; ++i) glds16(a.dz8 + dzo[i], base + (wave * NPAIR + i) * 1024);
+    for (int i = 0; i < NPA; ++i) glds16(a.dz8 + dzo[i], base + (wave * NPA + i) * 1024);
 #pragma unroll
-    for (int i = 0; i < NPAIR; ++i) glds16(a.x8 + xo[i], base + kImgBytes + (wave * NPAIR + i) * 1024);
+    for (int i = 0; i < NPB; ++i) glds16(a.x8 + xo[i], base + kImgA + (wave * NPB + i) * 1024);
   };
 
   f32x4 acc[NBn][NBc];
@@ -179,6 +254,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_fp8_kernel(ConvWgradFp8Args
   // the rotated 16-byte chunk of its block
   const int g = lane >> 4, li = lane & 15;
   const int lrow = 8 * g + (li >> 1);
+  // the row's chunk rotation (rows 32 j + lrow of every read j rotate alike)
+  const int rotA = (lrow >> rot_shift(WN)) & MKA, rotB = (lrow >> rot_shift(WC)) & MKB;
 
   if (ks_begin < ks_end) {
     stage(0);
@@ -192,24 +269,32 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_fp8_kernel(ConvWgradFp8Args
     i32x8 af[NBn];
     {
       // lane base (row lrow, the rotated chunk of block 0 of the wave's range) + immediate offsets;
-      // the range's last block (index 4 of 5) wraps to chunk 0 on rotated rows of the upper wave.
+      // the last rot_mask blocks of the range (index 4 of 5 at 160) wrap to the row's first chunks
+      // on rotated rows of the last wave: bnw / bcw are the bases one pitch lower where they do.
       // All A fragments are read first; the B fragments of block C + 1 are read under block C's
       // MFMAs (a 2-deep ring of 8 registers instead of all 40: the step otherwise spills).
-      const uint32_t b0 = (uint32_t)(uintptr_t)AG_LDS(base) + lrow * 160 + 8 * (li & 1) + (g & 1) * 16;
-      const uint32_t bn = b0 + wn * NBn * 16, bc = b0 + kImgBytes + wc * NBc * 16;
-      const uint32_t bn4 = bn - ((wn == 1 && (g & 1)) ? 160 : 0), bc4 = bc - ((wc == 1 && (g & 1)) ? 160 : 0);
+      const uint32_t b0 = (uint32_t)(uintptr_t)AG_LDS(base) + 8 * (li & 1);
+      const uint32_t bn = b0 + lrow * WN + (rotA + wn * NBn) * 16;
+      const uint32_t bc = b0 + kImgA + lrow * WC + (rotB + wc * NBc) * 16;
+      uint32_t bnw[MKA], bcw[MKB];  // block NB - MK + d wraps where its rotation is >= MK - d
+#pragma unroll
+      for (int d = 0; d < MKA; ++d) bnw[d] = bn - ((wn == 1 && rotA >= MKA - d) ? WN : 0);
+#pragma unroll
+      for (int d = 0; d < MKB; ++d) bcw[d] = bc - ((wc == NWC - 1 && rotB >= MKB - d) ? WC : 0);
+      auto abase = [&](auto I) { return I >= NBn - MKA ? bnw[I >= NBn - MKA ? I - (NBn - MKA) : 0] : bn; };
+      auto bbase = [&](auto C) { return C >= NBc - MKB ? bcw[C >= NBc - MKB ? C - (NBc - MKB) : 0] : bc; };
       u32x2 ra[NBn][4], rb[2][4];
       if constexpr ((PROBE & 4) != 0) {
         static_for<4>([&](auto J) {
-          static_for<NBn>([&](auto I) { ra[I][J] = u32x2{bn + I * 7u + J, bn4 ^ (unsigned)ks}; });
-          rb[0][J] = u32x2{bc + J, bc4 ^ (unsigned)ks};
+          static_for<NBn>([&](auto I) { ra[I][J] = u32x2{bn + I * 7u + J, bnw[0] ^ (unsigned)ks}; });
+          rb[0][J] = u32x2{bc + J, bcw[0] ^ (unsigned)ks};
           rb[1][J] = rb[0][J];
         });
       } else {
         static_for<4>([&](auto J) {
-          static_for<NBn>([&](auto I) { ra[I][J] = ds_read_tr8_off<J * 32 * 160 + I * 16>(I == NBn - 1 ? bn4 : bn); });
+          static_for<NBn>([&](auto I) { ra[I][J] = ds_read_tr8_off<J * 32 * WN + I * 16>(abase(I)); });
         });
-        static_for<4>([&](auto J) { rb[0][J] = ds_read_tr8_off<J * 32 * 160>(bc); });
+        static_for<4>([&](auto J) { rb[0][J] = ds_read_tr8_off<J * 32 * WC>(bbase(std::integral_constant<int, 0>{})); });
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
@@ -221,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_fp8_kernel(ConvWgradFp8Args
         constexpr int cb = C & 1, nb = (C + 1) & 1;
         if constexpr (C + 1 < NBc && (PROBE & 4) == 0)
           static_for<4>([&](auto J) {
-            rb[nb][J] = ds_read_tr8_off<J * 32 * 160 + (C + 1) * 16>(C + 1 == NBc - 1 ? bc4 : bc);
+            rb[nb][J] = ds_read_tr8_off<J * 32 * WC + (C + 1) * 16>(bbase(std::integral_constant<int, C + 1>{}));
           });
         const i32x8 bm = i32x8{(int)rb[cb][0].x, (int)rb[cb][0].y, (int)rb[cb][1].x, (int)rb[cb][1].y,
                                (int)rb[cb][2].x, (int)rb[cb][2].y, (int)rb[cb][3].x, (int)rb[cb][3].y};
@@ -262,7 +347,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_fp8_kernel(ConvWgradFp8Args
 
   // --- the split's partial tile: D[n][c], lane owns n..n+3 at column c
   const int nb0 = n0 + wn * (WN / 2) + ((lane >> 4) << 2);
-  const int cbase = c0 + wc * (WC / 2) + (lane & 15);
+  const int cbase = c0 + wc * (WC / NWC) + (lane & 15);
   float* out = a.slab + ((size_t)split * a.T + t) * (size_t)a.Cout * a.Cin;
 #pragma unroll
   for (int i = 0; i < NBn; ++i)
@@ -299,16 +384,19 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_fp8_kernel(ConvWgradFp8Args
 
 }  // namespace
 
-int wgrad_fp8_supported(int Cout, int Cin, int K) { return Cout == 160 && Cin == 160 && K == 3 ? 1 : 0; }
+int wgrad_fp8_supported(int Cout, int Cin, int K) {
+  return (Cout == 160 || Cout == 192) && Cin == Cout && K == 3 ? 1 : 0;
+}
 
-template <int WN, int WC, int PROBE>
+template <int WN, int WC, int NWV, int PROBE>
 static void launch_wgrad_fp8_t(const ConvWgradFp8Args& a, hipStream_t st) {
-  constexpr int smem = 2 * 2 * kImgBytes;  // two stages of two images
-  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_wgrad_fp8_kernel<WN, WC, PROBE>,
+  constexpr int smem = 2 * kStepPx * (WN + WC);  // two stages of two images
+  static_assert(smem * (8 / NWV) <= 160 * 1024, "LDS of the resident workgroups");
+  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_wgrad_fp8_kernel<WN, WC, NWV, PROBE>,
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, smem);
   hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
   dim3 grid(a.nsplit, a.T, (a.Cout / WN) * (a.Cin / WC));
-  hipLaunchKernelGGL((conv_wgrad_fp8_kernel<WN, WC, PROBE>), grid, dim3(256), smem, st, a);
+  hipLaunchKernelGGL((conv_wgrad_fp8_kernel<WN, WC, NWV, PROBE>), grid, dim3(64 * NWV), smem, st, a);
 }
 
 void launch_conv_wgrad_fp8(const ConvWgradFp8Args& a_in, hipStream_t st) {
@@ -316,13 +404,23 @@ void launch_conv_wgrad_fp8(const ConvWgradFp8Args& a_in, hipStream_t st) {
   a.divSS = make_fastdiv((uint32_t)(a.S * a.S));
   a.divS = make_fastdiv((uint32_t)a.S);
   if (!wgrad_fp8_supported(a.Cout, a.Cin, a.K))
-    throw std::invalid_argument("conv_wgrad_fp8: 160 -> 160 3x3 layers only");
+    throw std::invalid_argument("conv_wgrad_fp8: 160 -> 160 and 192 -> 192 3x3 layers only (got " +
+                                std::to_string(a.Cin) + " -> " + std::to_string(a.Cout) + ", K " +
+                                std::to_string(a.K) + ")");
+  if (a.Cout == 192) {
+#ifdef AGK_KERNEL_LAB
+    // probe 16: the rejected tile (one 8-wave 192 x 192 workgroup per CU), for the A/B in profiles/r9
+    if (a.probe == 16) return launch_wgrad_fp8_t<192, 192, 8, 0>(a, st);
+#endif
+    if (a.probe != 0) throw std::invalid_argument("conv_wgrad_fp8: the timing probes run at 160 only");
+    return launch_wgrad_fp8_t<192, 96, 4, 0>(a, st);
+  }
   constexpr int WN = 160, WC = 160;
 #ifdef AGK_KERNEL_LAB
   switch (a.probe) {
-    case 0: launch_wgrad_fp8_t<WN, WC, 0>(a, st); break;
+    case 0: launch_wgrad_fp8_t<WN, WC, 4, 0>(a, st); break;
 #define AGK_WG8_PROBE(P) \
-  case P: launch_wgrad_fp8_t<WN, WC, P>(a, st); break;
+  case P: launch_wgrad_fp8_t<WN, WC, 4, P>(a, st); break;
     AGK_WG8_PROBE(1) AGK_WG8_PROBE(2) AGK_WG8_PROBE(4) AGK_WG8_PROBE(8) AGK_WG8_PROBE(3) AGK_WG8_PROBE(5)
     AGK_WG8_PROBE(6) AGK_WG8_PROBE(7) AGK_WG8_PROBE(14) AGK_WG8_PROBE(15)
 #undef AGK_WG8_PROBE
@@ -330,7 +428,7 @@ void launch_conv_wgrad_fp8(const ConvWgradFp8Args& a_in, hipStream_t st) {
   }
 #else
   if (a.probe != 0) throw std::invalid_argument("conv_wgrad_fp8: timing probes are kernel-lab code");
-  launch_wgrad_fp8_t<WN, WC, 0>(a, st);
+  launch_wgrad_fp8_t<WN, WC, 4, 0>(a, st);
 #endif
 }
 

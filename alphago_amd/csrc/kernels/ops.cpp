@@ -237,6 +237,10 @@ void policy_head(const Tensor& y, const Tensor& w, const Tensor& b, const c10::o
   }
   a.ent_coef = (float)ent_coef;
   a.kl_coef = (float)kl_coef;
+  // the fused policy head writes no e5m2 dZ (that is head_backward's dz8): an fp8 trunk backward
+  // quantises the bf16 dz with quantize_bf8
+  TORCH_CHECK(a.dz8 == nullptr && a.dz8_scale == nullptr && a.dz8_amax == nullptr,
+              "policy_head: writes the bf16 dz only (no e5m2 dz8 output)");
   if (B == 0) return;
   agk::launch_policy_head(a, train, cur_stream());
   launch_check("policy_head");

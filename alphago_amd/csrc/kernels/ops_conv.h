@@ -211,7 +211,8 @@ inline void conv_wgrad_fp8_impl(const Tensor& x8, const Tensor& dz8, const Tenso
   TORCH_CHECK(x8.numel() < (1ll << 31) && dz8.numel() < (1ll << 31), "tensor too large for int32 offsets");
   const int64_t B = x8.size(0), HPi = x8.size(1), Cin = x8.size(3);
   const int64_t HPo = dz8.size(1), Cout = dz8.size(3);
-  TORCH_CHECK(agk::wgrad_fp8_supported((int)Cout, (int)Cin, (int)K), "conv_wgrad_fp8: 160 -> 160 3x3 layers only");
+  TORCH_CHECK(agk::wgrad_fp8_supported((int)Cout, (int)Cin, (int)K),
+              "conv_wgrad_fp8: 160 -> 160 and 192 -> 192 3x3 layers only (got ", Cin, " -> ", Cout, ", K ", K, ")");
   TORCH_CHECK(HPi == S + 2 * Pin && HPo == S + 2 * Po && Po >= 1 && Pin >= K / 2, "geometry mismatch");
   const int64_t nsplit = slab.size(0);
   TORCH_CHECK(slab.dim() == 4 && slab.size(1) == K * K && slab.size(2) == Cout && slab.size(3) == Cin, "bad slab");
@@ -321,9 +322,10 @@ inline void conv_fwd_fp8_impl(const Tensor& x, const Tensor& w, const Tensor& bi
   launch_check("conv_fwd_fp8");
 }
 
-// fp8 dgrad of the fp8-wgrad value step: dz8 e5m2 (B, HP, HP, 160) (MFMA scale scales[0]), w8t the
-// transposed flipped e4m3 weights (scales[1]), ReLU' from the forward's bitmask; outputs y_fp8 (e5m2 of
-// dx * out_scale[0]) and/or y_bf16; amax (optional) accumulates max |dx|
+// fp8 dgrad of the all-fp8 backward (160-wide value and 192-wide policy trunks): dz8 e5m2
+// (B, HP, HP, C), C = 160 or 192 (MFMA scale scales[0]), w8t the transposed flipped e4m3 weights
+// (scales[1]), ReLU' from the forward's bitmask; outputs y_fp8 (e5m2 of dx * out_scale[0]) and/or
+// y_bf16; amax (optional) accumulates max |dx|
 inline void conv_dgrad_fp8_bits_impl(const Tensor& dz8, const Tensor& w8t, const Tensor& mbits, const Tensor& scales,
                                      const Tensor& out_scale, const c10::optional<Tensor>& amax,
                                      const c10::optional<Tensor>& y_bf16, const c10::optional<Tensor>& y_fp8,
@@ -331,15 +333,18 @@ inline void conv_dgrad_fp8_bits_impl(const Tensor& dz8, const Tensor& w8t, const
   check_dev("conv_dgrad_fp8_bits", dz8, w8t, mbits, scales, out_scale, amax, y_bf16, y_fp8);
   CHECK_DEV(dz8); CHECK_DEV(w8t); CHECK_DEV(mbits); CHECK_CONTIG(dz8); CHECK_CONTIG(w8t); CHECK_CONTIG(mbits);
   TORCH_CHECK(dz8.scalar_type() == at::kByte && w8t.scalar_type() == at::kByte, "fp8 tensors are stored as uint8");
-  TORCH_CHECK(dz8.dim() == 4 && w8t.dim() == 3 && dz8.size(3) == 160 && w8t.size(1) == 160,
-              "dz8 (B, HP, HP, 160), w8t (nch, 160, cw)");
-  const int cw = fp8_check_chunks(w8t, K, 160, "conv_dgrad_fp8_bits");
+  TORCH_CHECK(dz8.dim() == 4 && w8t.dim() == 3, "dz8 (B, HP, HP, C), w8t (nch, C, cw)");
+  const int64_t C = dz8.size(3);
+  TORCH_CHECK((C == 160 || C == 192) && w8t.size(1) == C,
+              "conv_dgrad_fp8_bits: 160- and 192-wide layers only (dz8 has ", C, " channels, w8t ", w8t.size(1),
+              " rows)");
+  const int cw = fp8_check_chunks(w8t, K, C, "conv_dgrad_fp8_bits");
   TORCH_CHECK(scales.scalar_type() == at::kInt && scales.numel() >= 2 && out_scale.scalar_type() == at::kFloat &&
                   out_scale.numel() >= 1, "scales int32[2], out_scale f32[1]");
   TORCH_CHECK(mbits.scalar_type() == at::kInt, "mbits int32");
   TORCH_CHECK(y_bf16.has_value() || y_fp8.has_value(), "need an output");
   const int64_t B = dz8.size(0), HP = dz8.size(1), nch = w8t.size(0);
-  TORCH_CHECK(HP == S + 2 && dz8.size(2) == HP, "geometry (pad 1, 160 channels)");
+  TORCH_CHECK(HP == S + 2 && dz8.size(2) == HP, "geometry (pad 1)");
   TORCH_CHECK(mbits.numel() >= B * HP * HP * 8, "mbits too small: need B*HP*HP*8 words");
   agk::ConvFp8Args a{};
   a.x = dz8.data_ptr<uint8_t>(); a.w = w8t.data_ptr<uint8_t>();
@@ -358,11 +363,11 @@ inline void conv_dgrad_fp8_bits_impl(const Tensor& dz8, const Tensor& w8t, const
     TORCH_CHECK(amax->scalar_type() == at::kInt && amax->numel() >= agk::kFp8AmaxSlots, "amax int32[64]");
     a.amax = reinterpret_cast<unsigned*>(amax->data_ptr<int>());
   }
-  a.M = (int)(B * S * S); a.S = (int)S; a.Cin = 160; a.Cout = 160; a.K = (int)K;
+  a.M = (int)(B * S * S); a.S = (int)S; a.Cin = (int)C; a.Cout = (int)C; a.K = (int)K;
   a.HPi = (int)HP; a.offi = (int)(1 - K / 2); a.HPo = (int)HP; a.Po = 1; a.nch = (int)nch; a.cw = cw;
   a.dgrad = 1;
   a.mbits_in = reinterpret_cast<const uint32_t*>(mbits.data_ptr<int>());
-  TORCH_CHECK(B * HP * HP * 160 < (1ll << 31), "tensor too large for int32 offsets");
+  TORCH_CHECK(B * HP * HP * C < (1ll << 31), "tensor too large for int32 offsets");
   if (a.M == 0) return;
   agk::launch_conv_fwd_fp8(a, cur_stream());
   launch_check("conv_dgrad_fp8_bits");

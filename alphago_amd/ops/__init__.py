@@ -591,23 +591,31 @@ def conv_dgrad_bits_bf8(dz, wd, dx, mbits, dx8, scale, K: int, S: int, amax=None
 
 
 def conv_wgrad_fp8(x8, dz8, slab, dbslab, xscale, gscale, gmul, K: int, S: int, Pin: int, Po: int = 1, amax=None):
-    """fp8 weight gradient of a 160 -> 160 3x3 layer (conv_wgrad_fp8.hip): e4m3 x8 (E8M0 exponent
-    xscale[0]) x e5m2 dz8 (gscale[0]; gmul[0] = its 2^e multiplier, undone in the bias sums) into the
-    same split slab as conv_wgrad; reduce with conv_wgrad_reduce.  ``amax`` (int32[64]): max |dZ|
-    from the e5m2 bytes (the next step's delayed scale)."""
+    """fp8 weight gradient of a 160 -> 160 (value trunk) or 192 -> 192 (policy trunk) 3x3 layer
+    (conv_wgrad_fp8.hip): e4m3 x8 (E8M0 exponent xscale[0]) x e5m2 dz8 (gscale[0]; gmul[0] = its 2^e
+    multiplier, undone in the bias sums) into the same split slab as conv_wgrad, (nsplit, 9, C, C) with
+    nsplit from ``wgrad_fp8_nsplit(M, width=C)``; reduce with conv_wgrad_reduce.  ``amax`` (int32[64]):
+    max |dZ| from the e5m2 bytes (the next step's delayed scale).  Other shapes raise."""
     _ops().conv_wgrad_fp8(x8, dz8, slab, dbslab, xscale, gscale, gmul, K, S, Pin, Po, amax)
 
 
 def wgrad_fp8_supported(cout_p: int, cin_p: int, K: int) -> bool:
-    """Shapes the fp8 wgrad kernel covers (the value net's 160 -> 160 3x3 layers)."""
-    return cout_p == 160 and cin_p == 160 and K == 3
+    """Shapes the fp8 wgrad kernel covers: square 3x3 layers at the padded widths 160 (value trunk)
+    and 192 (policy trunk); the same rule as the C++ ``wgrad_fp8_supported``."""
+    return cout_p in (160, 192) and cin_p == cout_p and K == 3
 
 
-def wgrad_fp8_nsplit(M: int, K: int = 3, target_wgs: int = 512) -> int:
-    """Pixel splits of the fp8 wgrad (128-pixel steps, one 160 x 160 tile per tap and split,
-    two workgroups per CU): one resident round."""
+def wgrad_fp8_tiles(width: int = 160) -> int:
+    """Workgroups per (split, tap) of the fp8 wgrad: one 160 x 160 tile, or two 192 (n) x 96 (c) tiles."""
+    return 2 if width == 192 else 1
+
+
+def wgrad_fp8_nsplit(M: int, K: int = 3, target_wgs: int = 512, width: int = 160) -> int:
+    """Pixel splits of the fp8 wgrad (128-pixel steps; per tap and split one 160 x 160 tile, or at
+    ``width`` 192 two 192 x 96 tiles; two workgroups per CU either way): the grid
+    nsplit x K*K x tiles stays within one resident round of ``target_wgs`` workgroups."""
     nks = (M + 127) // 128
-    return max(1, min(target_wgs // (K * K), nks))
+    return max(1, min(target_wgs // (K * K * wgrad_fp8_tiles(width)), nks))
 
 
 def wino_pack_weights(w_oihw: torch.Tensor) -> torch.Tensor:
@@ -635,10 +643,10 @@ def conv_dgrad_fp8(dz8, w8t, mask, scales, out_scale, K: int, S: int, y_bf16, y_
 
 
 def conv_dgrad_fp8_bits(dz8, w8t, mbits, scales, out_scale, K: int, S: int, y_bf16=None, y_fp8=None, amax=None):
-    """fp8 dgrad of the fp8-wgrad value step (160 channels): dz8 e5m2 (the copy the previous dgrad
-    wrote for the fp8 wgrad; MFMA scale scales[0]) x the transposed flipped e4m3 weights (scales[1]),
-    ReLU' from the forward's bitmask ``mbits``; writes y_fp8 = e5m2(dx * out_scale[0]) and/or bf16
-    y_bf16; ``amax`` accumulates max |dx|."""
+    """fp8 dgrad of the all-fp8 backward (160 channels: value trunk; 192: policy trunk): dz8 e5m2 (the
+    copy the previous dgrad wrote for the fp8 wgrad; MFMA scale scales[0]) x the transposed flipped
+    e4m3 weights (scales[1]), ReLU' from the forward's bitmask ``mbits``; writes y_fp8 =
+    e5m2(dx * out_scale[0]) and/or bf16 y_bf16; ``amax`` accumulates max |dx|.  Other widths raise."""
     _ops().conv_dgrad_fp8_bits(dz8, w8t, mbits, scales, out_scale, amax, y_bf16, y_fp8, K, S)
 
 

@@ -437,14 +437,16 @@ class HipConvTrainer:
         self.gosc8 = torch.ones(L, device=dev)
         self.gamax8 = ops.fp8_amax_buffer(L, dev)
         self._g8_calibrated = False
-        # fp8 wgrad (160 -> 160 3x3 layers, conv_wgrad_fp8.hip): e4m3 inputs kept per layer (the
-        # forward's e4m3 outputs instead of a two-buffer ring), e5m2 output gradients written by
-        # the bitmask dgrad's epilogue (the head's by one quantise pass), delayed gradient scales
-        # as the fp8 dgrad's.  Layer 0 (49 planes) keeps the bf16 wgrad.  On by default where it
-        # applies (value net: 143 vs 201 us per layer at B = 1024, profiles/r3_fp8_wgrad.md);
-        # ALPHAGO_AMD_FP8_WGRAD=0 keeps the bf16 wgrad.
+        # fp8 wgrad (160 -> 160 and 192 -> 192 3x3 layers, conv_wgrad_fp8.hip): e4m3 inputs kept per
+        # layer (the forward's e4m3 outputs instead of a two-buffer ring), e5m2 output gradients
+        # written by the bitmask dgrad's epilogue (the head's by one quantise pass), delayed gradient
+        # scales as the fp8 dgrad's.  Layer 0 (48 / 49 planes) keeps the bf16 wgrad.  On by default
+        # on the 160-wide value trunk (143 vs 201 us per layer at B = 1024, profiles/r3_fp8_wgrad.md);
+        # ALPHAGO_AMD_FP8_WGRAD=0 keeps the bf16 wgrad there.  At 192 (policy trunk) it is opt-in:
+        # only an explicit fp8_wgrad=True turns it on, whatever the environment says, so the
+        # default fp8 policy step keeps its bf16 backward (profiles/r9/README.md).
         if fp8_wgrad is None:
-            fp8_wgrad = os.environ.get("ALPHAGO_AMD_FP8_WGRAD", "1") == "1"
+            fp8_wgrad = self.Fp == 160 and os.environ.get("ALPHAGO_AMD_FP8_WGRAD", "1") == "1"
         self.fp8_wgrad = bool(fp8_wgrad) and all(
             ops.wgrad_fp8_supported(self.Fp, self.Fp, self.K[l]) for l in range(1, L))
         # per-layer precision: the layers in fp8_bf16_layers run their forward, dgrad and wgrad in bf16
@@ -453,14 +455,15 @@ class HipConvTrainer:
         # With the fp8 wgrad the dgrad reads the same e5m2 dZ copy and writes e5m2 for the layer
         # below (conv_dgrad_fp8_bits): the all-fp8 backward is the default there (value 12 x 152,
         # B = 1024: 156.3k -> 179.9k positions/s, profiles/r3_fp8_wgrad.md);
-        # ALPHAGO_AMD_FP8_DGRAD=0 keeps the bf16 dgrad.  Elsewhere fp8 dgrad stays opt-in.
+        # ALPHAGO_AMD_FP8_DGRAD=0 keeps the bf16 dgrad.  Elsewhere (the 192-wide policy trunk
+        # included) fp8 dgrad stays opt-in: fp8_dgrad=True next to fp8_wgrad=True is the all-fp8 backward.
         if fp8_dgrad is None:
-            fp8_dgrad = self.fp8_wgrad and os.environ.get("ALPHAGO_AMD_FP8_DGRAD", "1") == "1"
+            fp8_dgrad = self.fp8_wgrad and self.Fp == 160 and os.environ.get("ALPHAGO_AMD_FP8_DGRAD", "1") == "1"
         self.fp8_dgrad = bool(fp8_dgrad)
         if self.fp8_wgrad:
             self.X8 = [None] + [torch.zeros(self.Y[0].shape, dtype=torch.uint8, device=dev) for _ in range(1, L)]
             self.DZ8 = [None] + [torch.zeros(self.DZ[0].shape, dtype=torch.uint8, device=dev) for _ in range(1, L)]
-            self.nsplit8 = ops.wgrad_fp8_nsplit(self._M, 3)
+            self.nsplit8 = ops.wgrad_fp8_nsplit(self._M, 3, width=self.Fp)
             need = self.nsplit8 * 9 * self.Fp * self.Fp
             if need > self._slabs[0].numel():
                 self._slabs = [torch.empty(need, device=dev) for _ in self._slabs]

@@ -79,8 +79,18 @@ class MetadataWriter(object):
         os.replace(tmp, self.file)
 
 
+class _SLParser(argparse.ArgumentParser):
+    """train-sl's parser: flag combinations that cannot run are parse errors."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        if getattr(ns, "fp8_backward", False) and ns.precision != "fp8":
+            self.error("--fp8-backward requires --precision fp8")
+        return ns, rest
+
+
 def _parser():
-    p = argparse.ArgumentParser(description="Perform supervised training on a policy network.")
+    p = _SLParser(description="Perform supervised training on a policy network.")
     p.add_argument("model", help="Path to a JSON model file (i.e. from CNNPolicy.save_model())")
     p.add_argument("train_data", help="A .h5 file of training data")
     p.add_argument("out_directory", help="directory where metadata and weights will be saved")
@@ -95,7 +105,11 @@ def _parser():
     p.add_argument("--train-val-test", nargs=3, type=float, default=[0.93, .05, .02])
     p.add_argument("--backend", default="auto", choices=["auto", "hip", "torch"])
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp8"],
-                   help="HIP backend conv forward precision (fp8: e4m3 block-scaled MFMA forward, bf16 backward)")
+                   help="HIP backend conv forward precision (fp8: e4m3 block-scaled MFMA forward, bf16 backward "
+                        "unless --fp8-backward)")
+    p.add_argument("--fp8-backward", action="store_true",
+                   help="with --precision fp8: all-fp8 trunk backward (e5m2 x e4m3 wgrad and dgrad on the 3x3 "
+                        "layers above the first; 160- and 192-wide trunks)")
     p.add_argument("--fp8-scale-guard", type=int, default=0,
                    help="fp8: activation scale exponents fall at most this many binades per step (0: unguarded, "
                         "the default; a 1-binade guard collapsed more SL runs, profiles/r6/README.md)")
@@ -194,6 +208,8 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
 
     B = args.minibatch
     pkw = {"precision": args.precision, "fp8_scale_guard": args.fp8_scale_guard} if args.precision != "bf16" else {}
+    if args.fp8_backward:
+        pkw.update(fp8_wgrad=True, fp8_dgrad=True)
     trainer = make_policy_trainer(net, B, args.learning_rate, args.decay, backend=args.backend, device=dev,
                                   iterations=iterations, **pkw)
     if args.graph and hasattr(trainer, "enable_graphs"):
