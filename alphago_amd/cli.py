@@ -26,7 +26,21 @@ import sys
 from typing import List, Optional
 
 
-def make_player(spec: str, device=None):
+SYMMETRY_CHOICES = ("none", "random", "all")
+
+
+def default_symmetries() -> str:
+    """ALPHAGO_AMD_SYMMETRIES, the default of every --symmetries flag ("none" when unset)."""
+    return os.environ.get("ALPHAGO_AMD_SYMMETRIES", "none")
+
+
+def add_symmetries_arg(p: argparse.ArgumentParser) -> None:
+    p.add_argument("--symmetries", choices=SYMMETRY_CHOICES, default=default_symmetries(),
+                   help="evaluate every position under one random board symmetry, or average all 8 "
+                        "(default: $ALPHAGO_AMD_SYMMETRIES or none)")
+
+
+def make_player(spec: str, device=None, symmetries: str = "none"):
     from .gtp.client import GTPClientPlayer
     from .models.policy import CNNPolicy, CNNValue
     from .search.arena import RandomPlayer
@@ -39,7 +53,7 @@ def make_player(spec: str, device=None):
         return GTPClientPlayer(rest)
     if kind == "policy":
         path, _, opt = rest.partition(":")
-        pol = CNNPolicy.load_model(path, device=device)
+        pol = CNNPolicy.load_model(path, device=device, symmetries=symmetries)
         if opt == "greedy":
             return GreedyPolicyPlayer(pol)
         return ProbabilisticPolicyPlayer(pol, temperature=float(opt) if opt else 1.0)
@@ -48,8 +62,8 @@ def make_player(spec: str, device=None):
         if not nets:
             nets, n = n, "1600"
         paths = nets.split(",")
-        pol = CNNPolicy.load_model(paths[0], device=device)
-        val = CNNValue.load_model(paths[1], device=device) if len(paths) > 1 else None
+        pol = CNNPolicy.load_model(paths[0], device=device, symmetries=symmetries)
+        val = CNNValue.load_model(paths[1], device=device, symmetries=symmetries) if len(paths) > 1 else None
         return MCTSPlayer(pol, val, n_playout=int(n))
     raise ValueError("unknown player spec %r" % spec)
 
@@ -81,17 +95,22 @@ def _init_model(argv):
     print(a.json_out)
 
 
-def _gtp(argv):
+def gtp_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="alphago_amd gtp")
     p.add_argument("--player", default="random")
     p.add_argument("--size", type=int, default=19)
-    a = p.parse_args(argv)
+    add_symmetries_arg(p)
+    return p
+
+
+def _gtp(argv):
+    a = gtp_parser().parse_args(argv)
     from .gtp.engine import run_gtp
 
-    run_gtp(make_player(a.player), size=a.size)
+    run_gtp(make_player(a.player, symmetries=a.symmetries), size=a.size)
 
 
-def _match(argv):
+def match_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="alphago_amd match")
     p.add_argument("player1")
     p.add_argument("player2")
@@ -99,10 +118,16 @@ def _match(argv):
     p.add_argument("--size", type=int, default=19)
     p.add_argument("--komi", type=float, default=7.5)
     p.add_argument("--sgf-dir", default=None)
-    a = p.parse_args(argv)
+    add_symmetries_arg(p)
+    return p
+
+
+def _match(argv):
+    a = match_parser().parse_args(argv)
     from .search.arena import play_match
 
-    res = play_match(make_player(a.player1), make_player(a.player2), a.games, a.size, a.komi, sgf_dir=a.sgf_dir)
+    res = play_match(make_player(a.player1, symmetries=a.symmetries), make_player(a.player2, symmetries=a.symmetries),
+                     a.games, a.size, a.komi, sgf_dir=a.sgf_dir)
     print(json.dumps(res))
     return res
 

@@ -286,6 +286,35 @@ void launch_sample_moves(const SampleArgs& a, hipStream_t st);
 void launch_head_grad_sums(const float* dhead, int B, int N, const float* loss, const float* correct, float* grad,
                            float* sums, hipStream_t st);
 void launch_pack_input(const PackInputArgs& a, hipStream_t st);
+
+// D4 symmetry ensembling at inference (symmetry.hip).  A trunk batch of G * B boards holds board b of
+// the submission under symmetry sym[g * B + b] at index g * B + b.
+struct D4ExpandArgs {
+  const __bf16* src;  // padded NHWC [B][S+2P][S+2P][Cp]
+  __bf16* dst;        // [GB][S+2P][S+2P][Cp]: board k = board k % B of src under sym[k] (interior only)
+  const int* sym;     // [GB] in 0..7
+  int B, GB, S, P, Cp;
+};
+struct PolicyHeadD4Args {
+  const __bf16* y;       // trunk output of the G * B boards, padded NHWC (P = 1, C)
+  const float* w;        // [C_real]
+  const float* b;        // [1]
+  const uint8_t* legal;  // [B][S*S] in the original frame, or null
+  const int* sym;        // [G * B]
+  float* probs;          // [B][S*S] original frame: the mean over g of the G distributions mapped back
+  float* scratch;        // [G * B][S*S] or null: lets small batches run one workgroup per orientation
+  int B, G, S, C, C_real;
+  float inv_temp;
+  float inv_g;           // (float)(1.0 / G), filled by the launcher
+  int LB;                // period of legal's rows over the kernel's boards (launcher)
+};
+// positions below which policy_head_d4 (G > 1, scratch given) runs one workgroup per orientation and a
+// group_mean pass instead of one workgroup per position walking its G orientations
+constexpr int kD4SplitBelow = 128;
+void launch_d4_expand(const D4ExpandArgs& a, hipStream_t st);
+void launch_policy_head_d4(const PolicyHeadD4Args& a, hipStream_t st);
+// out[b] = (v[b] + v[B + b] + ... + v[(G - 1) B + b]) * (1 / G), fp32 in g order
+void launch_group_mean(const float* v, float* out, int B, int G, hipStream_t st);
 void launch_pack_weights(const PackWeightsArgs& a, hipStream_t st);
 void launch_featurize(const FeaturizeArgs& a, hipStream_t st);
 void launch_conv_fwd_fp8(const ConvFp8Args& a, hipStream_t st);

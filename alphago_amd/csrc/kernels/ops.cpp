@@ -367,6 +367,78 @@ void pack_input(const Tensor& planes, const c10::optional<Tensor>& sym, const c1
   launch_check("pack_input");
 }
 
+// dst (G*B, S+2P, S+2P, Cp) bf16: board k = board k % B of src (B, S+2P, S+2P, Cp) under symmetry sym[k]
+// (pack_input's convention), interior only
+void d4_expand(const Tensor& src, const Tensor& dst, const Tensor& sym, int64_t S, int64_t P) {
+  check_dev("d4_expand", src, dst, sym);
+  CHECK_BF16(src); CHECK_CONTIG(src); CHECK_BF16(dst); CHECK_CONTIG(dst); CHECK_CONTIG(sym);
+  TORCH_CHECK(src.dim() == 4 && dst.dim() == 4, "d4_expand: src (B, HP, HP, Cp), dst (G*B, HP, HP, Cp)");
+  const int64_t B = src.size(0), GB = dst.size(0), HP = src.size(1), Cp = src.size(3);
+  TORCH_CHECK(S >= 1 && P >= 0 && HP == S + 2 * P && src.size(2) == HP, "d4_expand: square boards of S + 2 P");
+  TORCH_CHECK(dst.size(1) == HP && dst.size(2) == HP && dst.size(3) == Cp, "d4_expand: dst boards must match src's");
+  TORCH_CHECK(Cp % 8 == 0, "d4_expand: channels must be a multiple of 8 (16-byte chunks)");
+  TORCH_CHECK(GB == 0 || (B > 0 && GB % B == 0), "d4_expand: dst must hold a multiple of src's boards");
+  TORCH_CHECK(sym.scalar_type() == at::kInt && sym.numel() == GB, "d4_expand: sym int32 (G*B,)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(src.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(dst.data_ptr()) % 16 == 0,
+              "d4_expand: src and dst must be 16-byte aligned");
+  agk::D4ExpandArgs a{};
+  a.src = bfp(src); a.dst = bfp_mut(dst); a.sym = sym.data_ptr<int>();
+  a.B = (int)B; a.GB = (int)GB; a.S = (int)S; a.P = (int)P; a.Cp = (int)Cp;
+  if (GB == 0) return;
+  agk::launch_d4_expand(a, cur_stream());
+  launch_check("d4_expand");
+}
+
+// probs (B, S*S) f32 = mean over g of the legal-masked softmax of board g*B+b of y (G*B, S+2, S+2, C),
+// mapped back from symmetry sym[g*B+b] to the original frame; legal (B, S*S) in the original frame
+void policy_head_d4(const Tensor& y, const Tensor& w, const Tensor& b, const Tensor& probs, int64_t S,
+                    const Tensor& sym, int64_t G, const c10::optional<Tensor>& legal, double temperature,
+                    const c10::optional<Tensor>& scratch) {
+  check_dev("policy_head_d4", y, w, b, probs, sym, legal, scratch);
+  CHECK_BF16(y); CHECK_CONTIG(y); CHECK_F32(w); CHECK_CONTIG(w); CHECK_F32(b); CHECK_F32(probs); CHECK_CONTIG(probs);
+  CHECK_CONTIG(sym);
+  TORCH_CHECK(y.dim() == 4 && probs.dim() == 2, "policy_head_d4: y (G*B, S+2, S+2, C), probs (B, S*S)");
+  const int64_t B = probs.size(0), C = y.size(3);
+  TORCH_CHECK(G >= 1 && G <= 64 && y.size(0) == G * B, "policy_head_d4: y must hold G * B boards (1 <= G <= 64)");
+  TORCH_CHECK(S >= 1 && y.size(1) == S + 2 && y.size(2) == S + 2, "head input must have pad 1");
+  TORCH_CHECK(C % 8 == 0 && C <= 256, "head channels must be a multiple of 8 and <= 256");
+  TORCH_CHECK(w.numel() <= C, "head weight must have at most as many entries as the head has channels");
+  TORCH_CHECK(b.numel() >= 1, "head bias must have one entry");
+  TORCH_CHECK(S * S <= 361, "board too large (the head holds at most 19 x 19)");
+  TORCH_CHECK(probs.size(1) == S * S, "probs must be (B, S*S)");
+  TORCH_CHECK(sym.scalar_type() == at::kInt && sym.numel() == G * B, "sym: int32 (G*B,)");
+  TORCH_CHECK(temperature > 0.0, "temperature must be > 0");
+  agk::PolicyHeadD4Args a{};
+  a.y = bfp(y); a.w = w.data_ptr<float>(); a.b = b.data_ptr<float>(); a.probs = probs.data_ptr<float>();
+  a.sym = sym.data_ptr<int>();
+  a.B = (int)B; a.G = (int)G; a.S = (int)S; a.C = (int)C; a.C_real = (int)w.numel();
+  a.inv_temp = (float)(1.0 / temperature);
+  if (legal.has_value()) {
+    TORCH_CHECK(legal->scalar_type() == at::kByte && legal->numel() == B * S * S && legal->is_contiguous(),
+                "legal must be contiguous uint8 (B, S*S)");
+    a.legal = legal->data_ptr<uint8_t>();
+  }
+  if (scratch.has_value()) {  // (G*B, S*S) f32: few positions run one workgroup per orientation through it
+    CHECK_F32(*scratch); CHECK_CONTIG(*scratch);
+    TORCH_CHECK(scratch->numel() >= G * B * S * S, "scratch must hold (G*B, S*S) floats");
+    a.scratch = scratch->data_ptr<float>();
+  }
+  if (B == 0) return;
+  agk::launch_policy_head_d4(a, cur_stream());
+  launch_check("policy_head_d4");
+}
+
+// out (B,) f32 = (sum over g of v[g*B + b]) * (1 / G), in g order
+void group_mean(const Tensor& v, const Tensor& out, int64_t G) {
+  check_dev("group_mean", v, out);
+  CHECK_F32(v); CHECK_CONTIG(v); CHECK_F32(out); CHECK_CONTIG(out);
+  TORCH_CHECK(G >= 1 && v.numel() == G * out.numel(), "group_mean: v (G*B,), out (B,)");
+  TORCH_CHECK(v.numel() < (1ll << 31), "group_mean: v too large");
+  if (out.numel() == 0) return;
+  agk::launch_group_mean(v.data_ptr<float>(), out.data_ptr<float>(), (int)out.numel(), (int)G, cur_stream());
+  launch_check("group_mean");
+}
+
 // ws: list of OIHW fp32; wf: list of (T, Coutp, Cinp) bf16; wd: list (possibly empty entries skipped)
 void pack_weights(at::TensorList ws, at::TensorList wf, at::TensorList wd) {
   check_dev("pack_weights", ws, wf, wd);
@@ -890,6 +962,10 @@ TORCH_LIBRARY(alphago_amd, m) {
       "Tensor(c!)? correct, Tensor(d!)? dh, Tensor(e!)? dout, float grad_scale) -> ()");
   m.def("pack_input(Tensor planes, Tensor? sym, Tensor? target, Tensor(a!)? target_out, Tensor(b!) out, int P, "
         "Tensor? rows=None, Tensor(c!)? out8=None) -> ()");
+  m.def("d4_expand(Tensor src, Tensor(a!) dst, Tensor sym, int S, int P) -> ()");
+  m.def("policy_head_d4(Tensor y, Tensor w, Tensor b, Tensor(a!) probs, int S, Tensor sym, int G, Tensor? legal=None, "
+        "float temperature=1.0, Tensor(b!)? scratch=None) -> ()");
+  m.def("group_mean(Tensor v, Tensor(a!) out, int G) -> ()");
   m.def("pack_weights(Tensor[] ws, Tensor(a!)[] wf, Tensor(b!)[] wd) -> ()");
   m.def("sgd_update(Tensor(a!) p, Tensor g, float lr, float gscale) -> ()");
   m.def("comm_proxy(Tensor src, Tensor(a!) dst, int channels, float wire_us) -> ()");
@@ -950,6 +1026,9 @@ TORCH_LIBRARY_IMPL(alphago_amd, CUDA, m) {
   m.impl("conv_wgrad_fp8", &conv_wgrad_fp8);
   m.impl("policy_head", &policy_head);
   m.impl("pack_input", &pack_input);
+  m.impl("d4_expand", &d4_expand);
+  m.impl("policy_head_d4", &policy_head_d4);
+  m.impl("group_mean", &group_mean);
   m.impl("head_logits", &head_logits);
   m.impl("head_backward", &head_backward);
   m.impl("value_out", &value_out);

@@ -12,6 +12,18 @@ instead of uint8 planes: the GPU featurizer (ops/gpu_features.py) runs as the
 first node of the same graph, writing the conv input and the sensible-move
 mask directly (24x less H2D traffic than 48 uint8 planes, no CPU featurizing).
 
+Symmetry ensembling (``symmetries="random"`` / ``"all"``): a position is evaluated under G of the 8
+board symmetries (G = 1 drawn per board per submission, or all 8) and the outputs are mapped back to
+the board's own frame and averaged.  Symmetry s is ``pack_input``'s (``train/engine.symmetry_tables``):
+policy = 1/G sum_g P_s[fwd_s(p)], value = 1/G sum_g V(board under s).  A bucket of B positions then
+owns a trunk batch of G*B boards, board g*B + b being position b under symmetry sym[g*B + b]; the conv
+input is fanned out on the device (``pack_input`` with rows / sym, or ``d4_expand`` after the
+featurizer, which still runs once per position), the head folds the G outputs back inside one kernel
+(``policy_head_probs_d4`` / ``group_mean``), all in the same captured graph.  Masks, planes and the
+overflow list stay in the original frame.  Memory: an ``"all"`` bucket holds 8x the activations of a
+plain one -- a 1024-position bucket is an 8192-board trunk, about 2.8 GB per slot at 19x19x192 --
+so buckets stay lazy.  ``"none"`` (the default) is the plain single-orientation path, unchanged.
+
 Reference paths replaced: CNNPolicy.forward / batch_eval_state
 (policy.py:26-79) which featurised in Python and ran a Theano function per
 call; MCTS policy/value callables (mcts.py:107-118).
@@ -29,6 +41,14 @@ from .nets import PolicyNet, ValueNet
 
 DEFAULT_BUCKETS = (1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024)
 
+SYMMETRY_MODES = ("none", "random", "all")
+
+
+def _check_symmetries(mode: str) -> str:
+    if mode not in SYMMETRY_MODES:
+        raise ValueError("symmetries must be one of %s, not %r" % (", ".join(SYMMETRY_MODES), mode))
+    return mode
+
 
 class _Bucket:
     pass
@@ -38,7 +58,13 @@ class HipTrunkInference:
     """Forward-only runner of a ConvStack (+ head) on the HIP kernels."""
 
     def __init__(self, net, device, buckets: Sequence[int] = DEFAULT_BUCKETS, use_graphs: bool = True,
-                 feature_list: Optional[Sequence[str]] = None, precision: Optional[str] = None):
+                 feature_list: Optional[Sequence[str]] = None, precision: Optional[str] = None,
+                 symmetries: str = "none", symmetry_seed: int = 0):
+        self.symmetries = _check_symmetries(symmetries)
+        self.G = 8 if symmetries == "all" else 1  # orientations per position
+        self._sym = symmetries != "none"
+        self._rng = np.random.default_rng(symmetry_seed)
+        self._last_sub = None  # (bucket, n) of the last submission
         ops.load()
         self.net = net
         self.precision = precision or os.environ.get("ALPHAGO_AMD_PRECISION", "bf16")
@@ -134,15 +160,24 @@ class HipTrunkInference:
         dev, S = self.device, self.S
         bk = _Bucket()
         bk.B = B
+        Bt = bk.Bt = B * self.G  # trunk batch: every position under its G symmetries
         bk.planes = torch.zeros((B, self.C0, S, S), dtype=torch.uint8, device=dev)
         bk.legal = torch.ones((B, S * S), dtype=torch.uint8, device=dev)
-        bk.X0 = ops.padded_empty(B, S, self.P0, self.C0p, dev)
-        bk.Y = [ops.padded_empty(B, S, 1, self.Fp, dev) for _ in range(2)]
+        bk.X0 = ops.padded_empty(Bt, S, self.P0, self.C0p, dev)
+        bk.Y = [ops.padded_empty(Bt, S, 1, self.Fp, dev) for _ in range(2)]
+        if self._sym:
+            # trunk board g * B + b is position b under sym[g * B + b]; "random" refills sym per submission
+            bk.sym = torch.arange(self.G, dtype=torch.int32, device=dev).repeat_interleave(B) if self.G > 1 \
+                else torch.zeros(Bt, dtype=torch.int32, device=dev)
+            bk.rows = torch.arange(Bt, dtype=torch.int64, device=dev) % B
+            bk.last_sym = np.zeros(B, dtype=np.int32)
+            if self.fz is not None:  # the featurizer's single-orientation output, fanned out by d4_expand
+                bk.X0f = ops.padded_empty(B, S, self.P0, self.C0p, dev)
         # small buckets (ops.plan_conv): the weight-stationary kernel (tile 40) where it applies, else the
         # split-K 32-pixel conv (ops.conv_fwd_splitk), fp32 partials in bk.ws; not the buckets an fp8
         # engine runs in fp8 (their bf16 calibration forward runs the plain tiles)
-        M = B * S * S
-        small = self.precision != "fp8" or B < self.fp8_min_batch
+        M = Bt * S * S
+        small = self.precision != "fp8" or Bt < self.fp8_min_batch
         bk.plan = [ops.plan_conv(M, self.Fp, c, K, small=small) for c, K in zip(self.cin_p, self.K)]
         n = ops.splitk_workspace_numel(bk.plan, M, self.Fp)
         bk.ws = torch.empty(n, device=dev) if n else None
@@ -163,6 +198,8 @@ class HipTrunkInference:
 
     def _alloc_outputs(self, bk):
         bk.probs = torch.zeros((bk.B, self.S * self.S), device=self.device)
+        # "all": per-orientation rows for the head's small-batch path (ops.policy_head_probs_d4)
+        bk.probs_g = torch.zeros((bk.Bt, self.S * self.S), device=self.device) if self.G > 1 else None
 
     def set_encoded_planes(self, on: bool) -> None:
         """Make the encoded path also write uint8 planes (``encoded_planes_view``); re-captures graphs."""
@@ -181,11 +218,15 @@ class HipTrunkInference:
     def _trunk(self, bk, encoded: bool = False) -> torch.Tensor:
         if encoded:
             bk.ovf.zero_()
-            self.fz.run(bk.e_board, bk.e_ages, bk.e_meta, bk.e_ladder, nhwc=bk.X0, P=self.P0, sensible=bk.legal,
-                        overflow=bk.ovf, planes=bk.planes if self.encoded_planes else None)
+            self.fz.run(bk.e_board, bk.e_ages, bk.e_meta, bk.e_ladder, nhwc=bk.X0f if self._sym else bk.X0, P=self.P0,
+                        sensible=bk.legal, overflow=bk.ovf, planes=bk.planes if self.encoded_planes else None)
+            if self._sym:
+                ops.d4_expand(bk.X0f, bk.X0, bk.sym, self.S, self.P0)
+        elif self._sym:
+            ops.pack_input(bk.planes, bk.X0, self.P0, sym=bk.sym, rows=bk.rows)
         else:
             ops.pack_input(bk.planes, bk.X0, self.P0)
-        if self.precision == "fp8" and not getattr(self, "_calibrating", False) and bk.B >= self.fp8_min_batch:
+        if self.precision == "fp8" and not getattr(self, "_calibrating", False) and bk.Bt >= self.fp8_min_batch:
             return self._trunk_fp8(bk)
         x, pin = bk.X0, self.P0
         for l in range(self.L):
@@ -236,7 +277,35 @@ class HipTrunkInference:
             self.osc8[l] = 2.0 ** self.ex[l + 1]
 
     def _head(self, bk, y):
-        ops.policy_head_probs(y, self.head_w, self.head_b, bk.probs, self.S, legal=bk.legal)
+        if self._sym:
+            ops.policy_head_probs_d4(y, self.head_w, self.head_b, bk.probs, self.S, bk.sym, self.G, legal=bk.legal,
+                                     scratch=bk.probs_g)
+        else:
+            ops.policy_head_probs(y, self.head_w, self.head_b, bk.probs, self.S, legal=bk.legal)
+
+    def _draw_symmetries(self, bk, n: int) -> None:
+        """Per-submission part of the symmetry modes: "random" draws one symmetry per board on the host
+        and queues its copy with the other inputs (padding boards keep whatever they had)."""
+        self._last_sub = (bk, n)
+        if self.symmetries == "random":
+            bk.last_sym = self._rng.integers(0, 8, size=n, dtype=np.int32)
+            bk.sym[:n].copy_(torch.from_numpy(bk.last_sym), non_blocking=True)
+
+    def last_symmetries(self, handle=None) -> np.ndarray:
+        """Symmetries of the last submission (or of ``handle``'s bucket, valid until it is submitted
+        again): int32 (n,) -- zeros for "none", the draw for "random" -- or (8, n) for "all", row g
+        holding g."""
+        if handle is not None:
+            bk, n = handle[0], handle[1]
+        elif self._last_sub is not None:
+            bk, n = self._last_sub
+        else:
+            raise RuntimeError("nothing submitted yet")
+        if self.symmetries == "random":
+            return bk.last_sym[:n].copy()
+        if self.symmetries == "all":
+            return np.repeat(np.arange(8, dtype=np.int32)[:, None], n, 1)
+        return np.zeros(n, dtype=np.int32)
 
     def _run(self, bk, encoded: bool = False):
         self._head(bk, self._trunk(bk, encoded))
@@ -287,6 +356,7 @@ class HipTrunkInference:
         if n < bk.B:
             bk.e_board[n:].zero_()
             bk.e_ages[n:].fill_(255)
+        self._draw_symmetries(bk, n)
         if self.precision == "fp8" and not self.calibrated:
             self.calibrate(bk, encoded=True)
         if bk.graph_enc is not None:
@@ -353,6 +423,7 @@ class HipTrunkInference:
                 bk.legal[n:].fill_(1)
         else:
             bk.legal.fill_(1)
+        self._draw_symmetries(bk, n)
         if self.precision == "fp8" and not self.calibrated:
             self.calibrate(bk)
         if bk.graph is not None:
@@ -380,27 +451,113 @@ class HipValueInference(HipTrunkInference):
 
     def _alloc_outputs(self, bk):
         bk.values = torch.zeros((bk.B,), device=self.device)
-        bk.z = torch.zeros((bk.B, self.S * self.S), device=self.device)
-        bk.h = torch.zeros((bk.B, self.fc[0].shape[1]), device=self.device)
+        bk.z = torch.zeros((bk.Bt, self.S * self.S), device=self.device)
+        bk.h = torch.zeros((bk.Bt, self.fc[0].shape[1]), device=self.device)
+        if self.G > 1:  # the G values of every position, averaged by group_mean
+            bk.values_g = torch.zeros((bk.Bt,), device=self.device)
 
     def _head(self, bk, y):
         w1, b1, w2, b2 = self.fc
         ops.head_logits(y, self.head_w, self.head_b, bk.z, self.S)
         ops.dense_f32(bk.z, w1, bk.h, bias=b1)
-        ops.value_out(bk.h, w2.view(-1), b2, bk.values)
+        if self.G > 1:
+            ops.value_out(bk.h, w2.view(-1), b2, bk.values_g)
+            ops.group_mean(bk.values_g, bk.values, self.G)
+        else:  # "random": the value of the one drawn orientation is the output
+            ops.value_out(bk.h, w2.view(-1), b2, bk.values)
 
     def _outputs(self, bk, n):
         return bk.values[:n]
 
 
-class TorchPolicyInference:
+class _TorchSymmetries:
+    """The symmetry modes of the torch engines: the module docstring's definition in plain torch
+    (index tables from ``train/engine.symmetry_tables``)."""
+
+    def _init_symmetries(self, symmetries: str, symmetry_seed: int) -> None:
+        self.symmetries = _check_symmetries(symmetries)
+        self.G = 8 if symmetries == "all" else 1
+        self._rng = np.random.default_rng(symmetry_seed)
+        self._last_sym = None
+        self._table = None
+
+    def _draw(self, n: int) -> torch.Tensor:
+        """(G, n) long symmetries of this submission."""
+        if self.symmetries == "all":
+            sym = np.repeat(np.arange(8, dtype=np.int32)[:, None], n, 1)
+            self._last_sym = sym
+        elif self.symmetries == "random":
+            self._last_sym = self._rng.integers(0, 8, size=n, dtype=np.int32)
+            sym = self._last_sym[None]
+        else:
+            self._last_sym = np.zeros(n, dtype=np.int32)
+            sym = self._last_sym[None]
+        return torch.as_tensor(sym, device=self.device).long()
+
+    def _tables(self, sym_row: torch.Tensor):
+        """fwd, inv (n, S*S): transformed[fwd[p]] = original[p]; transformed = original.gather(inv)."""
+        if self._table is None:
+            from ..train.engine import symmetry_tables
+            self._table = symmetry_tables(self.net.board, self.device)
+        fwd = self._table[sym_row]
+        return fwd, torch.argsort(fwd, dim=1)
+
+    @staticmethod
+    def _transform(x: torch.Tensor, inv: torch.Tensor) -> torch.Tensor:
+        n, C, S, _ = x.shape
+        return torch.gather(x.reshape(n, C, S * S), 2, inv.unsqueeze(1).expand(n, C, S * S)).reshape(n, C, S, S)
+
+    def last_symmetries(self, handle=None) -> np.ndarray:
+        """As HipTrunkInference.last_symmetries."""
+        if self._last_sym is None:
+            raise RuntimeError("nothing submitted yet")
+        return self._last_sym.copy()
+
+
+class TorchPolicyInference(_TorchSymmetries):
     """CPU / reference path with the same interface."""
 
     supports_encoded = False
     needs_ladder = False
 
-    def __init__(self, net: PolicyNet, device="cpu"):
+    def __init__(self, net: PolicyNet, device="cpu", symmetries: str = "none", symmetry_seed: int = 0):
         self.net, self.device = net, torch.device(device)
+        self._init_symmetries(symmetries, symmetry_seed)
+
+    def sync_weights(self):
+        pass
+
+    def _plain(self, x, legal):
+        logits = self.net.logits_torch(x.float())
+        if legal is not None:
+            logits = logits.masked_fill(legal == 0, float("-inf"))
+        p = torch.softmax(logits, 1)
+        return torch.nan_to_num(p, nan=0.0)
+
+    @torch.no_grad()
+    def evaluate(self, planes, legal=None, slot: int = 0):
+        x = torch.as_tensor(planes).to(self.device)
+        if legal is not None:
+            legal = torch.as_tensor(legal).to(self.device)
+        sym = self._draw(x.shape[0])
+        if self.symmetries == "none":
+            return self._plain(x, legal)
+        acc = None
+        for g in range(self.G):  # fixed g order, fp32
+            fwd, inv = self._tables(sym[g])
+            p = self._plain(self._transform(x, inv), legal.gather(1, inv) if legal is not None else None)
+            p = p.gather(1, fwd)  # back to the original frame: P_s[fwd_s(p)]
+            acc = p if acc is None else acc + p
+        return acc * (1.0 / self.G)
+
+
+class TorchValueInference(_TorchSymmetries):
+    supports_encoded = False
+    needs_ladder = False
+
+    def __init__(self, net: ValueNet, device="cpu", symmetries: str = "none", symmetry_seed: int = 0):
+        self.net, self.device = net, torch.device(device)
+        self._init_symmetries(symmetries, symmetry_seed)
 
     def sync_weights(self):
         pass
@@ -408,38 +565,32 @@ class TorchPolicyInference:
     @torch.no_grad()
     def evaluate(self, planes, legal=None, slot: int = 0):
         x = torch.as_tensor(planes).to(self.device)
-        logits = self.net.logits_torch(x.float())
-        if legal is not None:
-            logits = logits.masked_fill(torch.as_tensor(legal).to(self.device) == 0, float("-inf"))
-        p = torch.softmax(logits, 1)
-        return torch.nan_to_num(p, nan=0.0)
+        sym = self._draw(x.shape[0])
+        if self.symmetries == "none":
+            return self.net.forward_torch(x.float())
+        acc = None
+        for g in range(self.G):
+            v = self.net.forward_torch(self._transform(x, self._tables(sym[g])[1]).float())
+            acc = v if acc is None else acc + v
+        return acc * (1.0 / self.G)
 
 
-class TorchValueInference:
-    supports_encoded = False
-    needs_ladder = False
-
-    def __init__(self, net: ValueNet, device="cpu"):
-        self.net, self.device = net, torch.device(device)
-
-    def sync_weights(self):
-        pass
-
-    @torch.no_grad()
-    def evaluate(self, planes, legal=None, slot: int = 0):
-        return self.net.forward_torch(torch.as_tensor(planes).to(self.device).float())
+def _torch_kw(kw):
+    """The engine keywords the torch engines take too (feature_list etc. are unused: CPU featurizer path)."""
+    return {k: v for k, v in kw.items() if k in ("symmetries", "symmetry_seed")}
 
 
 def make_policy_inference(net, device, **kw):
-    """HIP engine on a GPU (pass ``feature_list`` to enable evaluate_encoded), torch on CPU."""
+    """HIP engine on a GPU (pass ``feature_list`` to enable evaluate_encoded), torch on CPU;
+    ``symmetries`` ("none" / "random" / "all") and ``symmetry_seed`` apply to both."""
     device = torch.device(device)
     if device.type == "cuda":
         return HipTrunkInference(net, device, **kw)
-    return TorchPolicyInference(net, device)  # feature_list unused: CPU featurizer path
+    return TorchPolicyInference(net, device, **_torch_kw(kw))
 
 
 def make_value_inference(net, device, **kw):
     device = torch.device(device)
     if device.type == "cuda":
         return HipValueInference(net, device, **kw)
-    return TorchValueInference(net, device)  # feature_list unused: CPU featurizer path
+    return TorchValueInference(net, device, **_torch_kw(kw))

@@ -19,7 +19,7 @@ import torch
 from ..features import DEFAULT_FEATURES, VALUE_FEATURES, Preprocess
 from ..io import keras_compat
 from ..utils.gorecords import flatten_idx
-from .inference import make_policy_inference, make_value_inference
+from .inference import SYMMETRY_MODES, make_policy_inference, make_value_inference
 from .nets import PolicyNet, ValueNet
 
 
@@ -36,6 +36,7 @@ class _NetWrapper(object):
         self.device = torch.device(device) if device is not None else default_device()
         self.model = self.create_network(**kwargs).to(self.device)
         self._engine = None
+        self._symmetries, self._symmetry_seed = "none", 0
 
     @classmethod
     def create_network(cls, **kwargs):
@@ -43,9 +44,19 @@ class _NetWrapper(object):
 
     def _engine_kw(self):
         """GPU engines get the feature list so they can featurize on the device."""
+        kw = {"symmetries": self._symmetries, "symmetry_seed": self._symmetry_seed}
         if self.device.type == "cuda" and self.preprocessor.output_dim <= 64:
-            return {"feature_list": self.preprocessor.feature_list}
-        return {}
+            kw["feature_list"] = self.preprocessor.feature_list
+        return kw
+
+    def set_symmetries(self, mode: str, seed: int = 0) -> None:
+        """Evaluate under board symmetries from now on: "none", "random" (one drawn per board per
+        batch, generator seeded by ``seed``) or "all" (the mean over all 8); see models/inference.py.
+        The engine is rebuilt on its next use."""
+        if mode not in SYMMETRY_MODES:
+            raise ValueError("symmetries must be one of %s, not %r" % (", ".join(SYMMETRY_MODES), mode))
+        self._symmetries, self._symmetry_seed = mode, int(seed)
+        self._engine = None
 
     @property
     def engine(self):
@@ -69,7 +80,7 @@ class _NetWrapper(object):
             json.dump(specs, f)
 
     @classmethod
-    def load_model(cls, json_file: str, device=None, weights_file: Optional[str] = None):
+    def load_model(cls, json_file: str, device=None, weights_file: Optional[str] = None, symmetries: str = "none"):
         with open(json_file, "r") as f:
             specs = json.load(f)
         obj = cls.__new__(cls)
@@ -80,6 +91,7 @@ class _NetWrapper(object):
             raise ValueError("%s expects a %s spec" % (cls.__name__, cls._net_cls.__name__))
         obj.model = net.to(obj.device)
         obj._engine = None
+        obj.set_symmetries(symmetries)
         wf = weights_file or specs.get("weights_file")
         if wf:
             if not os.path.isabs(wf) and not os.path.exists(wf):

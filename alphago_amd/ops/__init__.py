@@ -357,6 +357,31 @@ def pack_input(planes_u8, out, P: int, sym=None, target=None, target_out=None, r
     return out
 
 
+def d4_expand(src, dst, sym, S: int, P: int):
+    """Padded NHWC ``src`` (B boards) -> ``dst`` (G*B boards): board ``k`` of ``dst`` is board ``k % B`` of
+    ``src`` under the D4 symmetry ``sym[k]`` (int32, pack_input's convention); interior only, a pure
+    16-byte-chunk gather.  One featurizer run feeds all G orientations of the ensembled engines."""
+    _ops().d4_expand(src, dst, sym, S, P)
+    return dst
+
+
+def policy_head_probs_d4(y, w, b, probs, S: int, sym, G: int, legal=None, temperature: float = 1.0, scratch=None):
+    """Symmetry-ensembled ``policy_head_probs``: ``y`` holds the trunk output of G*B boards, board
+    ``g*B + b`` being board b under symmetry ``sym[g*B + b]``.  ``probs`` (B, S*S) is the mean over g, in
+    g order, of the G legal-masked softmaxes mapped back to the original frame; ``legal`` (B, S*S) is in
+    the original frame.  Deterministic (no atomics).  ``scratch`` (G*B, S*S) fp32, optional: with it, fewer
+    than 128 positions run one workgroup per orientation into ``scratch`` and a ``group_mean`` pass (the
+    same fixed g order) instead of one workgroup per position walking its G orientations."""
+    _ops().policy_head_d4(y, w, b, probs, S, sym, G, legal, temperature, scratch)
+    return probs
+
+
+def group_mean(v, out, G: int):
+    """out[b] = (v[b] + v[B + b] + ... + v[(G-1) B + b]) * float32(1 / G), fp32 in that order."""
+    _ops().group_mean(v, out, G)
+    return out
+
+
 def pack_weights(ws, wf, wd=()):
     _ops().pack_weights(list(ws), list(wf), list(wd))
 

@@ -258,10 +258,10 @@ def make_server(service: GoService, host: str = "127.0.0.1", port: int = 8000) -
     return srv
 
 
-def serve_cli(argv: Sequence[str]) -> int:
+def serve_parser():
     import argparse
 
-    from ..models.policy import CNNPolicy, CNNValue
+    from ..cli import add_symmetries_arg
 
     p = argparse.ArgumentParser(prog="alphago_amd serve",
                                 description="HTTP/JSON position evaluation with dynamic batching")
@@ -278,14 +278,21 @@ def serve_cli(argv: Sequence[str]) -> int:
     p.add_argument("--devices", default=None,
                    help="comma-separated devices (e.g. cuda:0,cuda:1,...): one network copy and batcher per "
                         "device, requests to the least-loaded one")
-    a = p.parse_args(list(argv))
+    add_symmetries_arg(p)
+    return p
+
+
+def serve_cli(argv: Sequence[str]) -> int:
+    from ..models.policy import CNNPolicy, CNNValue
+
+    a = serve_parser().parse_args(list(argv))
     if a.precision:
         import os
 
         os.environ["ALPHAGO_AMD_PRECISION"] = a.precision  # read when each engine is built
     devs = a.devices.split(",") if a.devices else [a.device]
-    pol = [CNNPolicy.load_model(a.policy, device=d) for d in devs]
-    val = [CNNValue.load_model(a.value, device=d) for d in devs] if a.value else None
+    pol = [CNNPolicy.load_model(a.policy, device=d, symmetries=a.symmetries) for d in devs]
+    val = [CNNValue.load_model(a.value, device=d, symmetries=a.symmetries) for d in devs] if a.value else None
     svc = GoService(pol, val, a.max_batch, a.max_wait_ms)
     srv = make_server(svc, a.host, a.port)
     print("serving on http://%s:%d" % srv.server_address[:2], flush=True)
