@@ -256,8 +256,10 @@ __device__ __forceinline__ void conv_store_tile(const ConvFwdArgs& a, const f32x
 // ---------------- epilogue for the 32x32x16 MFMA layout (weights as A, pixels as B)
 // acc[i][j] (f32x16) of a wave: output channel nbase + 32 i + 8 g + 4 h + r
 // (h = lane >> 5, reg = 4 g + r) of pixel mrow + 32 j, mrow = the lane's pixel
-// of block 0.  ReLU' bitmask: per padded pixel (Cout/BN)*8 words; the lane's
-// 16*NB bits (bit 16 i + 4 g + r) sit in words blockIdx.y*8 + wn*4 + 2h + {0, 1}.
+// of block 0.  ReLU' bitmask: ConvEpilogue's layout, so any tile's dgrad can read this tile's bits
+// and the reverse.  With cw = 32 i + 8 g + 4 h + r the channel's offset in its wave half, the
+// layout's word is wn*4 + (cw % 16) / 4 and its bit 4 (cw / 16) + cw % 4: the lane's 16*NB bits sit in
+// words blockIdx.y*8 + wn*4 + h (even g) and + 2 (odd g), bit 8 i + 4 (g / 2) + r.
 template <int NB, int MB, int MODE>
 struct ConvEpilogue32 {
   int ooff[MB];
@@ -270,7 +272,7 @@ struct ConvEpilogue32 {
   __device__ __forceinline__ void load(const ConvFwdArgs& a, int mrow, int nbase, int wn) {
     const int SS = a.S * a.S;
     const int h = (threadIdx.x & 63) >> 5;
-    mslot = blockIdx.y * 8 + wn * 4 + 2 * h;
+    mslot = blockIdx.y * 8 + wn * 4 + h;
     mwords = gridDim.y * 8;
 #pragma unroll
     for (int j = 0; j < MB; ++j) {
@@ -297,7 +299,10 @@ struct ConvEpilogue32 {
           for (int g = 0; g < 4; ++g) mk[i][j][g] = *(const bf16x4*)(a.mask + ooff[j] + i * 32 + g * 8);
     } else if constexpr (MODE == MODE_MASKBITS) {
 #pragma unroll
-      for (int j = 0; j < MB; ++j) mw[j] = *(const uint2*)(a.mbits_in + (size_t)pix[j] * mwords + mslot);
+      for (int j = 0; j < MB; ++j) {
+        const uint32_t* p = a.mbits_in + (size_t)pix[j] * mwords + mslot;
+        mw[j] = make_uint2(p[0], p[2]);
+      }
     }
   }
 
@@ -313,7 +318,7 @@ struct ConvEpilogue32 {
           float v[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = acc[i][j][4 * g + r];
-          const int bit0 = 16 * i + 4 * g;
+          const int bit0 = 8 * i + 4 * (g >> 1);  // in word (g & 1)
           if constexpr (MODE == MODE_BIAS_RELU) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r] + bb[i][g][r], 0.f);
@@ -321,21 +326,25 @@ struct ConvEpilogue32 {
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = (float)mk[i][j][g][r] > 0.f ? v[r] : 0.f;
           } else if constexpr (MODE == MODE_MASKBITS) {
-            const uint32_t w = bit0 < 32 ? mw[j].x : mw[j].y;
+            const uint32_t w = (g & 1) ? mw[j].y : mw[j].x;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = ((w >> ((bit0 & 31) + r)) & 1u) ? v[r] : 0.f;
+            for (int r = 0; r < 4; ++r) v[r] = ((w >> (bit0 + r)) & 1u) ? v[r] : 0.f;
           }
           bf16x4 o;
 #pragma unroll
           for (int r = 0; r < 4; ++r) o[r] = (__bf16)v[r];
           if constexpr (MODE == MODE_BIAS_RELU) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) bits[bit0 >> 5] |= ((float)o[r] > 0.f ? 1u : 0u) << ((bit0 & 31) + r);
+            for (int r = 0; r < 4; ++r) bits[g & 1] |= ((float)o[r] > 0.f ? 1u : 0u) << (bit0 + r);
           }
           *(bf16x4*)(a.y + ooff[j] + i * 32 + g * 8) = o;
         }
       if constexpr (MODE == MODE_BIAS_RELU)
-        if (a.mbits_out) *(uint2*)(a.mbits_out + (size_t)pix[j] * mwords + mslot) = make_uint2(bits[0], bits[1]);
+        if (a.mbits_out) {
+          uint32_t* p = a.mbits_out + (size_t)pix[j] * mwords + mslot;
+          p[0] = bits[0];
+          p[2] = bits[1];
+        }
     }
   }
 };
