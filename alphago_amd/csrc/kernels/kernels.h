@@ -349,6 +349,7 @@ void launch_quantize_fp8(const __bf16* x, uint8_t* y, long n, float scale, hipSt
 #ifdef AGK_KERNEL_LAB
 void launch_bf8_convert_probe(const __bf16* x, uint8_t* y, long n, float scale, int mode, hipStream_t st);
 #endif
+// p, g: 16-byte aligned (float4 accesses; ops.cpp refuses anything else)
 void launch_sgd(float* p, const float* g, int64_t n, float lr, float gscale, hipStream_t st);
 
 // fused SGD + bf16 weight packs (pack.hip sgd_pack_kernel)
@@ -358,6 +359,9 @@ struct SgdPackLayer {
   int64_t off;     // OIHW fp32 weights at p + off (and their gradient at g + off)
   __bf16* wf;      // forward pack [T][Cout_p][Cin_p], or the packed-tap layout when pk_cpt > 0
   __bf16* wd;      // transposed dgrad pack [T][Cin_p][Cout_p] (taps flipped) or null
+                   // Never written (they keep the allocation's zeros): a trailing extra tap of wf / wd, and in
+                   // the packed-tap layout the chunks of the last step past tap T - 1 (q >= T * pk_cpt), which
+                   // pack_weights_kernel does zero
   int Cout_real, Cin_real, Cout_p, Cin_p, K, pk_cpt;
 };
 struct SgdPackArgs {

@@ -776,10 +776,18 @@ void comm_proxy(const Tensor& src, const Tensor& dst, int64_t channels, double w
   launch_check("comm_proxy");
 }
 
+// sgd_kernel / sgd_dev_kernel read p and g as float4: a contiguous view that starts inside a buffer
+// (p[1:]) is not 16-byte aligned
+static void check_float4_aligned(const char* op, const Tensor& p, const Tensor& g) {
+  const bool ok = reinterpret_cast<uintptr_t>(p.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 == 0;
+  TORCH_CHECK(ok, op, ": p and g must be 16-byte aligned (float4 loads)");
+}
+
 void sgd_update(const Tensor& p, const Tensor& g, double lr, double gscale) {
   check_dev("sgd_update", p, g);
   CHECK_F32(p); CHECK_F32(g); CHECK_CONTIG(p); CHECK_CONTIG(g);
   TORCH_CHECK(p.numel() == g.numel(), "size mismatch");
+  check_float4_aligned("sgd_update", p, g);
   agk::launch_sgd(p.data_ptr<float>(), g.data_ptr<float>(), p.numel(), (float)lr, (float)gscale, cur_stream());
   launch_check("sgd_update");
 }
@@ -790,6 +798,7 @@ void sgd_update_sched(const Tensor& p, const Tensor& g, const Tensor& sched, dou
   TORCH_CHECK(p.numel() == g.numel(), "size mismatch");
   TORCH_CHECK(sched.scalar_type() == at::kDouble && sched.numel() == 4 && sched.is_contiguous(),
               "sched must be float64[4] {lr0, decay, iterations, lr}");
+  check_float4_aligned("sgd_update_sched", p, g);
   agk::launch_sgd_sched(p.data_ptr<float>(), g.data_ptr<float>(), p.numel(), sched.data_ptr<double>(), (float)gscale,
                         cur_stream());
   launch_check("sgd_update_sched");

@@ -206,8 +206,12 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, i
 
 // Keras-SGD schedule kept on the device so a whole training step can be
 // captured in a HIP graph: sched = {lr0, decay, iterations, lr_current} (f64).
-// One thread computes lr = lr0 / (1 + decay * iterations) -- the same double
-// expression as KerasSGDSchedule.current() -- and advances the counter.
+// One thread computes lr = lr0 / (1 + decay * iterations) -- the double
+// expression of KerasSGDSchedule.current(); the compiler may contract the
+// denominator into one fma, so the contract is: within 4 * 2^-53 relative of
+// the host's value and equal to it where decay * iterations is exact
+// (tests/test_update_kernels.py; bit-equal at every t it runs) -- and
+// advances the counter.
 // An 8-entry schedule {lr0, decay, iterations, lr, beta_1, beta_2, opt, 0} adds Keras 1.0 Adam's
 // bias correction lr_t = lr sqrt(1 - beta_2^t) / (1 - beta_1^t), t = iterations + 1, when opt == 2.
 __global__ void sgd_sched_kernel(double* sched, int n) {
