@@ -7,7 +7,8 @@ Commands
   train-rl       RL policy training by self-play     (reference reinforcement_policy_trainer CLI)
   value-generate self-play positions for the value net
   selfplay-mcts  batched MCTS self-play games (SGF + states / pi / outcomes HDF5)
-  selfplay-to-sl MCTS self-play records -> SL training data (most-visited or played move targets)
+  selfplay-to-sl MCTS self-play records -> SL training data (most-visited or played move targets;
+                 --target dist adds the visit distributions for train-sl --targets pi)
   train-value    value-network regression
   gtp            run a GTP v2 engine on stdin/stdout (reference interface/gtp_wrapper)
   match          play games between two players (policy / mcts / random / external GTP)

@@ -121,6 +121,25 @@ struct PolicyHeadArgs {
   float ent_coef, kl_coef;  // >= 0; loss_kind 0 only; neither is multiplied by weight[b]
 };
 
+// Soft-target training head (head_soft.hip): the plain training head's arguments with a target
+// distribution per board in place of the move index.  A struct of its own, so that PolicyHeadArgs (the
+// kernarg layout of the plain and REG kernels) stays as it is.
+struct PolicyHeadSoftArgs {
+  const __bf16* y;      // padded NHWC (HP = S+2, P = 1, C)
+  const float* w;       // [C_real]
+  const float* b;       // [1]
+  const float* tdist;   // [B][T] target distribution, T = S*S or S*S + 1 (a trailing pass column is not
+                        // read); negatives / NaN count as 0, the board part is renormalised, zero or infinite mass = no loss
+  const int* sym;       // [B] in 0..7 or null: the symmetry pack_input applied to the board's planes
+  const float* weight;  // [B] per-board gradient weight or null
+  __bf16* dz;           // padded NHWC grad
+  float* loss;          // [B]
+  float* correct;       // [B]
+  float* dhead;         // [B][C_real + 1] per-board partials of dW_head, db_head
+  int B, S, C, C_real, T;
+  float grad_scale;     // d(mean loss)/d(logit) scale = 1/global_batch
+};
+
 struct ValueOutArgs {
   const float* h;       // [B][D] dense-1 output
   const float* w2;      // [D]
@@ -268,6 +287,7 @@ unsigned debug_error_fetch_and_clear(hipStream_t st);
 void launch_wgrad_reduce(const WgradReduceArgs& a, hipStream_t st);
 void launch_wgrad_reduce_multi(const std::vector<WgradReduceArgs>& jobs, hipStream_t st);
 void launch_policy_head(const PolicyHeadArgs& a, bool train, hipStream_t st);
+void launch_policy_head_soft(const PolicyHeadSoftArgs& a, hipStream_t st);
 void launch_head_logits(const PolicyHeadArgs& a, hipStream_t st);
 void launch_head_backward(const PolicyHeadArgs& a, const float* dlogits, hipStream_t st);
 void launch_value_out(const ValueOutArgs& a, hipStream_t st);

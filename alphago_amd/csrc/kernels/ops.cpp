@@ -246,6 +246,54 @@ void policy_head(const Tensor& y, const Tensor& w, const Tensor& b, const c10::o
   launch_check("policy_head");
 }
 
+// Soft-target training head (head_soft.hip): tdist (B, S*S or S*S + 1) f32 is a target distribution per
+// board in the planes' original frame, sym the symmetry pack_input gave the board.  Only what the schema
+// names exists here: no legal mask, temperature, binary-CE loss, entropy / KL terms, stats, probs or e5m2
+// dz (those stay with policy_head, which takes no distribution).
+void policy_head_soft(const Tensor& y, const Tensor& w, const Tensor& b, const Tensor& tdist,
+                      const c10::optional<Tensor>& sym, const c10::optional<Tensor>& weight, const Tensor& dz,
+                      const Tensor& loss, const Tensor& correct, const Tensor& dhead, int64_t S, double grad_scale) {
+  check_dev("policy_head_soft", y, w, b, tdist, sym, weight, dz, loss, correct, dhead);
+  CHECK_BF16(y); CHECK_CONTIG(y); CHECK_F32(w); CHECK_F32(b);
+  TORCH_CHECK(y.dim() == 4, "head input must be (B, S+2, S+2, C)");
+  const int64_t B = y.size(0), C = y.size(3);
+  TORCH_CHECK(y.size(1) == S + 2 && y.size(2) == S + 2, "head input must have pad 1");
+  TORCH_CHECK(C % 8 == 0 && C <= 256, "head channels must be a multiple of 8 and <= 256");
+  TORCH_CHECK(w.numel() <= C, "head weight must have at most as many entries as the head has channels");
+  TORCH_CHECK(S >= 1 && S * S <= 361, "board too large (the head holds at most 19 x 19)");
+  CHECK_F32(tdist); CHECK_CONTIG(tdist);
+  TORCH_CHECK(tdist.dim() == 2 && tdist.size(0) == B && (tdist.size(1) == S * S || tdist.size(1) == S * S + 1),
+              "tdist must be (B, S*S) or (B, S*S + 1)");
+  CHECK_BF16(dz); CHECK_CONTIG(dz); CHECK_F32(loss); CHECK_F32(correct); CHECK_F32(dhead);
+  CHECK_CONTIG(loss); CHECK_CONTIG(correct); CHECK_CONTIG(dhead);
+  TORCH_CHECK(dz.sizes() == y.sizes(), "dz must match y");
+  TORCH_CHECK(loss.numel() >= B && correct.numel() >= B, "loss and correct must hold B entries");
+  TORCH_CHECK(dhead.numel() >= B * (w.numel() + 1), "dhead too small");
+  agk::PolicyHeadSoftArgs a{};
+  a.y = bfp(y);
+  a.w = w.data_ptr<float>();
+  a.b = b.data_ptr<float>();
+  a.tdist = tdist.data_ptr<float>();
+  a.dz = bfp_mut(dz);
+  a.loss = loss.data_ptr<float>();
+  a.correct = correct.data_ptr<float>();
+  a.dhead = dhead.data_ptr<float>();
+  a.B = (int)B; a.S = (int)S; a.C = (int)C; a.C_real = (int)w.numel(); a.T = (int)tdist.size(1);
+  a.grad_scale = (float)grad_scale;
+  if (sym.has_value()) {
+    TORCH_CHECK(sym->scalar_type() == at::kInt && sym->numel() == B && sym->is_contiguous(), "sym: int32 (B,)");
+    a.sym = sym->data_ptr<int>();
+  }
+  if (weight.has_value()) {
+    CHECK_F32(*weight); CHECK_CONTIG(*weight);
+    TORCH_CHECK(weight->numel() == B, "weight must be (B,)");
+    a.weight = weight->data_ptr<float>();
+  }
+  if (B == 0) return;
+  agk::launch_policy_head_soft(a, cur_stream());
+  launch_check("policy_head_soft");
+}
+
 // z: (B, S*S) f32 <- y (B, S+2, S+2, C) bf16 . w + b
 void head_logits(const Tensor& y, const Tensor& w, const Tensor& b, const Tensor& z, int64_t S) {
   check_dev("head_logits", y, w, b, z);
@@ -962,6 +1010,8 @@ TORCH_LIBRARY(alphago_amd, m) {
       "policy_head(Tensor y, Tensor w, Tensor b, Tensor? target, Tensor? legal, Tensor? weight, Tensor(a!)? dz, Tensor(b!)? loss, "
       "Tensor(c!)? correct, Tensor(d!)? dhead, Tensor(e!)? probs, int S, float grad_scale, float temperature, "
       "int loss_kind=0, Tensor? ref_probs=None, Tensor(f!)? stats=None, float ent_coef=0.0, float kl_coef=0.0) -> ()");
+  m.def("policy_head_soft(Tensor y, Tensor w, Tensor b, Tensor tdist, Tensor? sym, Tensor? weight, Tensor(a!) dz, "
+        "Tensor(b!) loss, Tensor(c!) correct, Tensor(d!) dhead, int S, float grad_scale) -> ()");
   m.def("head_logits(Tensor y, Tensor w, Tensor b, Tensor(a!) z, int S) -> ()");
   m.def("head_backward(Tensor y, Tensor w, Tensor dlogits, Tensor(a!) dz, Tensor(b!) dhead, int S, "
         "Tensor(c!)? dz8=None, Tensor? dz8_scale=None, Tensor(d!)? dz8_amax=None) -> ()");
@@ -1034,6 +1084,7 @@ TORCH_LIBRARY_IMPL(alphago_amd, CUDA, m) {
   m.impl("conv_dgrad_bits_bf8", &conv_dgrad_bits_bf8);
   m.impl("conv_wgrad_fp8", &conv_wgrad_fp8);
   m.impl("policy_head", &policy_head);
+  m.impl("policy_head_soft", &policy_head_soft);
   m.impl("pack_input", &pack_input);
   m.impl("d4_expand", &d4_expand);
   m.impl("policy_head_d4", &policy_head_d4);

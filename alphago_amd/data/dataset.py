@@ -1,7 +1,8 @@
 """Training-position datasets (HDF5 schema of SURVEY.md §2.6).
 
 ``PositionDataset`` serves minibatches of (uint8 planes, int32 move targets)
-on the training device.  Each rank opens the file with the global row ids it
+on the training device (``targets="pi"``: float32 target distributions, one row
+per position, instead of the moves).  Each rank opens the file with the global row ids it
 owns (``rows``: its shard of the shuffled train/val permutation, see
 ``shard_rows``), so a rank never holds another rank's positions — host RAM and
 HBM per rank are ~N/world rows, and a node's 8 x 288 GB of HBM holds a full
@@ -137,15 +138,23 @@ class PositionDataset(object):
             self._targets_all = (acts[:, 0] * self.size + acts[:, 1]).astype(np.int32)
         elif targets == "outcomes":  # value-network regression targets z in {-1, 0, 1}
             self._targets_all = np.asarray(self.f["outcomes"].read()).astype(np.float32)
+        elif targets == "pi":  # per-position target distributions over the board points (selfplay-to-sl --target dist)
+            if "pi" not in self.f:
+                raise KeyError("%s has no 'pi' dataset (write it with selfplay-to-sl --target dist)" % path)
+            pds = self.f["pi"]
+            if len(pds.shape) != 2 or pds.shape[0] != self.n:
+                raise ValueError("%s: 'pi' must be (%d, T), got %s" % (path, self.n, tuple(pds.shape)))
+            self._targets_all = None  # (N, T) float32 is 361 x the moves: only this shard's rows are read
         else:
-            raise ValueError("targets must be 'actions' or 'outcomes'")
+            raise ValueError("targets must be 'actions', 'outcomes' or 'pi'")
         self.features = [x.decode() for x in self.f.attrs["features"]] if "features" in self.f.attrs else None
         self.chunked = ds.chunked
         self.chunk_rows = ds.chunk_rows if ds.chunked else 0
         self.rows = np.arange(self.n, dtype=np.int64) if rows is None else np.asarray(rows, np.int64)
         if len(self.rows) and (self.rows.min() < 0 or self.rows.max() >= self.n):
             raise IndexError("row ids outside [0, %d)" % self.n)
-        self.targets_np = self._targets_all[self.rows]
+        self.targets_np = self._targets_all[self.rows] if targets != "pi" else self._load_pi(self.f["pi"])
+        self.target_shape = tuple(self.targets_np.shape[1:])  # () for moves / outcomes, (T,) for distributions
         nbytes = len(self.rows) * int(np.prod(self.row_shape))
         fits = nbytes <= budget_gb * (1 << 30)
         self.resident = (resident == "yes") or (resident == "auto" and fits)
@@ -160,6 +169,21 @@ class PositionDataset(object):
             self.targets = None
 
     # ------------------------------------------------------------ host reads
+    def _load_pi(self, pds) -> np.ndarray:
+        """This shard's rows of the target distributions, read and validated a block at a time (in
+        file order): every entry finite and >= 0, every row with mass."""
+        out = np.empty((len(self.rows), pds.shape[1]), np.float32)
+        order = np.argsort(self.rows, kind="stable")
+        for s in range(0, len(order), 65536):
+            sel = order[s:s + 65536]
+            blk = np.asarray(pds.rows(self.rows[sel], self.threads), dtype=np.float32)
+            if not np.isfinite(blk).all() or (blk < 0).any():
+                raise ValueError("%s: 'pi' holds a non-finite or negative entry" % self.path)
+            if not (blk.sum(1) > 0).all():
+                raise ValueError("%s: 'pi' holds a row without mass" % self.path)
+            out[sel] = blk
+        return out
+
     def _load_rows(self, rows: np.ndarray) -> np.ndarray:
         """Rows in the given order; chunked files are decoded a block of chunks
         at a time, each chunk holding a requested row decoded exactly once."""
@@ -208,7 +232,8 @@ class PositionDataset(object):
         if self._stage is None or self._stage[0].shape[0] < n:
             pin = self.device.type == "cuda"
             self._stage = (torch.empty((n,) + self.row_shape, dtype=torch.uint8, pin_memory=pin),
-                           torch.empty((n,), dtype=torch.from_numpy(self.targets_np[:0]).dtype, pin_memory=pin))
+                           torch.empty((n,) + self.target_shape, dtype=torch.from_numpy(self.targets_np[:0]).dtype,
+                                       pin_memory=pin))
         hx, ht = self._stage[0][:n], self._stage[1][:n]
         self._gather_host(pos, hx.numpy())
         ht.numpy()[:] = self.targets_np[pos]
@@ -236,10 +261,11 @@ class Prefetcher(object):
         shape = (batch_size,) + ds.row_shape
         tdt = torch.from_numpy(ds.targets_np[:0]).dtype
         self.hx = [torch.empty(shape, dtype=torch.uint8, pin_memory=self.cuda) for _ in range(self.depth)]
-        self.ht = [torch.empty((batch_size,), dtype=tdt, pin_memory=self.cuda) for _ in range(self.depth)]
+        tshape = (batch_size,) + ds.target_shape
+        self.ht = [torch.empty(tshape, dtype=tdt, pin_memory=self.cuda) for _ in range(self.depth)]
         if self.cuda:
             self.dx = [torch.empty(shape, dtype=torch.uint8, device=dev) for _ in range(self.depth)]
-            self.dt = [torch.empty((batch_size,), dtype=tdt, device=dev) for _ in range(self.depth)]
+            self.dt = [torch.empty(tshape, dtype=tdt, device=dev) for _ in range(self.depth)]
             self.copy_stream = torch.cuda.Stream(dev)
             self.copied = [torch.cuda.Event() for _ in range(self.depth)]
             self.consumed = [None] * self.depth

@@ -335,6 +335,18 @@ def policy_head_train(y, w, b, target, dz, loss, correct, dhead, S: int, grad_sc
                        1 if bce else 0, ref_probs, stats, float(ent_coef), float(kl_coef))
 
 
+def policy_head_train_soft(y, w, b, tdist, dz, loss, correct, dhead, S: int, grad_scale: float, weight=None,
+                           sym=None):
+    """Fused policy head training step towards a target DISTRIBUTION per board (a search's root visit
+    distribution) instead of one move: ``tdist`` (B, S*S) or (B, S*S + 1) f32 in the planes' original
+    frame -- a trailing pass column is not read, negative entries count as 0 and the board part is
+    renormalised.  ``sym`` (B,) int32 is the tensor ``pack_input`` got: the kernel moves the
+    distribution with the board.  Per board ``loss`` = -sum_i q_i log p_i (no clip) and ``correct`` =
+    [argmax p == first argmax q]; a row without board mass is "no loss" (zero loss, metric and
+    gradient), and so is a row with an infinite entry (NaN entries count as 0).  No ``bce``, regularisers, ``stats`` or ``probs``: those belong to ``policy_head_train``."""
+    _ops().policy_head_soft(y, w, b, tdist, sym, weight, dz, loss, correct, dhead, S, float(grad_scale))
+
+
 def head_grad_sums(dhead, loss, correct, grad, sums):
     """grad = dhead.sum(0) and sums[:2] = (loss.sum(), correct.sum()) in one deterministic launch."""
     _ops().head_grad_sums(dhead, loss, correct, grad, sums)

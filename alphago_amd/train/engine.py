@@ -79,6 +79,60 @@ def apply_symmetry(planes: torch.Tensor, targets: Optional[torch.Tensor], sym: t
     return out, tout
 
 
+def apply_symmetry_dist(dist: torch.Tensor, sym: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """A (B, T) target distribution moved with its board: the mass of point p goes to fwd[s][p], the
+    rule ``apply_symmetry`` applies to an integer target (a one-hot row stays the one-hot of the
+    transformed move).  T = S*S or S*S + 1; a trailing pass column stays where it is."""
+    SS = table.shape[1]
+    if dist.dim() != 2 or dist.shape[1] not in (SS, SS + 1):
+        raise ValueError("target distribution must be (B, %d) or (B, %d)" % (SS, SS + 1))
+    inv = torch.argsort(table[sym.long()], dim=1)  # inv[b][i] = the point that lands on i
+    out = dist.clone()
+    out[:, :SS] = torch.gather(dist[:, :SS], 1, inv)
+    return out
+
+
+_SOFT_REFUSED = ("soft (distribution) targets train the plain cross-entropy only: leave policy_loss at 'ce' and "
+                 "ent_coef, kl_coef and collect_* off")
+
+
+_SOFT_NO_GRAPH = ("soft (distribution) targets are not supported in graph mode: the captured SL step takes one "
+                  "move per board")
+
+
+def is_soft_target(targets: torch.Tensor) -> bool:
+    """Floating (B, T) targets are per-board distributions (the soft-target head); integer targets
+    are move indices."""
+    return targets.is_floating_point() and targets.dim() == 2
+
+
+def soft_target_loss(logits: torch.Tensor, dist: torch.Tensor):
+    """The soft-target objective in torch ops (ops.policy_head_train_soft's): negatives clamped to
+    0 (NaN too), a pass column dropped, the board part renormalised; per board (CE = -sum q log p,
+    top-1 agreement, has-loss flag).  Both top-1 indices are the smallest among the maxima, the
+    kernel's tie rule (visit counts tie often; torch.argmax promises no order).  Terms with q_i == 0
+    add nothing, also where log p_i = -inf.  A row without board mass, or with an infinite entry,
+    has no loss."""
+    SS = logits.shape[1]
+    q = dist[:, :SS].to(logits.dtype)
+    q = torch.where(q > 0, q, torch.zeros_like(q))
+    m = q.sum(1, keepdim=True)
+    ok = (m > 0) & torch.isfinite(m)
+    has = ok.squeeze(1)
+    qh = torch.where(ok, q / torch.where(ok, m, torch.ones_like(m)), torch.zeros_like(q))
+    logp = torch.log_softmax(logits, 1)
+    ce = -torch.where(qh > 0, qh * logp, torch.zeros_like(logp)).sum(1)
+    correct = ((first_argmax(logits) == first_argmax(q)) & has).float()
+    return ce, correct, has
+
+
+def first_argmax(z: torch.Tensor) -> torch.Tensor:
+    """(B,) smallest index among each row's maxima."""
+    n = z.shape[1]
+    idx = torch.arange(n, device=z.device).expand_as(z)
+    return torch.where(z == z.max(1, keepdim=True).values, idx, torch.full_like(idx, n)).min(1).values
+
+
 class FlatParams:
     """fp32 master parameters and gradients, each in ONE flat device buffer.
 
@@ -501,7 +555,8 @@ class HipConvTrainer:
     def _init_head(self):
         pass
 
-    def _head_train(self, targets, gscale: float, weight) -> None:
+    def _head_train(self, targets, gscale: float, weight, sym=None) -> None:
+        """Head forward + backward into dZ[L-1] and the head gradient; ``sym`` is the forward's."""
         raise NotImplementedError
 
     # ------------------------------------------------------------------ helpers
@@ -772,7 +827,7 @@ class HipConvTrainer:
                 self._train_fwd = False
                 self._rows = None
         with trace_range("head"):
-            self._head_train(targets, 1.0 / (B * self.env.world_size), weight)
+            self._head_train(targets, 1.0 / (B * self.env.world_size), weight, sym)
         with trace_range("backward+allreduce"):
             self.backward_trunk(reduce)
 
@@ -923,7 +978,35 @@ class HipPolicyTrainer(HipConvTrainer):
         self.tgt = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
 
     def _forward_for_head(self, planes, targets, sym):
+        if is_soft_target(targets):  # no move target to transform: the soft head moves the distribution itself
+            self._check_soft(targets)
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(_SOFT_NO_GRAPH)
+            self.forward_trunk(planes, sym)
+            return
         self.forward_trunk(planes, sym, targets, self.tgt)
+
+    def _check_soft(self, dist) -> None:
+        """Soft targets (``is_soft_target``) run the plain soft-target head."""
+        if self.policy_loss == "bce" or self.ent_coef or self.kl_coef or self.collect_stats or self.collect_probs:
+            raise ValueError(_SOFT_REFUSED)
+        SS = self.S * self.S
+        if dist.shape[0] != self.batch or dist.shape[1] not in (SS, SS + 1):
+            raise ValueError("soft targets must be (%d, %d) or (%d, %d), got %s"
+                             % (self.batch, SS, self.batch, SS + 1, tuple(dist.shape)))
+
+    def _head_soft(self, dist, gscale, weight, sym) -> None:
+        if dist.dtype != torch.float32 or not dist.is_contiguous():
+            dist = dist.float().contiguous()
+        ops.policy_head_train_soft(self.Y[-1], self.fp.views["head_w"].view(-1), self.fp.views["head_b"], dist,
+                                   self.DZ[-1], self.loss, self.correct, self.dhead, self.S, gscale, weight=weight,
+                                   sym=sym)
+
+    def step(self, planes: torch.Tensor, targets: torch.Tensor, sym: Optional[torch.Tensor] = None,
+             weight: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None):
+        if is_soft_target(targets) and self.use_graph:  # before the graph path allocates its static inputs
+            raise RuntimeError(_SOFT_NO_GRAPH)
+        return super().step(planes, targets, sym, weight, rows)
 
     policy_loss = "ce"  # or "bce": the reference RL loss (binary CE on the softmax)
 
@@ -960,17 +1043,23 @@ class HipPolicyTrainer(HipConvTrainer):
                 kw["probs"] = self.head_probs
         return kw
 
-    def _head_train(self, targets, gscale, weight):
-        hw = self.fp.views["head_w"].view(-1)
-        hb = self.fp.views["head_b"]
-        ops.policy_head_train(self.Y[-1], hw, hb, self.tgt, self.DZ[-1], self.loss, self.correct, self.dhead,
-                              self.S, gscale, weight=weight, bce=self.policy_loss == "bce",
-                              **self._head_extras(True))
+    def _head_train(self, targets, gscale, weight, sym=None):
+        if is_soft_target(targets):
+            self._head_soft(targets, gscale, weight, sym)
+        else:
+            self._head_hard(gscale, weight)
         ho, hn = self.fp.segments["head_w"]
         # head gradient and the step's two metric sums in one launch (a fresh 2-vector per step, so
         # the returned scalars stay valid after the next step)
         self._metric_sums = torch.empty(2, device=self.device)
         ops.head_grad_sums(self.dhead, self.loss, self.correct, self.fp.grad[ho:ho + hn + 1], self._metric_sums)
+
+    def _head_hard(self, gscale, weight):
+        hw = self.fp.views["head_w"].view(-1)
+        hb = self.fp.views["head_b"]
+        ops.policy_head_train(self.Y[-1], hw, hb, self.tgt, self.DZ[-1], self.loss, self.correct, self.dhead,
+                              self.S, gscale, weight=weight, bce=self.policy_loss == "bce",
+                              **self._head_extras(True))
 
     def _step_metrics(self):
         return self._metric_sums[0], self._metric_sums[1]
@@ -978,6 +1067,11 @@ class HipPolicyTrainer(HipConvTrainer):
     @torch.no_grad()
     def evaluate(self, planes: torch.Tensor, targets: torch.Tensor):
         """Loss/accuracy without update (validation)."""
+        if is_soft_target(targets):
+            self._check_soft(targets)
+            self.forward_trunk(planes)
+            self._head_soft(targets, 0.0, None, None)
+            return self.loss.sum(), self.correct.sum()
         self.forward_trunk(planes, None, targets, self.tgt)
         hw = self.fp.views["head_w"].view(-1)
         ops.policy_head_train(self.Y[-1], hw, self.fp.views["head_b"], self.tgt, self.DZ[-1], self.loss,
@@ -1038,7 +1132,7 @@ class HipValueTrainer(HipConvTrainer):
         ops.head_logits(self.Y[-1], v["head_w"].view(-1), v["head_b"], self.z, self.S)
         ops.dense_f32(self.z, v["fc1_w"], self.h, bias=v["fc1_b"])  # h = z W1 + b1
 
-    def _head_train(self, targets, gscale, weight):
+    def _head_train(self, targets, gscale, weight, sym=None):
         v, gv = self.fp.views, self.fp.grad_views
         self._head_forward()
         self.tval.copy_(targets)
@@ -1146,7 +1240,22 @@ class TorchPolicyTrainer(_TorchTrainerBase):
         named = _trunk_named(net.trunk) + [("head_w", net.head_w), ("head_b", net.head_b)]
         self._setup(net, batch, lr, decay, device, dtype, iterations, named, optimizer, momentum, nesterov)
 
+    def _loss_soft(self, planes, dist, sym, weight):
+        """Targets are distributions (B, S*S [+ pass]): mean over the batch of -sum_i q_i log p_i,
+        the objective of the HIP soft-target head."""
+        if self.policy_loss == "bce" or self.ent_coef or self.kl_coef or self.collect_stats or self.collect_probs:
+            raise ValueError(_SOFT_REFUSED)
+        if sym is not None:
+            planes, _ = apply_symmetry(planes, None, sym, self.table)
+            dist = apply_symmetry_dist(dist, sym, self.table)
+        logits = self.net.logits_torch(planes.to(self.dtype))
+        per, correct, has = soft_target_loss(logits, dist)
+        w = has.to(per.dtype) if weight is None else has.to(per.dtype) * weight
+        return (per * w).sum() / (planes.shape[0] * self.env.world_size), per, correct
+
     def _loss(self, planes, targets, sym, weight):
+        if is_soft_target(targets):
+            return self._loss_soft(planes, targets, sym, weight)
         if sym is not None:
             planes, targets = apply_symmetry(planes, targets, sym, self.table)
         x = planes.to(self.dtype)

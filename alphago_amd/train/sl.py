@@ -24,7 +24,9 @@ Differences (all fixes from SURVEY.md §2.7):
 * ``--resident no`` streams the shard from the host through a pinned ring,
   a prefetch thread and a copy stream (block-shuffled order for LZF-chunked
   files, so each chunk is decoded about once per pass);
-* per-board D4 augmentation happens on the GPU inside ``pack_input``.
+* per-board D4 augmentation happens on the GPU inside ``pack_input``;
+* ``--targets pi`` trains towards a distribution per position (the search visit
+  distributions written by ``selfplay-to-sl --target dist``) instead of one move.
 
 Run: ``python -m alphago_amd.train.sl model.json data.h5 outdir -B 256``
 (multi-GPU: ``torchrun --nproc-per-node 8 -m alphago_amd.train.sl ...``).
@@ -86,6 +88,8 @@ class _SLParser(argparse.ArgumentParser):
         ns, rest = super().parse_known_args(args, namespace)
         if getattr(ns, "fp8_backward", False) and ns.precision != "fp8":
             self.error("--fp8-backward requires --precision fp8")
+        if getattr(ns, "graph", False) and getattr(ns, "targets", "actions") == "pi":
+            self.error("--graph runs the one-move-per-board step: not with --targets pi")
         return ns, rest
 
 
@@ -115,6 +119,10 @@ def _parser():
                         "the default; a 1-binade guard collapsed more SL runs, profiles/r6/README.md)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--no-symmetries", action="store_true", help="disable random D4 augmentation")
+    p.add_argument("--targets", default="actions", choices=["actions", "pi"],
+                   help="actions: the move of each position (default).  pi: its target distribution, the 'pi' "
+                        "dataset of selfplay-to-sl --target dist (soft-target head: cross-entropy against the "
+                        "search's visit distribution)")
     p.add_argument("--resident", default="auto", choices=["auto", "yes", "no"])
     p.add_argument("--metrics", default=None, help="JSONL metrics file (per-epoch and per-step records)")
     p.add_argument("--log-every", type=int, default=100,
@@ -168,6 +176,7 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
             meta.metadata = json.load(f)
     meta.metadata["training_data"] = args.train_data
     meta.metadata["model_file"] = args.model
+    meta.metadata["targets"] = args.targets
     run_cfg = RunConfig.capture("train-sl", args, env, kernel_backend=args.backend,
                                 dtype="bf16" if dev.type == "cuda" and args.backend != "torch" else "fp32")
     meta.metadata["config"] = run_cfg.to_dict()
@@ -191,7 +200,7 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
         my_train = block_shuffle(my_train, chunk_rows, seed=args.seed * 1000 + rank)
         my_val = np.sort(my_val)  # validation order does not matter; sorted = each chunk decoded once
     dataset = PositionDataset(args.train_data, device=dev, resident=args.resident,
-                              rows=np.concatenate([my_train, my_val]))
+                              rows=np.concatenate([my_train, my_val]), targets=args.targets)
     n_my_train, n_my_val = len(my_train), len(my_val)
     rows_per_rank = agdist.all_gather_object(len(dataset)) if env.distributed else [len(dataset)]
     meta.metadata["data"] = {"rows_per_rank": rows_per_rank, "resident": bool(dataset.resident),
@@ -320,7 +329,10 @@ def _validate(trainer, dataset, mine, B, dev):
             pad = B - len(idx)
             planes = torch.cat([planes, torch.zeros((pad,) + tuple(planes.shape[1:]), dtype=planes.dtype,
                                                     device=planes.device)])
-            tgt = torch.cat([tgt, torch.full((pad,), -1, dtype=tgt.dtype, device=tgt.device)])
+            # no-loss rows: move -1, or an all-zero distribution
+            fill = (torch.zeros((pad,) + tuple(tgt.shape[1:]), dtype=tgt.dtype, device=tgt.device) if tgt.dim() == 2
+                    else torch.full((pad,), -1, dtype=tgt.dtype, device=tgt.device))
+            tgt = torch.cat([tgt, fill])
         l, c = trainer.evaluate(planes, tgt)
         loss += l.double()
         corr += c.double()
