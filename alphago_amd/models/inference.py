@@ -131,6 +131,13 @@ class HipTrunkInference:
 
     @torch.no_grad()
     def sync_weights(self) -> None:
+        """Re-read the module's parameters into the engine's device copies.
+
+        Contract: no device tensor that a captured graph reads is ever rebound.  A bucket's graph holds
+        the addresses of ``wf``, ``wf_ws``, ``bias_p``, ``head_w``, ``head_b``, ``w8``, ``scales8``,
+        ``osc8`` (and a subclass's own weights, ``_after_sync``) from the moment it is captured, so a
+        refresh writes into those tensors in place; a tensor bound to a fresh allocation here would
+        leave every captured bucket replaying the old weights out of freed memory."""
         tr = self.net.trunk
         ws = [w.detach().to(self.device, torch.float32).contiguous() for w in tr.weights]
         ops.pack_weights(ws, self.wf)
@@ -142,7 +149,11 @@ class HipTrunkInference:
         self.head_b.copy_(self.net.head_b.detach().view(-1))
         if self.precision == "fp8":
             for l in range(self.L):
-                self.w8[l], self.ew[l] = ops.pack_weights_fp8(ws[l], self.Fp, self.cin_p[l])
+                w8, self.ew[l] = ops.pack_weights_fp8(ws[l], self.Fp, self.cin_p[l])
+                if self.w8[l] is None:
+                    self.w8[l] = w8
+                else:  # captured fp8 graphs read this buffer
+                    self.w8[l].copy_(w8)
                 self.scales8[l, 1] = 127 - self.ew[l]
             self.calibrated = False  # activation ranges change with the weights
         self._after_sync()
@@ -447,7 +458,11 @@ class HipValueInference(HipTrunkInference):
 
     def _after_sync(self):
         n = self.net
-        self.fc = [t.detach().to(self.device, torch.float32).clone() for t in (n.fc1_w, n.fc1_b, n.fc2_w, n.fc2_b)]
+        src = [t.detach() for t in (n.fc1_w, n.fc1_b, n.fc2_w, n.fc2_b)]
+        if self.fc is None:  # allocated once: the captured dense_f32 / value_out read these addresses
+            self.fc = [torch.empty(t.shape, dtype=torch.float32, device=self.device) for t in src]
+        for dst, t in zip(self.fc, src):
+            dst.copy_(t)
 
     def _alloc_outputs(self, bk):
         bk.values = torch.zeros((bk.B,), device=self.device)
