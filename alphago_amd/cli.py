@@ -10,13 +10,15 @@ Commands
   selfplay-to-sl MCTS self-play records -> SL training data (most-visited or played move targets;
                  --target dist adds the visit distributions for train-sl --targets pi)
   train-value    value-network regression
+  train-pv       dual policy+value net on selfplay-mcts records (pi and outcomes in one step)
   gtp            run a GTP v2 engine on stdin/stdout (reference interface/gtp_wrapper)
   match          play games between two players (policy / mcts / random / external GTP)
   bench          the headline SL throughput benchmark (bench.py)
   serve          HTTP/JSON policy/value/genmove service with dynamic batching
 
 Player specs (gtp/match): ``random``, ``policy:MODEL.json[:greedy|:T]``,
-``mcts:POLICY.json[,VALUE.json]:PLAYOUTS``, ``gtp:COMMAND LINE``.
+``mcts:POLICY.json[,VALUE.json]:PLAYOUTS`` (a dual ``init-model pv`` file alone is both nets),
+``gtp:COMMAND LINE``.
 """
 from __future__ import annotations
 
@@ -43,7 +45,7 @@ def add_symmetries_arg(p: argparse.ArgumentParser) -> None:
 
 def make_player(spec: str, device=None, symmetries: str = "none"):
     from .gtp.client import GTPClientPlayer
-    from .models.policy import CNNPolicy, CNNValue
+    from .models.policy import CNNPolicy, CNNPolicyValue, CNNValue, is_dual_spec
     from .search.arena import RandomPlayer
     from .search.players import GreedyPolicyPlayer, MCTSPlayer, ProbabilisticPolicyPlayer
 
@@ -63,6 +65,11 @@ def make_player(spec: str, device=None, symmetries: str = "none"):
         if not nets:
             nets, n = n, "1600"
         paths = nets.split(",")
+        if is_dual_spec(paths[0]):  # a dual (policy + value) net: the one file is the whole player
+            if len(paths) > 1:
+                raise ValueError("%s holds a dual policy+value net: no separate value net goes with it" % paths[0])
+            return MCTSPlayer(CNNPolicyValue.load_model(paths[0], device=device, symmetries=symmetries),
+                              None, n_playout=int(n))
         pol = CNNPolicy.load_model(paths[0], device=device, symmetries=symmetries)
         val = CNNValue.load_model(paths[1], device=device, symmetries=symmetries) if len(paths) > 1 else None
         return MCTSPlayer(pol, val, n_playout=int(n))
@@ -71,10 +78,11 @@ def make_player(spec: str, device=None, symmetries: str = "none"):
 
 def _init_model(argv):
     from .features import DEFAULT_FEATURES, VALUE_FEATURES
-    from .models.policy import CNNPolicy, CNNValue
+    from .models.policy import CNNPolicy, CNNPolicyValue, CNNValue
 
     p = argparse.ArgumentParser(prog="alphago_amd init-model")
-    p.add_argument("kind", choices=["policy", "value"])
+    p.add_argument("kind", choices=["policy", "value", "pv"],
+                   help="pv: the dual policy+value net (one trunk, two heads; 192 filters by default)")
     p.add_argument("json_out")
     p.add_argument("--weights", default=None, help="also write random-init weights (Keras HDF5)")
     p.add_argument("--features", default=None, help="comma-separated feature list")
@@ -89,6 +97,9 @@ def _init_model(argv):
     if a.kind == "policy":
         feats = a.features.split(",") if a.features else DEFAULT_FEATURES
         m = CNNPolicy(feats, board=a.board, filters_per_layer=a.filters or 128, layers=a.layers, device="cpu")
+    elif a.kind == "pv":
+        feats = a.features.split(",") if a.features else VALUE_FEATURES
+        m = CNNPolicyValue(feats, board=a.board, filters_per_layer=a.filters or 192, layers=a.layers, device="cpu")
     else:
         feats = a.features.split(",") if a.features else VALUE_FEATURES
         m = CNNValue(feats, board=a.board, filters_per_layer=a.filters or 152, layers=a.layers, device="cpu")
@@ -173,6 +184,9 @@ def _dispatch(argv: List[str]):
     if cmd == "train-value":
         from .train.value import train_cli
         return train_cli(rest)
+    if cmd == "train-pv":
+        from .train.pv import run_training as run_pv
+        return run_pv(rest)
     if cmd == "gtp":
         return _gtp(rest)
     if cmd == "match":

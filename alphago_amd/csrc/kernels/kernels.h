@@ -292,6 +292,23 @@ void launch_head_logits(const PolicyHeadArgs& a, hipStream_t st);
 void launch_head_backward(const PolicyHeadArgs& a, const float* dlogits, hipStream_t st);
 void launch_value_out(const ValueOutArgs& a, hipStream_t st);
 
+// Dual-head inference (head_pv.hip): one pass over the trunk's last activation gives the policy
+// head's masked softmax and the value head's 1x1-conv logits (the input of dense_f32 / value_out).
+struct PolicyValueHeadArgs {
+  const __bf16* y;       // padded NHWC (HP = S+2, P = 1, C)
+  const float* wp;       // [C_real] policy head
+  const float* bp;       // [1]
+  const float* wv;       // [C_real] value head
+  const float* bv;       // [1]
+  const uint8_t* legal;  // [B][S*S] or null
+  float* probs;          // [B][S*S] policy_head_probs' bits
+  float* zv;             // [B][S*S] y . wv + bv (head_logits' quantity)
+  int B, S, C, C_real;
+};
+void launch_policy_value_head(const PolicyValueHeadArgs& a, hipStream_t st);
+// head_backward that adds into dz instead of overwriting it (PolicyHeadArgs: y, w, dz, dhead, B, S, C, C_real)
+void launch_head_backward_add(const PolicyHeadArgs& a, const float* dlogits, hipStream_t st);
+
 // fused move sampling (sample.hip): out[b] = a draw from probs[b]**beta, -1 where has[b] == 0
 struct SampleArgs {
   const float* probs;    // [B][NP]

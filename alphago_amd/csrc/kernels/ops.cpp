@@ -353,6 +353,60 @@ void head_backward(const Tensor& y, const Tensor& w, const Tensor& dlogits, cons
   launch_check("head_backward");
 }
 
+// head_backward that accumulates: where y > 0, dz = bf16(dz + dlogits x w) (one fp32 fma, head_pv.hip);
+// dhead as head_backward.  There is no e5m2 form of an accumulation: dz8 is refused.
+void head_backward_add(const Tensor& y, const Tensor& w, const Tensor& dlogits, const Tensor& dz, const Tensor& dhead,
+                       int64_t S, const c10::optional<Tensor>& dz8) {
+  check_dev("head_backward_add", y, w, dlogits, dz, dhead, dz8);
+  TORCH_CHECK(!dz8.has_value(), "head_backward_add: accumulating into an e5m2 dz8 is not supported "
+              "(accumulate into the bf16 dz and quantise it with quantize_bf8)");
+  CHECK_BF16(y); CHECK_CONTIG(y); CHECK_F32(w); CHECK_CONTIG(w); CHECK_F32(dlogits); CHECK_CONTIG(dlogits);
+  CHECK_BF16(dz); CHECK_CONTIG(dz); CHECK_F32(dhead); CHECK_CONTIG(dhead);
+  TORCH_CHECK(y.dim() == 4, "head input must be (B, S+2, S+2, C)");
+  const int64_t B = y.size(0), C = y.size(3);
+  TORCH_CHECK(y.size(1) == S + 2 && y.size(2) == S + 2 && C % 8 == 0 && C >= 8 && C <= 256 && w.numel() <= C &&
+                  S >= 1 && S * S <= 361, "head geometry");
+  TORCH_CHECK(dz.sizes() == y.sizes() && dlogits.numel() == B * S * S && dhead.numel() >= B * (w.numel() + 1), "shapes");
+  agk::PolicyHeadArgs a{};
+  a.y = bfp(y); a.w = w.data_ptr<float>(); a.dz = bfp_mut(dz); a.dhead = dhead.data_ptr<float>();
+  a.B = (int)B; a.S = (int)S; a.C = (int)C; a.C_real = (int)w.numel();
+  if (B == 0) return;
+  agk::launch_head_backward_add(a, dlogits.data_ptr<float>(), cur_stream());
+  launch_check("head_backward_add");
+}
+
+// Dual-head inference: probs (B, S*S) = policy_head's masked softmax at temperature 1 of y . wp + bp, and
+// zv (B, S*S) = y . wv + bv (head_logits' quantity), from one read of the board (head_pv.hip)
+void policy_value_head(const Tensor& y, const Tensor& wp, const Tensor& bp, const Tensor& wv, const Tensor& bv,
+                       const Tensor& probs, const Tensor& zv, int64_t S, const c10::optional<Tensor>& legal) {
+  check_dev("policy_value_head", y, wp, bp, wv, bv, probs, zv, legal);
+  CHECK_BF16(y); CHECK_CONTIG(y); CHECK_F32(wp); CHECK_F32(bp); CHECK_F32(wv); CHECK_F32(bv);
+  CHECK_CONTIG(wp); CHECK_CONTIG(wv);
+  CHECK_F32(probs); CHECK_CONTIG(probs); CHECK_F32(zv); CHECK_CONTIG(zv);
+  TORCH_CHECK(y.dim() == 4, "head input must be (B, S+2, S+2, C)");
+  const int64_t B = y.size(0), C = y.size(3);
+  TORCH_CHECK(y.size(1) == S + 2 && y.size(2) == S + 2, "head input must have pad 1");
+  TORCH_CHECK(C % 8 == 0 && C >= 8 && C <= 256, "head channels must be a multiple of 8 and <= 256");
+  TORCH_CHECK(wp.numel() <= C && wv.numel() == wp.numel(), "both head weights must have the same (at most C) entries");
+  TORCH_CHECK(bp.numel() >= 1 && bv.numel() >= 1, "head biases must hold one entry");
+  TORCH_CHECK(S >= 1 && S * S <= 361, "board too large (the head holds at most 19 x 19)");
+  TORCH_CHECK(probs.numel() == B * S * S && zv.numel() == B * S * S, "probs and zv must be (B, S*S)");
+  agk::PolicyValueHeadArgs a{};
+  a.y = bfp(y);
+  a.wp = wp.data_ptr<float>(); a.bp = bp.data_ptr<float>();
+  a.wv = wv.data_ptr<float>(); a.bv = bv.data_ptr<float>();
+  a.probs = probs.data_ptr<float>(); a.zv = zv.data_ptr<float>();
+  a.B = (int)B; a.S = (int)S; a.C = (int)C; a.C_real = (int)wp.numel();
+  if (legal.has_value()) {
+    TORCH_CHECK(legal->scalar_type() == at::kByte && legal->numel() == B * S * S && legal->is_contiguous(),
+                "legal must be uint8 (B, S*S)");
+    a.legal = legal->data_ptr<uint8_t>();
+  }
+  if (B == 0) return;
+  agk::launch_policy_value_head(a, cur_stream());
+  launch_check("policy_value_head");
+}
+
 void value_out(const Tensor& h, const Tensor& w2, const Tensor& b2, const c10::optional<Tensor>& target,
                const c10::optional<Tensor>& weight, const Tensor& v, const c10::optional<Tensor>& loss,
                const c10::optional<Tensor>& correct, const c10::optional<Tensor>& dh, const c10::optional<Tensor>& dout,
@@ -1015,6 +1069,10 @@ TORCH_LIBRARY(alphago_amd, m) {
   m.def("head_logits(Tensor y, Tensor w, Tensor b, Tensor(a!) z, int S) -> ()");
   m.def("head_backward(Tensor y, Tensor w, Tensor dlogits, Tensor(a!) dz, Tensor(b!) dhead, int S, "
         "Tensor(c!)? dz8=None, Tensor? dz8_scale=None, Tensor(d!)? dz8_amax=None) -> ()");
+  m.def("head_backward_add(Tensor y, Tensor w, Tensor dlogits, Tensor(a!) dz, Tensor(b!) dhead, int S, "
+        "Tensor(c!)? dz8=None) -> ()");
+  m.def("policy_value_head(Tensor y, Tensor wp, Tensor bp, Tensor wv, Tensor bv, Tensor(a!) probs, Tensor(b!) zv, "
+        "int S, Tensor? legal=None) -> ()");
   m.def("head_grad_sums(Tensor dhead, Tensor loss, Tensor correct, Tensor(a!) grad, Tensor(b!) sums) -> ()");
   m.def(
       "value_out(Tensor h, Tensor w2, Tensor b2, Tensor? target, Tensor? weight, Tensor(a!) v, Tensor(b!)? loss, "
@@ -1091,6 +1149,8 @@ TORCH_LIBRARY_IMPL(alphago_amd, CUDA, m) {
   m.impl("group_mean", &group_mean);
   m.impl("head_logits", &head_logits);
   m.impl("head_backward", &head_backward);
+  m.impl("head_backward_add", &head_backward_add);
+  m.impl("policy_value_head", &policy_value_head);
   m.impl("value_out", &value_out);
   m.impl("pack_weights", &pack_weights);
   m.impl("ws_pack", &ws_pack);

@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from ..models.nets import PolicyNet, ValueNet
+from ..models.nets import PolicyNet, PolicyValueNet, ValueNet
 from .h5lite import H5File, H5Writer
 
 _NULLS = {"W_constraint": None, "W_regularizer": None, "activity_regularizer": None, "b_constraint": None,
@@ -100,9 +100,29 @@ def model_from_keras_json(spec: str):
     return PolicyNet(input_dim, board=board, filters_per_layer=filters, layers=len(trunk), **kw)
 
 
+def pv_spec(net: PolicyValueNet) -> Dict:
+    """The dual net's architecture (it is no Keras Sequential: a spec key of its own, ``pv_model``)."""
+    return dict(net.arch)
+
+
+def pv_from_spec(arch: Dict) -> PolicyValueNet:
+    arch = dict(arch)
+    for k in ("input_dim", "board", "filters_per_layer", "layers", "dense"):
+        if k not in arch:
+            raise ValueError("pv_model spec lacks %r" % k)
+    return PolicyValueNet(**{k: int(v) for k, v in arch.items()})
+
+
 def _weights_in_order(net) -> List[Tuple[str, List[torch.Tensor]]]:
-    names = _layer_names(net)
     tr = net.trunk
+    if isinstance(net, PolicyValueNet):  # trunk, policy head, then the value head's three layers
+        out = [("convolution2d_%d" % (i + 1), [tr.weights[i], tr.biases[i]]) for i in range(tr.layers)]
+        out.append(("convolution2d_%d" % (tr.layers + 1), [net.head_w, net.head_b]))
+        out.append(("value_convolution2d_1", [net.vhead_w, net.vhead_b]))
+        out.append(("value_dense_1", [net.fc1_w, net.fc1_b]))
+        out.append(("value_dense_2", [net.fc2_w, net.fc2_b]))
+        return out
+    names = _layer_names(net)
     out = []
     for i in range(tr.layers):
         out.append((names[i], [tr.weights[i], tr.biases[i]]))

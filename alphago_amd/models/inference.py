@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .nets import PolicyNet, ValueNet
+from .nets import PolicyNet, PolicyValueNet, ValueNet
 
 DEFAULT_BUCKETS = (1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024)
 
@@ -485,6 +485,65 @@ class HipValueInference(HipTrunkInference):
         return bk.values[:n]
 
 
+class HipPolicyValueInference(HipTrunkInference):
+    """Dual net: HIP trunk, then both heads from one read of its output -- policy_value_head (the
+    policy head's masked softmax and the value head's 1x1 conv) -> dense_f32 -> value_out, all inside
+    the captured graph.
+
+    The outputs of a bucket are one (B, S*S + 1) row per position, the move probabilities followed by
+    the value, so that ``submit_encoded(to_host=True)`` / ``collect`` (the base class's, unchanged)
+    bring both to the host in one copy behind one event; ``split_outputs`` takes such rows apart.
+    ``evaluate`` returns the pair (probs (n, S*S), values (n,)).  No symmetry ensembling yet."""
+
+    dual = True
+
+    def __init__(self, net: PolicyValueNet, device, **kw):
+        if kw.get("symmetries", "none") != "none":
+            raise ValueError("the dual (policy + value) engine does not ensemble over symmetries yet: "
+                             "symmetries must be \"none\", not %r" % (kw["symmetries"],))
+        self.vhead = None
+        super().__init__(net, device, **kw)
+
+    def _after_sync(self):
+        n = self.net
+        src = [n.vhead_w.detach().view(-1), n.vhead_b.detach().view(-1)] + \
+              [t.detach() for t in (n.fc1_w, n.fc1_b, n.fc2_w, n.fc2_b)]
+        if self.vhead is None:  # allocated once: the captured head kernels read these addresses
+            self.vhead = [torch.empty(t.shape, dtype=torch.float32, device=self.device) for t in src]
+        for dst, t in zip(self.vhead, src):
+            dst.copy_(t)
+
+    def _alloc_outputs(self, bk):
+        SS = self.S * self.S
+        bk.probs = torch.zeros((bk.B, SS), device=self.device)
+        bk.z = torch.zeros((bk.B, SS), device=self.device)
+        bk.h = torch.zeros((bk.B, self.vhead[2].shape[1]), device=self.device)
+        bk.values = torch.zeros((bk.B,), device=self.device)
+        bk.out = torch.zeros((bk.B, SS + 1), device=self.device)
+
+    def _head(self, bk, y):
+        vw, vb, w1, b1, w2, b2 = self.vhead
+        SS = self.S * self.S
+        ops.policy_value_head(y, self.head_w, self.head_b, vw, vb, bk.probs, bk.z, self.S, legal=bk.legal)
+        ops.dense_f32(bk.z, w1, bk.h, bias=b1)
+        ops.value_out(bk.h, w2.view(-1), b2, bk.values)
+        bk.out[:, :SS].copy_(bk.probs)
+        bk.out[:, SS].copy_(bk.values)
+
+    def _outputs(self, bk, n):
+        return bk.out[:n]
+
+    def split_outputs(self, out):
+        """(probs (n, S*S), values (n,)) views of output rows (device tensor or collect()'s numpy)."""
+        SS = self.S * self.S
+        return out[:, :SS], out[:, SS]
+
+    @torch.no_grad()
+    def evaluate(self, planes, legal=None, slot: int = 0):
+        """As HipTrunkInference.evaluate; returns (probs (n, S*S), values (n,))."""
+        return self.split_outputs(super().evaluate(planes, legal, slot))
+
+
 class _TorchSymmetries:
     """The symmetry modes of the torch engines: the module docstring's definition in plain torch
     (index tables from ``train/engine.symmetry_tables``)."""
@@ -590,6 +649,33 @@ class TorchValueInference(_TorchSymmetries):
         return acc * (1.0 / self.G)
 
 
+class TorchPolicyValueInference:
+    """CPU / fp32 oracle of the dual net: TorchPolicyInference._plain's and TorchValueInference's op
+    sequences on one shared trunk output.  ``evaluate`` returns (probs (n, S*S), values (n,))."""
+
+    supports_encoded = False
+    needs_ladder = False
+    dual = True
+    symmetries = "none"
+
+    def __init__(self, net: PolicyValueNet, device="cpu", symmetries: str = "none", symmetry_seed: int = 0):
+        if _check_symmetries(symmetries) != "none":
+            raise ValueError("the dual (policy + value) engine does not ensemble over symmetries yet: "
+                             "symmetries must be \"none\", not %r" % (symmetries,))
+        self.net, self.device = net, torch.device(device)
+
+    def sync_weights(self):
+        pass
+
+    @torch.no_grad()
+    def evaluate(self, planes, legal=None, slot: int = 0):
+        x = torch.as_tensor(planes).to(self.device)
+        logits, values = self.net.logits_value_torch(x.float())
+        if legal is not None:
+            logits = logits.masked_fill(torch.as_tensor(legal).to(self.device) == 0, float("-inf"))
+        return torch.nan_to_num(torch.softmax(logits, 1), nan=0.0), values
+
+
 def _torch_kw(kw):
     """The engine keywords the torch engines take too (feature_list etc. are unused: CPU featurizer path)."""
     return {k: v for k, v in kw.items() if k in ("symmetries", "symmetry_seed")}
@@ -609,3 +695,11 @@ def make_value_inference(net, device, **kw):
     if device.type == "cuda":
         return HipValueInference(net, device, **kw)
     return TorchValueInference(net, device, **_torch_kw(kw))
+
+
+def make_policy_value_inference(net, device, **kw):
+    """The dual net's engine: HIP on a GPU, torch on CPU.  ``symmetries`` other than "none" raises."""
+    device = torch.device(device)
+    if device.type == "cuda":
+        return HipPolicyValueInference(net, device, **kw)
+    return TorchPolicyValueInference(net, device, **_torch_kw(kw))

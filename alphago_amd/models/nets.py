@@ -43,6 +43,10 @@ def he_uniform_(net: nn.Module, generator=None) -> nn.Module:
         for w in list(net.trunk.weights) + [net.head_w]:
             bound = (6.0 / (w.shape[1] * w.shape[2] * w.shape[3])) ** 0.5
             w.uniform_(-bound, bound, generator=generator)
+        vh = getattr(net, "vhead_w", None)  # PolicyValueNet's second 1x1 head
+        if vh is not None:
+            bound = (6.0 / (vh.shape[1] * vh.shape[2] * vh.shape[3])) ** 0.5
+            vh.uniform_(-bound, bound, generator=generator)
         for name in ("fc1_w", "fc2_w"):  # Keras (in, out) layout: fan_in = rows
             w = getattr(net, name, None)
             if w is not None:
@@ -170,3 +174,63 @@ class ValueNet(nn.Module):
         if x.dtype == torch.uint8:
             x = x.float()
         return self.forward_torch(x)
+
+
+class PolicyValueNet(nn.Module):
+    """Dual-head network: one ConvStack, the policy head of PolicyNet (1x1 conv, softmax over S*S)
+    and the value head of ValueNet (1x1 conv, Dense(dense, linear), Dense(1, tanh)) on its output.
+    Reads the value net's planes (49 with ``color``)."""
+
+    def __init__(self, input_dim: int = 49, board: int = 19, filters_per_layer: int = 192, layers: int = 12,
+                 dense: int = 256, **kwargs):
+        super().__init__()
+        widths = [int(kwargs.get("filter_width_%d" % i, 5 if i == 1 else 3)) for i in range(1, layers + 1)]
+        self.arch = dict(input_dim=input_dim, board=board, filters_per_layer=filters_per_layer, layers=layers,
+                         dense=dense)
+        for i, w in enumerate(widths, 1):
+            if (i == 1 and w != 5) or (i > 1 and w != 3):
+                self.arch["filter_width_%d" % i] = w
+        self.board = board
+        self.trunk = ConvStack(input_dim, filters_per_layer, layers, widths)
+        self.head_w = nn.Parameter(torch.empty(1, filters_per_layer, 1, 1))
+        self.head_b = nn.Parameter(torch.zeros(1))
+        self.vhead_w = nn.Parameter(torch.empty(1, filters_per_layer, 1, 1))
+        self.vhead_b = nn.Parameter(torch.zeros(1))
+        self.fc1_w = nn.Parameter(torch.empty(board * board, dense))  # Keras Dense layout (in, out)
+        self.fc1_b = nn.Parameter(torch.zeros(dense))
+        self.fc2_w = nn.Parameter(torch.empty(dense, 1))
+        self.fc2_b = nn.Parameter(torch.zeros(1))
+        for p in (self.head_w, self.vhead_w, self.fc1_w, self.fc2_w):
+            keras_uniform_(p)
+
+    @property
+    def input_dim(self):
+        return self.arch["input_dim"]
+
+    def flops_per_position(self) -> float:
+        """Forward FLOPs per board (2*MACs): the trunk once, both 1x1 head convs and the two dense layers."""
+        s2 = self.board * self.board
+        tot, cin = 0.0, self.trunk.in_planes
+        for k in self.trunk.widths:
+            tot += 2.0 * s2 * cin * self.trunk.filters * k * k
+            cin = self.trunk.filters
+        d = self.arch["dense"]
+        return tot + 2 * (2.0 * s2 * cin) + 2.0 * s2 * d + 2.0 * d
+
+    def heads_torch(self, h: torch.Tensor):
+        """(policy logits (B, S*S), value (B,)) from the trunk output: PolicyNet.logits_torch's and
+        ValueNet.forward_torch's op sequences."""
+        z = F.conv2d(h, self.head_w.to(h.dtype), self.head_b.to(h.dtype)).flatten(1).float()
+        zv = F.conv2d(h, self.vhead_w.to(h.dtype), self.vhead_b.to(h.dtype)).flatten(1).float()
+        zv = zv @ self.fc1_w + self.fc1_b
+        return z, torch.tanh(zv @ self.fc2_w + self.fc2_b).squeeze(1)
+
+    def logits_value_torch(self, x: torch.Tensor):
+        return self.heads_torch(self.trunk.forward_torch(x))
+
+    def forward(self, x: torch.Tensor):
+        """x: (B, C, S, S) float/uint8 planes -> (probs (B, S*S), value (B,))."""
+        if x.dtype == torch.uint8:
+            x = x.float()
+        z, v = self.logits_value_torch(x)
+        return torch.softmax(z, dim=1), v

@@ -19,8 +19,9 @@ import torch
 from ..features import DEFAULT_FEATURES, VALUE_FEATURES, Preprocess
 from ..io import keras_compat
 from ..utils.gorecords import flatten_idx
-from .inference import SYMMETRY_MODES, make_policy_inference, make_value_inference
-from .nets import PolicyNet, ValueNet
+from .inference import (SYMMETRY_MODES, make_policy_inference, make_policy_value_inference,
+                        make_value_inference)
+from .nets import PolicyNet, PolicyValueNet, ValueNet
 
 
 def default_device() -> torch.device:
@@ -86,7 +87,7 @@ class _NetWrapper(object):
         obj = cls.__new__(cls)
         obj.preprocessor = Preprocess(specs["feature_list"])
         obj.device = torch.device(device) if device is not None else default_device()
-        net = keras_compat.model_from_keras_json(specs["keras_model"])
+        net = cls._net_from_specs(specs)
         if not isinstance(net, cls._net_cls):
             raise ValueError("%s expects a %s spec" % (cls.__name__, cls._net_cls.__name__))
         obj.model = net.to(obj.device)
@@ -98,6 +99,12 @@ class _NetWrapper(object):
                 wf = os.path.join(os.path.dirname(os.path.abspath(json_file)), wf)
             keras_compat.load_weights(obj.model, wf)
         return obj
+
+    @classmethod
+    def _net_from_specs(cls, specs):
+        if "keras_model" not in specs:  # e.g. a dual net's file ("pv_model"): not this wrapper's
+            raise ValueError("%s expects a %s spec" % (cls.__name__, cls._net_cls.__name__))
+        return keras_compat.model_from_keras_json(specs["keras_model"])
 
     def load_weights(self, weights_file: str) -> None:
         keras_compat.load_weights(self.model, weights_file)
@@ -176,3 +183,103 @@ class CNNValue(_NetWrapper):
 
     def eval_state(self, state) -> float:
         return self.batch_eval_state([state])[0]
+
+
+def is_dual_spec(json_file: str) -> bool:
+    """Whether a model JSON holds a dual (policy + value) net: decided by its spec key."""
+    with open(json_file, "r") as f:
+        return "pv_model" in json.load(f)
+
+
+class CNNPolicyValue(_NetWrapper):
+    """Dual-head network: one trunk, state -> (distribution over moves, expected outcome for the
+    player to move).  ``eval_state`` / ``batch_eval_state`` are CNNPolicy's (the move list);
+    ``batch_eval_value`` and ``batch_eval_both`` give the value head.  The model file carries the
+    architecture under ``pv_model`` (the net is no Keras Sequential); weights use the layer-ordered
+    HDF5 layout of the other nets."""
+
+    _net_cls = PolicyValueNet
+    _select = staticmethod(CNNPolicy._select)
+    dual = True  # BatchedMCTS: one forward gives priors and values
+
+    def __init__(self, feature_list: Sequence[str] = VALUE_FEATURES, device=None, **kwargs):
+        super().__init__(feature_list, device=device, **kwargs)
+
+    def _make_engine(self):
+        return make_policy_value_inference(self.model, self.device, **self._engine_kw())
+
+    # ---------------------------------------------------------- persistence
+    def save_model(self, json_file: str, weights_file: Optional[str] = None) -> None:
+        specs = {"pv_model": keras_compat.pv_spec(self.model), "feature_list": self.preprocessor.feature_list}
+        if weights_file is not None:
+            keras_compat.save_weights(self.model, weights_file)
+            specs["weights_file"] = weights_file
+        with open(json_file, "w") as f:
+            json.dump(specs, f)
+
+    @classmethod
+    def _net_from_specs(cls, specs):
+        if "pv_model" not in specs:
+            raise ValueError("%s expects a %s spec" % (cls.__name__, cls._net_cls.__name__))
+        return keras_compat.pv_from_spec(specs["pv_model"])
+
+    # ----------------------------------------------------------- evaluation
+    def forward(self, planes, legal=None):
+        """(B, F, S, S) planes -> (probs (B, S*S), values (B,)) numpy."""
+        planes = np.asarray(planes)
+        if planes.dtype != np.uint8:
+            planes = planes.astype(np.uint8)
+        probs, values = self.engine.evaluate(planes, legal)
+        return probs.float().cpu().numpy(), values.float().cpu().numpy()
+
+    def _check_states(self, states):
+        size = states[0].size
+        if any(st.size != size for st in states):
+            raise ValueError("all states must have the same size")
+        return size
+
+    def batch_eval_both(self, states, moves_lists=None):
+        """One forward: ([(move, prob), ...] per state as ``batch_eval_state``, [value per state])."""
+        if not states:
+            return [], []
+        size = self._check_states(states)
+        probs, values = self.forward(self.preprocessor.states_to_uint8(states))
+        moves_lists = moves_lists or [st.get_legal_moves() for st in states]
+        return ([self._select(probs[i], moves_lists[i], size) for i in range(len(states))],
+                [float(v) for v in values])
+
+    def batch_eval_state(self, states, moves_lists=None):
+        return self.batch_eval_both(states, moves_lists)[0]
+
+    def eval_state(self, state, moves=None):
+        return self.batch_eval_state([state], [moves] if moves is not None else None)[0]
+
+    def batch_eval_value(self, states) -> List[float]:
+        if not states:
+            return []
+        self._check_states(states)
+        return [float(v) for v in self.forward(self.preprocessor.states_to_uint8(states))[1]]
+
+    # ---------------------------------------------------------------- split
+    def split(self):
+        """(CNNPolicy, CNNValue) carrying copies of the trunk and the respective head, both on this
+        net's feature list: the pair computes what the two heads compute, each on its own trunk."""
+        a, fl = self.model.arch, list(self.preprocessor.feature_list)
+        kw = {k: v for k, v in a.items() if k.startswith("filter_width_")}
+        pol = CNNPolicy(fl, device=self.device, board=a["board"], filters_per_layer=a["filters_per_layer"],
+                        layers=a["layers"], **kw)
+        val = CNNValue(fl, device=self.device, board=a["board"], filters_per_layer=a["filters_per_layer"],
+                       layers=a["layers"], dense=a["dense"], **kw)
+        m = self.model
+        with torch.no_grad():
+            for dst in (pol.model, val.model):
+                for l in range(m.trunk.layers):
+                    dst.trunk.weights[l].copy_(m.trunk.weights[l])
+                    dst.trunk.biases[l].copy_(m.trunk.biases[l])
+            pol.model.head_w.copy_(m.head_w)
+            pol.model.head_b.copy_(m.head_b)
+            val.model.head_w.copy_(m.vhead_w)
+            val.model.head_b.copy_(m.vhead_b)
+            for n in ("fc1_w", "fc1_b", "fc2_w", "fc2_b"):
+                getattr(val.model, n).copy_(getattr(m, n))
+        return pol, val

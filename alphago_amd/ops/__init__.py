@@ -541,6 +541,22 @@ def head_backward(y, w, dlogits, dz, dhead, S: int, dz8=None, dz8_scale=None, dz
     _ops().head_backward(y, w, dlogits, dz, dhead, S, dz8, dz8_scale, dz8_amax)
 
 
+def head_backward_add(y, w, dlogits, dz, dhead, S: int, dz8=None):
+    """``head_backward`` that accumulates: where y > 0, dz = bf16(dz + dlogits x w) (one fp32 fma, then
+    round-to-nearest-even); elsewhere dz keeps its bits.  ``dhead`` as ``head_backward``.  The dual
+    trainer's value head adds into the dZ the policy head wrote.  ``dz8`` is refused: an e5m2 buffer
+    cannot be accumulated into."""
+    _ops().head_backward_add(y, w, dlogits, dz, dhead, S, dz8)
+
+
+def policy_value_head(y, wp, bp, wv, bv, probs, zv, S: int, legal=None):
+    """Both heads of the dual net from one read of the trunk output: ``probs`` (B, S*S) is
+    ``policy_head_probs(y, wp, bp, legal)`` bit for bit, ``zv`` (B, S*S) fp32 the value head's 1x1 conv
+    ``y . wv + bv`` (``head_logits``' quantity, the input of ``dense_f32``)."""
+    _ops().policy_value_head(y, wp, bp, wv, bv, probs, zv, S, legal)
+    return probs, zv
+
+
 def value_out(h, w2, b2, v, target=None, weight=None, loss=None, correct=None, dh=None, dout=None,
               grad_scale: float = 1.0):
     """v = tanh(h w2 + b2); with target: MSE loss, sign agreement, dh and per-board [dw2 | db2]."""

@@ -43,6 +43,11 @@ def _fallback_eval(engine, planes, masks=None) -> np.ndarray:
     return engine.evaluate(planes, masks, slot=FALLBACK_SLOT).float().cpu().numpy()
 
 
+def _fallback_eval_dual(engine, planes, masks=None):
+    p, v = engine.evaluate(planes, masks, slot=FALLBACK_SLOT)
+    return p.float().cpu().numpy(), v.float().cpu().numpy()
+
+
 class _ForestGroup(object):
     """Several native Forests presented as one (tree t -> (forest, local index))."""
 
@@ -104,6 +109,8 @@ class BatchedMCTS(object):
         if rollout_policy not in self.ROLLOUT_POLICIES:
             raise ValueError("rollout_policy must be one of %s" % sorted(self.ROLLOUT_POLICIES))
         self.policy, self.value = policy, value
+        # a dual (policy + value) net: one forward per leaf batch gives the priors and the values
+        self._dual = value is None and bool(getattr(policy, "dual", False))
         self.rollout_policy = rollout_policy
         self.playout_depth = playout_depth
         self.pipeline = pipeline
@@ -211,9 +218,12 @@ class BatchedMCTS(object):
         hp, hv = handles
         # mask: sensible moves from the GPU featurizer, so apply() skips its own scan
         probs, mask, bad = pe.collect(hp)
+        values = None
+        if self._dual:  # rows of S*S probabilities and the value, from the one submission
+            probs, values = pe.split_outputs(probs)
+            values = np.array(values, dtype=np.float32, copy=True)
         probs = np.array(probs, copy=True)
         mask = np.array(mask, copy=True)
-        values = None
         if hv is not None:
             values, _, vbad = ve.collect(hv)
             values = np.array(values, copy=True)
@@ -227,7 +237,10 @@ class BatchedMCTS(object):
             vs = getattr(self, "_vstream", None)
             if vs is not None:
                 torch.cuda.current_stream(vs.device).wait_stream(vs)
-            probs[bad] = _fallback_eval(pe, planes, masks)
+            if self._dual:
+                probs[bad], values[bad] = _fallback_eval_dual(pe, planes, masks)
+            else:
+                probs[bad] = _fallback_eval(pe, planes, masks)
             mask[bad] = masks
             if ve is not None:
                 values[bad] = _fallback_eval(ve, self.value.preprocessor.states_to_uint8(states))
@@ -252,8 +265,12 @@ class BatchedMCTS(object):
         f.leaf_features_into(buf.data_ptr(), buf.numel(), self.threads)
         planes = buf.view(L, f.feature_planes, s0.size, s0.size)
         masks = torch.from_numpy(f.leaf_masks())
-        probs = self.policy.engine.evaluate(planes, masks).float().cpu().numpy()
         values = None
+        if self._dual:
+            probs, values = self.policy.engine.evaluate(planes, masks)
+            probs, values = probs.float().cpu().numpy(), values.float().cpu().numpy()
+        else:
+            probs = self.policy.engine.evaluate(planes, masks).float().cpu().numpy()
         if self.value is not None:
             if self._same_feats:
                 vplanes = planes

@@ -388,11 +388,12 @@ def phase_table(stats: List[RoundStats], width: int = 50) -> List[Dict[str, floa
 
 def selfplay_cli(argv=None):
     """``selfplay-mcts``: full-game batched MCTS self-play on every rank (torchrun), SGFs + HDF5."""
-    from ..models.policy import CNNPolicy, CNNValue
+    from ..models.policy import CNNPolicy, CNNPolicyValue, CNNValue, is_dual_spec
     from ..parallel import dist as agdist
 
     p = argparse.ArgumentParser(description="Full-game batched MCTS self-play (SGF + HDF5 training records)")
-    p.add_argument("policy_json")
+    p.add_argument("policy_json", help="policy net, or a dual policy+value net (init-model pv): that net alone "
+                                       "runs the search, and `states` holds its own planes")
     p.add_argument("out_directory")
     p.add_argument("--value-json", default=None)
     p.add_argument("--games", type=int, default=256, help="games per rank")
@@ -418,9 +419,16 @@ def selfplay_cli(argv=None):
     p.add_argument("--keep-shards", action="store_true")
     a = p.parse_args(argv)
     env = agdist.init_from_env()
-    policy = CNNPolicy.load_model(a.policy_json, device=env.device)
-    value = CNNValue.load_model(a.value_json, device=env.device) if a.value_json else None
-    lm = a.lmbda if a.lmbda is not None else (0.0 if value is not None else 1.0)
+    dual = is_dual_spec(a.policy_json)
+    if dual:
+        if a.value_json:
+            raise SystemExit("selfplay-mcts: %s holds a dual policy+value net; --value-json does not go with it"
+                             % a.policy_json)
+        policy, value = CNNPolicyValue.load_model(a.policy_json, device=env.device), None
+    else:
+        policy = CNNPolicy.load_model(a.policy_json, device=env.device)
+        value = CNNValue.load_model(a.value_json, device=env.device) if a.value_json else None
+    lm = a.lmbda if a.lmbda is not None else (0.0 if value is not None or dual else 1.0)
     cfg = MCTSConfig(n_playout=a.playouts, leaves_per_tree=a.leaves_per_tree, c_puct=a.c_puct, lmbda=lm,
                      rollout_policy=a.rollout_policy, rollout_limit=a.rollout_limit, temperature=a.temperature,
                      temp_moves=a.temp_moves, noise=a.noise or None, resign=a.resign, resign_moves=a.resign_moves)
@@ -428,8 +436,9 @@ def selfplay_cli(argv=None):
     os.makedirs(a.out_directory, exist_ok=True)
     h5 = os.path.join(a.out_directory, "selfplay.h5" if env.world_size == 1 else "selfplay.h5.rank%d" % env.rank)
     sgf = None if a.no_sgf else os.path.join(a.out_directory, "sgf", "rank%d" % env.rank)
+    wkw = {"features": list(policy.preprocessor.feature_list)} if dual else {}  # the dual net's own planes
     writer = SelfPlayWriter(h5, sgf, size=S, positions_per_game=a.positions_per_game,
-                            seed=a.seed * 1009 + env.rank)
+                            seed=a.seed * 1009 + env.rank, **wkw)
     stats: List[RoundStats] = []
     t0 = time.perf_counter()
     play_selfplay(policy, value, a.games, a.concurrent, cfg, size=S, komi=a.komi, max_moves=a.max_moves or None,

@@ -283,9 +283,13 @@ def serve_parser():
 
 
 def serve_cli(argv: Sequence[str]) -> int:
-    from ..models.policy import CNNPolicy, CNNValue
+    from ..models.policy import CNNPolicy, CNNValue, is_dual_spec
 
     a = serve_parser().parse_args(list(argv))
+    for path in (a.policy, a.value):
+        if path and is_dual_spec(path):
+            raise SystemExit("serve: %s holds a dual policy+value net, which the service does not batch yet; "
+                             "serve the pair from CNNPolicyValue.split() instead" % path)
     if a.precision:
         import os
 

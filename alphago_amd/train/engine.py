@@ -1176,6 +1176,155 @@ class HipValueTrainer(HipConvTrainer):
         return self.val.clone()
 
 
+_PV_NO_GRAPH = ("the dual (policy + value) trainer is not supported in graph mode: the captured SL step takes one "
+                "move per board and no outcome")
+
+_PV_REFUSED = ("the dual (policy + value) trainer trains the plain cross-entropy plus the value MSE only: leave "
+               "policy_loss at 'ce' and ent_coef, kl_coef and collect_* off")
+
+
+def _pv_targets(targets):
+    if not isinstance(targets, (tuple, list)) or len(targets) != 2:
+        raise ValueError("the dual trainer's targets are a pair (moves or pi, outcomes z)")
+    return targets[0], targets[1]
+
+
+class HipPolicyValueTrainer(HipPolicyTrainer):
+    """Dual net (PolicyValueNet): one HIP trunk, the policy trainer's fused head and the value
+    trainer's head on its output.  Called as ``step(planes, (pi_or_moves, z), sym=None, weight=None)``
+    / ``compute_grads(...)``; the loss is policy CE (hard moves or a soft ``(B, S*S [+ 1])``
+    distribution, exactly HipPolicyTrainer's heads) + ``value_coef`` * MSE(v, z), each term divided
+    by the global batch.  ``value_coef`` (default 1.0, AlphaGo Zero's equal weighting) enters through
+    ``value_out``'s ``grad_scale``.
+
+    Order of a step: trunk forward; the policy head (writes dZ[L-1] and its per-board head partials);
+    ``head_logits`` -> ``dense_f32`` -> ``value_out`` and the two ``dense_f32`` backward calls as in
+    HipValueTrainer; ``head_backward_add`` adds the value head's ReLU'-masked dY into dZ[L-1]; the
+    ``head_grad_sums`` calls; the unchanged trunk backward and update.  All eight head tensors live
+    in the flat parameters, so the fused optimizer, the buckets and data parallelism need nothing new.
+
+    ``step`` returns (policy loss sum, top-1 sum, value squared-error sum, sign-agreement sum).
+
+    fp8: the head writes the bf16 dZ only (``_top_e5m2_fusable`` is False: a sum of two heads cannot
+    be accumulated in e5m2), so an fp8 backward works through the unfused ``quantize_bf8`` pass over
+    the summed dZ[L-1], the policy trainer's path.  Graph mode and the regularised head options
+    (``ent_coef``, ``kl_coef``, ``collect_*``, ``policy_loss='bce'``) are refused."""
+
+    def __init__(self, net, batch: int, lr: float = 0.003, decay: float = 0.0, value_coef: float = 1.0, **kw):
+        self.value_coef = float(value_coef)
+        super().__init__(net, batch, lr, decay, **kw)
+
+    def _head_named_params(self):
+        n = self.net
+        return [("head_w", n.head_w), ("head_b", n.head_b), ("vhead_w", n.vhead_w), ("vhead_b", n.vhead_b),
+                ("fc1_w", n.fc1_w), ("fc1_b", n.fc1_b), ("fc2_w", n.fc2_w), ("fc2_b", n.fc2_b)]
+
+    def _init_head(self):
+        super()._init_head()
+        B, NP, dev = self.batch, self.S * self.S, self.device
+        D = self.net.fc1_w.shape[1]
+        self.z = torch.zeros(B, NP, device=dev)
+        self.h = torch.zeros(B, D, device=dev)
+        self.dh = torch.zeros(B, D, device=dev)
+        self.dzl = torch.zeros(B, NP, device=dev)
+        self.val = torch.zeros(B, device=dev)
+        self.dout = torch.zeros(B, D + 1, device=dev)
+        self.vdhead = torch.zeros(B, self.F + 1, device=dev)
+        self.tval = torch.zeros(B, device=dev)
+        self.vloss = torch.zeros(B, device=dev)
+        self.vcorrect = torch.zeros(B, device=dev)
+
+    def enable_graphs(self, on: bool = True) -> None:
+        if on:
+            raise RuntimeError(_PV_NO_GRAPH)
+        super().enable_graphs(False)
+
+    def _top_e5m2_fusable(self) -> bool:
+        return False
+
+    def _check_plain(self) -> None:
+        if self.policy_loss != "ce" or self.ent_coef or self.kl_coef or self.collect_stats or self.collect_probs:
+            raise ValueError(_PV_REFUSED)
+
+    def _forward_for_head(self, planes, targets, sym):
+        self._check_plain()
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(_PV_NO_GRAPH)
+        pi, z = _pv_targets(targets)
+        if z.numel() != self.batch:
+            raise ValueError("outcomes must hold %d entries, got %d" % (self.batch, z.numel()))
+        super()._forward_for_head(planes, pi, sym)
+
+    def _value_forward(self):
+        v = self.fp.views
+        ops.head_logits(self.Y[-1], v["vhead_w"].view(-1), v["vhead_b"], self.z, self.S)
+        ops.dense_f32(self.z, v["fc1_w"], self.h, bias=v["fc1_b"])  # h = z W1 + b1
+
+    def _head_train(self, targets, gscale, weight, sym=None):
+        pi, z = _pv_targets(targets)
+        v, gv = self.fp.views, self.fp.grad_views
+        # 1. the policy head, unchanged: dZ[L-1] and its [dW_head | db_head] partials
+        if is_soft_target(pi):
+            self._head_soft(pi, gscale, weight, sym)
+        else:
+            self._head_hard(gscale, weight)
+        # 2. the value head's forward, output layer and dense backward (HipValueTrainer._head_train)
+        self._value_forward()
+        self.tval.copy_(z)
+        ops.value_out(self.h, v["fc2_w"].view(-1), v["fc2_b"], self.val, target=self.tval, weight=weight,
+                      loss=self.vloss, correct=self.vcorrect, dh=self.dh, dout=self.dout,
+                      grad_scale=gscale * self.value_coef)
+        ops.dense_f32(self.z, self.dh, gv["fc1_w"], trans_a=True)  # dW1 = z^T dh
+        ops.dense_f32(self.dh, v["fc1_w"], self.dzl, trans_b=True)  # dz = dh W1^T
+        # 3. the value head's dY added into the policy head's dZ[L-1]
+        ops.head_backward_add(self.Y[-1], v["vhead_w"].view(-1), self.dzl, self.DZ[-1], self.vdhead, self.S)
+        # 4. column sums of every per-board partial, and the four metric sums (fresh vectors per step)
+        self._metric_sums = torch.empty(2, device=self.device)
+        self._vmetric_sums = torch.empty(2, device=self.device)
+        ho, hn = self.fp.segments["head_w"]
+        ops.head_grad_sums(self.dhead, self.loss, self.correct, self.fp.grad[ho:ho + hn + 1], self._metric_sums)
+        ops.head_grad_sums(self.dh, self.vloss, self.vcorrect, gv["fc1_b"], self._vmetric_sums)
+        o2, n2 = self.fp.segments["fc2_w"]
+        ops.head_grad_sums(self.dout, self.vloss, self.vcorrect, self.fp.grad[o2:o2 + n2 + 1], self._vmetric_sums)
+        vo, vn = self.fp.segments["vhead_w"]
+        ops.head_grad_sums(self.vdhead, self.vloss, self.vcorrect, self.fp.grad[vo:vo + vn + 1], self._vmetric_sums)
+
+    def step(self, planes, targets, sym: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None,
+             rows: Optional[torch.Tensor] = None):
+        if self.use_graph:
+            raise RuntimeError(_PV_NO_GRAPH)
+        self.compute_grads(planes, targets, sym, weight, rows=rows)
+        self.apply_update()
+        return self._step_metrics()
+
+    def _step_metrics(self):
+        return self._metric_sums[0], self._metric_sums[1], self._vmetric_sums[0], self._vmetric_sums[1]
+
+    @torch.no_grad()
+    def predict(self, planes: torch.Tensor) -> torch.Tensor:
+        """Values (batch,) of the current weights, forward only."""
+        self.forward_trunk(planes, None, None, None)
+        self._value_forward()
+        v = self.fp.views
+        ops.value_out(self.h, v["fc2_w"].view(-1), v["fc2_b"], self.val)
+        return self.val.clone()
+
+    @torch.no_grad()
+    def evaluate(self, planes: torch.Tensor, targets):
+        """The four metric sums without an update (validation)."""
+        self._check_plain()
+        pi, z = _pv_targets(targets)
+        pl, pc = super().evaluate(planes, pi)  # leaves the trunk output in Y[-1]
+        self._value_forward()
+        v = self.fp.views
+        ops.value_out(self.h, v["fc2_w"].view(-1), v["fc2_b"], self.val)
+        zt = z.float()
+        return pl, pc, ((self.val - zt) ** 2).sum(), (torch.sign(self.val) == torch.sign(zt)).float().sum()
+
+    def policy_stats(self, planes, ref_probs=None):
+        raise ValueError(_PV_REFUSED)
+
+
 class _TorchTrainerBase:
     def _setup(self, net, batch, lr, decay, device, dtype, iterations, named, optimizer="sgd", momentum=0.0,
                nesterov=False):
@@ -1347,6 +1496,69 @@ class TorchValueTrainer(_TorchTrainerBase):
         return obj, err, (torch.sign(v) == torch.sign(z)).float()
 
 
+class TorchPolicyValueTrainer(_TorchTrainerBase):
+    """Autograd twin of HipPolicyValueTrainer: mean over the global batch of the policy CE (hard or soft
+    targets, TorchPolicyTrainer's expressions) + ``value_coef`` * (v - z)^2 on one trunk output."""
+
+    policy_loss = "ce"
+    ent_coef = 0.0
+    kl_coef = 0.0
+    collect_stats = False
+    collect_probs = False
+
+    def __init__(self, net, batch: int, lr: float = 0.003, decay: float = 0.0, device=None, dtype=torch.float32,
+                 iterations: int = 0, optimizer: str = "sgd", momentum: float = 0.0, nesterov: bool = False,
+                 value_coef: float = 1.0):
+        self.value_coef = float(value_coef)
+        named = _trunk_named(net.trunk) + [(n, getattr(net, n)) for n in (
+            "head_w", "head_b", "vhead_w", "vhead_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
+        self._setup(net, batch, lr, decay, device, dtype, iterations, named, optimizer, momentum, nesterov)
+
+    def _loss(self, planes, targets, sym, weight):
+        if self.policy_loss != "ce" or self.ent_coef or self.kl_coef or self.collect_stats or self.collect_probs:
+            raise ValueError(_PV_REFUSED)
+        pi, z = _pv_targets(targets)
+        soft = is_soft_target(pi)
+        if sym is not None:
+            if soft:
+                planes, _ = apply_symmetry(planes, None, sym, self.table)
+                pi = apply_symmetry_dist(pi, sym, self.table)
+            else:
+                planes, pi = apply_symmetry(planes, pi, sym, self.table)
+        logits, v = self.net.logits_value_torch(planes.to(self.dtype))
+        norm = planes.shape[0] * self.env.world_size
+        if soft:
+            per, correct, has = soft_target_loss(logits, pi)
+            w = has.to(per.dtype) if weight is None else has.to(per.dtype) * weight
+            pobj = (per * w).sum() / norm
+        else:
+            t = pi.long()
+            valid = t >= 0
+            correct = ((logits.argmax(1) == t) & valid).float()
+            w = valid.float() if weight is None else valid.float() * weight
+            lt = torch.log_softmax(logits, 1).gather(1, t.clamp_min(0).unsqueeze(1)).squeeze(1)
+            per = -torch.clamp(lt, min=math.log(1e-7), max=math.log(1 - 1e-7)) * valid
+            pobj = (-(lt * w)).sum() / norm
+        zt = z.to(v.dtype)
+        err = (v - zt) ** 2
+        vobj = (err if weight is None else err * weight).sum() / norm
+        self._vlast = (err.detach(), (torch.sign(v) == torch.sign(zt)).float().detach())
+        return pobj + self.value_coef * vobj, per, correct
+
+    def step(self, planes, targets, sym=None, weight=None, rows=None):
+        pl, pc = super().step(planes, targets, sym, weight, rows)
+        return pl, pc, self._vlast[0].sum(), self._vlast[1].sum()
+
+    @torch.no_grad()
+    def evaluate(self, planes, targets):
+        pl, pc = super().evaluate(planes, targets)
+        return pl, pc, self._vlast[0].sum(), self._vlast[1].sum()
+
+    @torch.no_grad()
+    def predict(self, planes) -> torch.Tensor:
+        return self.net.logits_value_torch(planes.to(self.dtype))[1]
+
+
 def make_value_trainer(net: ValueNet, batch: int, lr: float, decay: float = 0.0, backend: str = "auto",
                        device=None, **kw):
     dev = torch.device(device) if device is not None else agdist.env().device
@@ -1365,6 +1577,21 @@ def make_policy_trainer(net: PolicyNet, batch: int, lr: float, decay: float = 0.
     if backend == "hip":
         return HipPolicyTrainer(net, batch, lr, decay, device=dev, **kw)
     return TorchPolicyTrainer(net, batch, lr, decay, device=dev, **_torch_kw(kw))
+
+
+def make_policy_value_trainer(net, batch: int, lr: float, decay: float = 0.0, backend: str = "auto", device=None,
+                              **kw):
+    """The dual net's trainer: HipPolicyValueTrainer on a GPU, TorchPolicyValueTrainer otherwise
+    (``value_coef`` goes to both)."""
+    dev = torch.device(device) if device is not None else agdist.env().device
+    if backend == "auto":
+        backend = "hip" if dev.type == "cuda" else "torch"
+    if backend == "hip":
+        return HipPolicyValueTrainer(net, batch, lr, decay, device=dev, **kw)
+    tkw = _torch_kw(kw)
+    if "value_coef" in kw:
+        tkw["value_coef"] = kw["value_coef"]
+    return TorchPolicyValueTrainer(net, batch, lr, decay, device=dev, **tkw)
 
 
 def _torch_kw(kw: dict) -> dict:
