@@ -25,7 +25,12 @@
 //   identically for both operands so that each 32-lane half reads 8 distinct
 //   contiguous rows (conflict free).  Partial sums go to a per-split fp32 slab
 //   that conv_wgrad_reduce_kernel sums deterministically into the OIHW fp32
-//   gradient (and the bias gradient, accumulated by the tap-0 workgroups).
+//   gradient (and the bias gradient).  Staging addresses are stepped: a lane splits its
+//   first pixel into (board, row, column) once and then advances 32 pixels per stage by
+//   compares and adds of host-precomputed byte deltas (ConvWgradArgs::st_*), after the
+//   stage's MFMAs are issued; the DMA takes a scalar base and a 32-bit lane offset, the
+//   fragment reads immediate offsets.  The bias pixel sums are dealt out over the taps'
+//   workgroups: one 16-channel block per (tap, wave column) of the c0 == 0 column.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -375,6 +380,7 @@ void launch_conv_wgrad_direct(const ConvWgradArgs& a_in, int ksub, hipStream_t s
   a.divS = make_fastdiv((uint32_t)a.S);
   a.xcd_group = 0;
   a.nsplit = 1;
+  wgrad_fill_steps(a);
   if (!a.grad_w || !wgrad_direct_supported(a.Cout, a.Cin, a.cin_real, a.K))
     throw std::invalid_argument("conv_wgrad_direct: needs grad_w, Cout % 32 == 0 and a 48 / 32 c tile");
   const int wc = wgrad_direct_wc(a.Cin, a.cin_real);
@@ -455,6 +461,7 @@ void launch_conv_wgrad(const ConvWgradArgs& a_in, hipStream_t st) {
   a.divSS = make_fastdiv((uint32_t)(a.S * a.S));
   a.divS = make_fastdiv((uint32_t)a.S);
   a.xcd_group = 1;  // kernel-row workgroups of a split on one XCD (conv_wgrad_kernel)
+  wgrad_fill_steps(a);  // stepped staging addresses (wgrad_tile)
 #ifdef AGK_KERNEL_LAB
   if (a.variant == 5) {
     // one-kernel-row wgrad (conv_wgrad_row.hip), kernel lab: in the power-limited steady state it ran

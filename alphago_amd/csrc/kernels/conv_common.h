@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <utility>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -123,11 +125,46 @@ __device__ __forceinline__ void lgkm_fence(bf16x4 (&a)[N], bf16x4 (&b)[N]) {
 // vmcnt(0) before every such read while any LDS-DMA is outstanding (it cannot
 // tell the read from the DMA target), which would drain the ring; the caller
 // waits lgkmcnt itself (lgkm_fence below) before touching the results.
-__device__ __forceinline__ bf16x4 ds_read_tr16_asm(const char* p) {
+// f(std::integral_constant<int, 0>{}) ... f(<N - 1>): a loop whose index is a compile-time constant
+// inside the body (immediate operands of inline asm)
+template <class F, int... I>
+__device__ __forceinline__ void static_for_seq(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_seq(f, std::make_integer_sequence<int, N>{});
+}
+
+// OFF: the instruction's immediate byte offset (16-bit, unsigned) -- the reads of a stage share one
+// address register instead of one VALU add each.
+template <int OFF = 0>
+__device__ __forceinline__ bf16x4 ds_read_tr16_at(uint32_t lds_addr) {
+  static_assert(OFF >= 0 && OFF < 65536, "ds_read offset: 16-bit unsigned");
   bf16x4 v;
-  const uint32_t off = (uint32_t)(uintptr_t)(AG_LDS(p));
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(off));
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(lds_addr), "n"(OFF));
   return v;
+}
+template <int OFF = 0>
+__device__ __forceinline__ bf16x4 ds_read_tr16_asm(const char* p) {
+  return ds_read_tr16_at<OFF>((uint32_t)(uintptr_t)(AG_LDS(p)));
+}
+
+// 16-byte global -> LDS DMA from a wave-uniform base pointer plus a 32-bit per-lane byte offset
+// (global_load_lds_dwordx4 v, s[base:base+1]): no 64-bit vector pointer per piece.  This is the form
+// hipcc selects for `uniform base + zero-extended 32-bit lane offset`; it is the compiler's choice, not
+// a guarantee (pin the base with sgpr_ptr so that it is not folded into the lane's part).  Where it
+// does not match, the code is still correct and builds the 64-bit address with a v_lshl_add_u64.
+// pins a wave-uniform pointer to a scalar register pair (no instruction): the compiler cannot fold
+// it into the per-lane part of an address
+__device__ __forceinline__ const char* sgpr_ptr(const char* p) {
+  const uint64_t v = (uint64_t)(uintptr_t)p;
+  uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  asm("" : "+s"(lo), "+s"(hi));
+  return (const char*)(uintptr_t)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ void glds16_so(const void* sbase, uint32_t voff, void* lds_wave_base) {
+  glds16((const char*)sbase + (size_t)voff, lds_wave_base);
 }
 
 

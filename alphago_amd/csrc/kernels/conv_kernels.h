@@ -938,7 +938,7 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_pk_kernel(ConvFwdArg
 template <int WN, int WC, int NWC, int TAPS, int NWN = 2>
 __device__ __forceinline__ void wgrad_store(const ConvWgradArgs& a,
                                             const f32x4 (&acc)[TAPS][WN / (16 * NWN)][WC / (16 * NWC)],
-                                            const float (&dbs)[WN / (16 * NWN)], bool do_bias, int split, int t,
+                                            const float (&dbs)[WN / (16 * NWN)], unsigned bmask, int split, int t,
                                             int n0, int c0, int wn, int wc, int lane, int zero_split) {
   constexpr int NBn = WN / (16 * NWN), NBc = WC / (16 * NWC);
   const int nb0 = n0 + wn * (WN / NWN) + ((lane >> 4) << 2);
@@ -961,9 +961,10 @@ __device__ __forceinline__ void wgrad_store(const ConvWgradArgs& a,
             }
           }
         }
-    if (do_bias && a.grad_b) {
+    if (bmask && a.grad_b) {
 #pragma unroll
       for (int i = 0; i < NBn; ++i) {
+        if (!(bmask & (1u << i))) continue;
         float s = dbs[i];
         s += __shfl_xor(s, 16, 64);
         s += __shfl_xor(s, 32, 64);
@@ -995,9 +996,10 @@ __device__ __forceinline__ void wgrad_store(const ConvWgradArgs& a,
 #pragma unroll
         for (int r = 0; r < 4; ++r) out[(size_t)(nb0 + i * 16 + r) * a.Cin + cbase + j * 16] = 0.f;
   }
-  if (do_bias) {
+  if (bmask) {
 #pragma unroll
     for (int i = 0; i < NBn; ++i) {
+      if (!(bmask & (1u << i))) continue;
       float s = dbs[i];
       s += __shfl_xor(s, 16, 64);
       s += __shfl_xor(s, 32, 64);
@@ -1020,7 +1022,7 @@ __device__ __forceinline__ void wgrad_store(const ConvWgradArgs& a,
 // UP: unit pipelining inside a sub-step -- the x fragments of column unit u + 1 (a (tap, c block)
 // pair) are read while the MFMAs of unit u run, instead of every fragment before the first MFMA;
 // only the dz fragments and unit 0 stay exposed after the barrier.
-template <int WN, int WC, int KSUB, int NWC, int TAPS, int NS = 2, int NWN = 2, bool UP = false>
+template <int WN, int WC, int KSUB, int NWC, int TAPS, int NS = 2, int NWN = 2, bool UP = false, bool SPREAD = true>
 __device__ __forceinline__ void wgrad_tile(const ConvWgradArgs& a, int split, int ks_begin, int ks_end, int t,
                                            int tstep, int n0, int c0, int zero_split) {
   // NWN (n) x NWC (c) waves; NWC = 2 gives each wave a 96x96 tile at 192x192
@@ -1044,87 +1046,142 @@ __device__ __forceinline__ void wgrad_tile(const ConvWgradArgs& a, int split, in
   const int toff = (kh * a.HPi + kw) * a.Cin + c0;
   const int SS = a.S * a.S;
 
-  auto stage = [&](int ks, int buf) {
-    const int half = (lane & 1) * 8;
+  // ---- staging addresses.  A lane's pixel of consecutive sub-steps advances by 32, and stage() is
+  // called for consecutive stages of [ks_begin, ks_end), so the pixel's (board, row, column) is split by
+  // division ONCE here and then stepped: (sj, si) and the running byte offsets move by the host's
+  // per-step deltas (ConvWgradArgs::st_*), with one compare per wrap.  Offsets are 32-bit byte offsets
+  // from wave-uniform base pointers (n0 / the tap offset / the piece live in the scalar base).
+  // ONE: every wave stages only dz pieces or only x pieces (one scalar branch per stage instead of one
+  // per piece) and walks only that tensor: the walk's constants are wave-uniform selects.
+  // The step is split as whole boards + st_q rows + st_r columns (st_q, st_r < S), so one column wrap
+  // and one row wrap per step cover every board size, those below 64 points included.
+  // WALK false: the 5x5 tap-merged rows of the 160-wide n tile (162 VGPRs) have no room for the walk's
+  // state at the workgroups per CU their grid is sized for (wgrad_plan), so they keep the division per
+  // sub-step; everything else in this function is the same for them.
+  constexpr bool ONE = KSUB == 1 && (WN / 16) % IPW == 0 && NINSTR == NWAVES * IPW;
+  constexpr bool WALK = !(WN == 160 && TAPS == 5);
+  constexpr int NT = ONE ? 1 : 2;            // tensors a wave walks: [0] = dz (ONE: its own), [1] = x
+  constexpr int NDZW = ONE ? (WN / 16) / IPW : 0;  // ONE: waves below stage dz
+  const bool wdz = !ONE || wave < NDZW;
+  const int wHP[2] = {wdz ? a.HPo : a.HPi, a.HPi}, wP[2] = {wdz ? a.Po : a.offi, a.offi};
+  const int wC[2] = {wdz ? a.Cout : a.Cin, a.Cin};
+  const int wst[2] = {wdz ? a.dz_st : a.x_st, a.x_st}, wrow[2] = {wdz ? a.dz_row : a.x_row, a.x_row};
+  const int wbrd[2] = {wdz ? a.dz_brd : a.x_brd, a.x_brd};
+  const uint32_t half2 = (lane & 1) * 16;
+  // lanes past the last pixel: dz element 0 (a zero border), x pixel M - 1 (finite)
+  const uint32_t wtail[2] = {(wdz ? 0u : a.x_last) + half2, a.x_last + half2};
+  const char* const dzb = (const char*)(a.dz + n0);
+  const char* const xb = (const char*)(a.x + toff);
+  int px = ks_begin * (32 * KSUB) + (lane >> 1);
+  int sj, si;
+  uint32_t woff[NT];
+  auto locate = [&](int pm) {
+    const int b = fdiv(pm, a.divSS);
+    const int rem = pm - b * SS;
+    si = fdiv(rem, a.divS);
+    sj = rem - si * a.S;
+#pragma unroll
+    for (int k = 0; k < NT; ++k)
+      woff[k] = (uint32_t)(((b * wHP[k] + si + wP[k]) * wHP[k] + sj + wP[k]) * wC[k]) * 2u + half2;
+  };
+  if constexpr (WALK) locate(px);
+  auto advance = [&]() {
+    px += 32;
+    if constexpr (!WALK) return;
+    sj += a.st_r;
+    si += a.st_q;
+    const bool cw = sj >= a.S;  // next row
+    sj = cw ? sj - a.S : sj;
+    si = cw ? si + 1 : si;
+    const bool rw = si >= a.S;  // next board
+    si = rw ? si - a.S : si;
+#pragma unroll
+    for (int k = 0; k < NT; ++k) woff[k] += (uint32_t)(wst[k] + (cw ? wrow[k] : 0) + (rw ? wbrd[k] : 0));
+  };
+  // source of x piece xj: tap xj / XP, channel piece xj % XP.  ONE: each of the wave's IPW piece bases
+  // is pinned to a scalar register pair here, before the loop (sgpr_ptr), and the DMA takes it with the
+  // lane's 32-bit offset.  The general path pins the two tensor bases only and adds the piece's
+  // (wave-uniform) constant per piece: pinning every piece there would cost two v_readfirstlane per
+  // piece inside the loop.
+  const char* const dzp = sgpr_ptr(dzb);
+  const char* const xp = sgpr_ptr(xb);
+  auto xpiece = [&](int xj) { return xp + ((xj / XP) * tstep + (xj % XP) * 16) * 2; };
+  auto dzpiece = [&](int jj) { return dzp + jj * 32; };
+  const char* pb[IPW];  // ONE: this wave's piece bases
+  if constexpr (ONE) {
+#pragma unroll
+    for (int i = 0; i < IPW; ++i)
+      pb[i] = sgpr_ptr(wdz ? dzpiece(wave * IPW + i) : xpiece(wave * IPW + i - WN / 16));
+  }
+
+  // DEFER (one sub-step per stage): the caller advances after the stage's MFMAs are issued, so the
+  // address arithmetic runs in their shadow and not between the barrier and the fragment reads
+  constexpr bool DEFER = KSUB == 1;
+  auto stage = [&](int buf) {
     char* base = smem + buf * STAGE;
-    int dzr[KSUB], xr[KSUB];
 #pragma unroll
     for (int sub = 0; sub < KSUB; ++sub) {
-      const int px = (ks * KSUB + sub) * 32 + (lane >> 1);
-      const int pm = px < a.M ? px : a.M - 1;
-      const int b = fdiv(pm, a.divSS);
-      const int rem = pm - b * SS;
-      const int ii = fdiv(rem, a.divS);
-      const int jx = rem - ii * a.S;
-      dzr[sub] = px < a.M ? ((b * a.HPo + ii + a.Po) * a.HPo + jx + a.Po) * a.Cout : 0;  // 0 = zero border
-      xr[sub] = ((b * a.HPi + ii + a.offi) * a.HPi + jx + a.offi) * a.Cin + toff;
-    }
-    // dz pieces and x pieces in separate loops: a per-piece select between the
-    // two source tensors makes hipcc drain vmcnt(0) before the LDS reads that
-    // follow, which would turn the double buffer into a synchronous load
+      uint32_t o[NT];
+      if constexpr (!WALK) locate(px < a.M ? px : a.M - 1);
 #pragma unroll
-    for (int sub = 0; sub < KSUB; ++sub) {
-      const __bf16* dsrc = a.dz + dzr[sub] + n0 + half;
-      const __bf16* xsrc = a.x + xr[sub] + half;
+      for (int k = 0; k < NT; ++k) o[k] = px < a.M ? woff[k] : wtail[k];
+      if constexpr (!DEFER) advance();
+      // Debug build: every piece's element range is checked on the path the production build runs.
+      // The offsets are unsigned, so an offset that went below zero shows as one far above the extent.
+      if constexpr (ONE) {
+#pragma unroll
+        for (int i = 0; i < IPW; ++i) {
 #ifdef AGK_DEBUG
+          const int pc = wave * IPW + i, xj = pc - WN / 16;
+          const long long e =
+              (long long)(o[0] >> 1) + (wdz ? n0 + pc * 16 : toff + (xj / XP) * tstep + (xj % XP) * 16);
+          if (!AGK_DCHECK(e + 8 <= (wdz ? a.dz_elems : a.x_elems), wdz ? DBG_WG_DZ : DBG_WG_X)) {
+            glds16(wdz ? a.dz : a.x, base + (wave * IPW + i) * 1024);
+            continue;
+          }
+#endif
+          glds16_so(pb[i], o[0], base + (wave * IPW + i) * 1024);
+        }
+        continue;
+      }
+      // dz pieces and x pieces in separate loops: a per-piece select between the
+      // two source tensors makes hipcc drain vmcnt(0) before the LDS reads that
+      // follow, which would turn the double buffer into a synchronous load
 #pragma unroll
       for (int i = 0; i < IPW; ++i) {
         const int jj = wave * IPW + i - sub * (NINSTR / KSUB);
         if (jj >= 0 && jj < WN / 16) {
-          const long long o = (long long)dzr[sub] + n0 + half + jj * 16;
-          const bool ok = AGK_DCHECK(o >= 0 && o + 8 <= a.dz_elems, DBG_WG_DZ);
-          glds16(ok ? dsrc + jj * 16 : a.dz, base + sub * SUB + jj * 1024);
-        }
-        if constexpr (NS > 2) {  // see the release loop below
-          if (jj >= NINSTR / KSUB) glds16(dsrc, base + sub * SUB);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < IPW; ++i) {
-        const int jj = wave * IPW + i - sub * (NINSTR / KSUB);
-        if (jj >= WN / 16 && jj < NINSTR / KSUB) {
-          const int xj = jj - WN / 16;  // tap xj / XP, channel piece xj % XP
-          const long long o = (long long)xr[sub] + half + (xj / XP) * tstep + (xj % XP) * 16;
-          const bool ok = AGK_DCHECK(o >= 0 && o + 8 <= a.x_elems, DBG_WG_X);
-          glds16(ok ? xsrc + (xj / XP) * tstep + (xj % XP) * 16 : a.x, base + sub * SUB + jj * 1024);
-        }
-      }
-#else
-      if constexpr (KSUB == 1 && (WN / 16) % IPW == 0 && NINSTR == NWAVES * IPW) {
-        // every wave stages only dz pieces or only x pieces: one scalar branch per stage instead of
-        // one per piece
-        if (wave < (WN / 16) / IPW) {
-#pragma unroll
-          for (int i = 0; i < IPW; ++i) glds16(dsrc + (wave * IPW + i) * 16, base + (wave * IPW + i) * 1024);
-        } else {
-#pragma unroll
-          for (int i = 0; i < IPW; ++i) {
-            const int xj = wave * IPW + i - WN / 16;  // tap xj / XP, channel piece xj % XP
-            glds16(xsrc + (xj / XP) * tstep + (xj % XP) * 16, base + (WN / 16 + xj) * 1024);
+#ifdef AGK_DEBUG
+          const long long e = (long long)(o[0] >> 1) + n0 + jj * 16;
+          if (!AGK_DCHECK(e + 8 <= a.dz_elems, DBG_WG_DZ)) {
+            glds16(a.dz, base + sub * SUB + jj * 1024);
+            continue;
           }
+#endif
+          glds16_so(dzpiece(jj), o[0], base + sub * SUB + jj * 1024);
         }
-        continue;
-      }
-#pragma unroll
-      for (int i = 0; i < IPW; ++i) {
-        const int jj = wave * IPW + i - sub * (NINSTR / KSUB);
-        if (jj >= 0 && jj < WN / 16) glds16(dsrc + jj * 16, base + sub * SUB + jj * 1024);
         // LDS ring with unequal piece counts: a wave past the last piece re-issues dz piece 0 (same
         // bytes to the same LDS address), so every wave has exactly IPW DMAs per stage -- the
         // vmcnt unit ring_wait counts in
         if constexpr (NS > 2) {
-          if (jj >= NINSTR / KSUB) glds16(dsrc, base + sub * SUB);
+          if (jj >= NINSTR / KSUB) glds16_so(dzpiece(0), o[0], base + sub * SUB);
         }
       }
 #pragma unroll
       for (int i = 0; i < IPW; ++i) {
         const int jj = wave * IPW + i - sub * (NINSTR / KSUB);
         if (jj >= WN / 16 && jj < NINSTR / KSUB) {
-          const int xj = jj - WN / 16;  // tap xj / XP, channel piece xj % XP
-          glds16(xsrc + (xj / XP) * tstep + (xj % XP) * 16, base + sub * SUB + jj * 1024);
+          const int xj = jj - WN / 16;
+#ifdef AGK_DEBUG
+          const long long e = (long long)(o[NT - 1] >> 1) + toff + (xj / XP) * tstep + (xj % XP) * 16;
+          if (!AGK_DCHECK(e + 8 <= a.x_elems, DBG_WG_X)) {
+            glds16(a.x, base + sub * SUB + jj * 1024);
+            continue;
+          }
+#endif
+          glds16_so(xpiece(xj), o[NT - 1], base + sub * SUB + jj * 1024);
         }
       }
-#endif
     }
   };
 
@@ -1138,15 +1195,49 @@ __device__ __forceinline__ void wgrad_tile(const ConvWgradArgs& a, int split, in
   float dbs[NBn];
 #pragma unroll
   for (int i = 0; i < NBn; ++i) dbs[i] = 0.f;
-  const bool do_bias = (t == 0) && (c0 == 0) && (wc == 0);
+  // bias partials (the pixel sums of dz).  Every wave with the same wn holds the same dz fragments in
+  // the same lanes, in every tap's workgroup of the c0 == 0 column, so the NBn 16-channel blocks are
+  // dealt out: block i goes to (tap group, wc) slot i % slots -- 36 slots for 6 blocks in the 3x3
+  // 192 x 192 kernel, 15 for 3 in the first layer's rows -- and no wave carries more than one where the
+  // slots suffice.  The per-lane sum is the same whoever computes it.  bmask bit i: this wave sums block i.
+  // SPREAD false (PAIR, whose odd tap covers two splits): all blocks on the wc == 0 waves of tap 0.
+  unsigned bmask = 0;
+  if (c0 == 0) {
+    if constexpr (SPREAD) {
+      const int slots = (a.T / TAPS) * NWC, slot = (t / TAPS) * NWC + wc;
+#pragma unroll
+      for (int i = 0; i < NBn; ++i) bmask |= (i % slots == slot ? 1u : 0u) << i;
+    } else if (t == 0 && wc == 0) {
+      bmask = (1u << NBn) - 1u;
+    }
+  }
+  bmask = __builtin_amdgcn_readfirstlane(bmask);
+  // each block's sum under its own wave-uniform branch: eight elements in order, then the running
+  // sum (separate chains per block are never packed into v_pk_add_f32)
+  auto bias_add = [&](const bf16x8 (&af)[NBn]) {
+    if (bmask == 0) return;
+#pragma unroll
+    for (int i = 0; i < NBn; ++i)
+      if (bmask & (1u << i)) {
+        float s = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s += (float)af[i][e];
+        dbs[i] += s;
+      }
+  };
 
-  // transposed-read addresses: group g = lane>>4, row q = (lane&15)>>2, col 4p, p = lane&3
+  // transposed-read addresses: group g = lane>>4, row q = (lane&15)>>2, col 4p, p = lane&3; the lane
+  // reads rows 4g..4g+3 at tr0 and rows 16+4g..16+4g+3 512 bytes on.  One dz and one x address register
+  // per wave (the buffer's offset folded in per stage); block, tap and sub-step are immediate offsets.
   const int g = lane >> 4;
   const int q = (lane & 15) >> 2;
   const int p = lane & 3;
-  const int tr0 = (4 * g + q) * 32 + p * 8;         // rows 4g..4g+3
-  const int tr1 = (16 + 4 * g + q) * 32 + p * 8;    // rows 16+4g..16+4g+3
+  const uint32_t tr0 = (uint32_t)(uintptr_t)AG_LDS(smem) + (4 * g + q) * 32 + p * 8;
+  const uint32_t fr_dz = tr0 + wn * NBn * 1024;
+  const uint32_t fr_x = tr0 + DZ_BYTES + wc * NBc * 1024;
+  constexpr int TRH = 16 * 32;  // second row group
   constexpr int NF = NBn + TAPS * NBc;  // fragments read per sub-step
+  static_assert((KSUB - 1) * SUB + (TAPS * XP) * 1024 + TRH < 65536, "fragment reads: 16-bit immediate offsets");
 
   constexpr bool RING = NS > 2;
   static_assert(!RING || KSUB == 1, "ring: one sub-step per stage");
@@ -1154,47 +1245,56 @@ __device__ __forceinline__ void wgrad_tile(const ConvWgradArgs& a, int split, in
   if constexpr (RING) {
 #pragma unroll
     for (int s = 0; s < NS - 1; ++s)
-      if (ks_begin + s < ks_end) stage(ks_begin + s, s);
+      if (ks_begin + s < ks_end) {
+        stage(s);
+        if constexpr (DEFER) advance();
+      }
   } else if (ks_begin < ks_end) {
-    stage(ks_begin, 0);
+    stage(0);
+    if constexpr (DEFER) advance();
     wait_vmcnt0();
     __syncthreads();
   }
   for (int ks = ks_begin; ks < ks_end; ++ks) {
     int cur = (ks - ks_begin) & 1;
+    bool staged = false;
     if constexpr (RING) {
       const int later = (ks_end - 1 - ks) < (NS - 2) ? (ks_end - 1 - ks) : (NS - 2);
       ring_wait<IPW, (NS > 2 ? NS - 2 : 0)>(later);
       __syncthreads();  // stage ks visible to every wave; the slot read last step is free
       cur = (ks - ks_begin) % NS;
-      if (ks + NS - 1 < ks_end) stage(ks + NS - 1, (ks - ks_begin + NS - 1) % NS);
-    } else if (ks + 1 < ks_end) {
-      stage(ks + 1, cur ^ 1);
-    }
-#pragma unroll
-    for (int sub = 0; sub < KSUB; ++sub) {
-      const char* base = smem + cur * STAGE + sub * SUB;
-      bf16x4 tl[NF], th[NF];
-#pragma unroll
-      for (int i = 0; i < NBn; ++i) {
-        const char* cb = base + (wn * NBn + i) * 1024;
-        tl[i] = ds_read_tr16_asm(cb + tr0);
-        th[i] = ds_read_tr16_asm(cb + tr1);
+      if (ks + NS - 1 < ks_end) {
+        stage((ks - ks_begin + NS - 1) % NS);
+        staged = true;
       }
+    } else if (ks + 1 < ks_end) {
+      stage(cur ^ 1);
+      staged = true;
+    }
+    const uint32_t cdz = fr_dz + cur * STAGE, cx = fr_x + cur * STAGE;
+    static_for<KSUB>([&](auto sub_c) {
+      constexpr int sub = decltype(sub_c)::value;
+      bf16x4 tl[NF], th[NF];
+      static_for<NBn>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        tl[i] = ds_read_tr16_at<sub * SUB + i * 1024>(cdz);
+        th[i] = ds_read_tr16_at<sub * SUB + i * 1024 + TRH>(cdz);
+      });
       if constexpr (UP) {
         constexpr int NU = TAPS * NBc;  // column units u = tp * NBc + j
-        auto read_unit = [&](int u) {
-          const char* cb = base + DZ_BYTES + ((u / NBc) * XP + wc * NBc + (u % NBc)) * 1024;
-          tl[NBn + u] = ds_read_tr16_asm(cb + tr0);
-          th[NBn + u] = ds_read_tr16_asm(cb + tr1);
+        auto read_unit = [&](auto uc) {
+          constexpr int u = decltype(uc)::value;
+          constexpr int xo = sub * SUB + ((u / NBc) * XP + (u % NBc)) * 1024;
+          tl[NBn + u] = ds_read_tr16_at<xo>(cx);
+          th[NBn + u] = ds_read_tr16_at<xo + TRH>(cx);
         };
-        read_unit(0);
+        read_unit(std::integral_constant<int, 0>{});
         bf16x8 af[NBn];
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-          if (u + 1 < NU) read_unit(u + 1);
+        static_for<NU>([&](auto uc) {
+          constexpr int u = decltype(uc)::value;
+          if constexpr (u + 1 < NU) read_unit(std::integral_constant<int, u + 1>{});
           // all but the two reads of unit u + 1 have returned (LDS reads complete in order)
-          if (u == 0) {
+          if constexpr (u == 0) {
 #pragma unroll
             for (int i = 0; i < NBn; ++i) {
               if (NU > 1) lgkm_wait_pair<2>(tl[i], th[i]);
@@ -1208,51 +1308,36 @@ __device__ __forceinline__ void wgrad_tile(const ConvWgradArgs& a, int split, in
                                    th[NBn + u][0], th[NBn + u][1], th[NBn + u][2], th[NBn + u][3]};
 #pragma unroll
           for (int i = 0; i < NBn; ++i) acc[u / NBc][i][u % NBc] = mfma16x16x32(af[i], bu, acc[u / NBc][i][u % NBc]);
-        }
-        if (do_bias) {
-#pragma unroll
-          for (int i = 0; i < NBn; ++i) {
-            float sb = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) sb += (float)af[i][e];
-            dbs[i] += sb;
-          }
-        }
-        continue;
-      }
-#pragma unroll
-      for (int tp = 0; tp < TAPS; ++tp)
-#pragma unroll
-        for (int j = 0; j < NBc; ++j) {
-          const char* cb = base + DZ_BYTES + (tp * XP + wc * NBc + j) * 1024;
-          tl[NBn + tp * NBc + j] = ds_read_tr16_asm(cb + tr0);
-          th[NBn + tp * NBc + j] = ds_read_tr16_asm(cb + tr1);
-        }
-      lgkm_fence<NF>(tl, th);
-      bf16x8 af[NBn], bfm[TAPS * NBc];
-#pragma unroll
-      for (int i = 0; i < NBn; ++i)
-        af[i] = bf16x8{tl[i][0], tl[i][1], tl[i][2], tl[i][3], th[i][0], th[i][1], th[i][2], th[i][3]};
-#pragma unroll
-      for (int j = 0; j < TAPS * NBc; ++j)
-        bfm[j] = bf16x8{tl[NBn + j][0], tl[NBn + j][1], tl[NBn + j][2], tl[NBn + j][3],
-                        th[NBn + j][0], th[NBn + j][1], th[NBn + j][2], th[NBn + j][3]};
-#pragma unroll
-      for (int tp = 0; tp < TAPS; ++tp)
+        });
+        bias_add(af);
+      } else {
+        static_for<TAPS * NBc>([&](auto uc) {
+          constexpr int u = decltype(uc)::value;  // tp * NBc + j
+          constexpr int xo = sub * SUB + ((u / NBc) * XP + (u % NBc)) * 1024;
+          tl[NBn + u] = ds_read_tr16_at<xo>(cx);
+          th[NBn + u] = ds_read_tr16_at<xo + TRH>(cx);
+        });
+        lgkm_fence<NF>(tl, th);
+        bf16x8 af[NBn], bfm[TAPS * NBc];
 #pragma unroll
         for (int i = 0; i < NBn; ++i)
+          af[i] = bf16x8{tl[i][0], tl[i][1], tl[i][2], tl[i][3], th[i][0], th[i][1], th[i][2], th[i][3]};
 #pragma unroll
-          for (int j = 0; j < NBc; ++j)
-            acc[tp][i][j] = mfma16x16x32(af[i], bfm[tp * NBc + j], acc[tp][i][j]);
-      if (do_bias) {
+        for (int j = 0; j < TAPS * NBc; ++j)
+          bfm[j] = bf16x8{tl[NBn + j][0], tl[NBn + j][1], tl[NBn + j][2], tl[NBn + j][3],
+                          th[NBn + j][0], th[NBn + j][1], th[NBn + j][2], th[NBn + j][3]};
 #pragma unroll
-        for (int i = 0; i < NBn; ++i) {
-          float s = 0.f;
+        for (int tp = 0; tp < TAPS; ++tp)
 #pragma unroll
-          for (int e = 0; e < 8; ++e) s += (float)af[i][e];
-          dbs[i] += s;
-        }
+          for (int i = 0; i < NBn; ++i)
+#pragma unroll
+            for (int j = 0; j < NBc; ++j)
+              acc[tp][i][j] = mfma16x16x32(af[i], bfm[tp * NBc + j], acc[tp][i][j]);
+        bias_add(af);
       }
+    });
+    if constexpr (DEFER) {
+      if (staged) advance();
     }
     if constexpr (!RING) {
       wait_vmcnt0();
@@ -1260,7 +1345,7 @@ __device__ __forceinline__ void wgrad_tile(const ConvWgradArgs& a, int split, in
     }
   }
 
-  wgrad_store<WN, WC, NWC, TAPS, NWN>(a, acc, dbs, do_bias, split, t, n0, c0, wn, wc, lane, zero_split);
+  wgrad_store<WN, WC, NWC, TAPS, NWN>(a, acc, dbs, bmask, split, t, n0, c0, wn, wc, lane, zero_split);
 }
 
 // LINE staging (wgrad variants 6 and 7): every DMA piece moves 8 whole 128-byte pixel lines (one
@@ -1460,7 +1545,7 @@ __device__ __forceinline__ void wgrad_tile_line(const ConvWgradArgs& a, int spli
       wait_vmcnt0();
       __syncthreads();
     }
-    wgrad_store<WN, WC, NWC, TAPS>(a, acc, dbs, do_bias, split, t, n0, c0, wn, wc, lane, zero_split);
+    wgrad_store<WN, WC, NWC, TAPS>(a, acc, dbs, do_bias ? (1u << NBn) - 1u : 0u, split, t, n0, c0, wn, wc, lane, zero_split);
     return;
   }
   if (ks_begin < ks_end) {
@@ -1516,7 +1601,7 @@ __device__ __forceinline__ void wgrad_tile_line(const ConvWgradArgs& a, int spli
     wait_vmcnt0();
     __syncthreads();
   }
-  wgrad_store<WN, WC, NWC, TAPS>(a, acc, dbs, do_bias, split, t, n0, c0, wn, wc, lane, zero_split);
+  wgrad_store<WN, WC, NWC, TAPS>(a, acc, dbs, do_bias ? (1u << NBn) - 1u : 0u, split, t, n0, c0, wn, wc, lane, zero_split);
 }
 
 // LINE && !PAIR: two 8-wave workgroups per CU like the production per-tap kernel (<= 128 VGPRs)
@@ -1562,7 +1647,7 @@ __global__ __launch_bounds__(64 * NWN * NWC, (MW > 0 ? MW : (LINE && !PAIR) ? 4 
       int ke = kb + 2 * a.ksteps_per_split;
       if (ke > nks_total) ke = nks_total;
       if constexpr (LINE) wgrad_tile_line<WN, WC, KSUB, NWC, 1>(a, s0, kb, ke, t, 0, n0, c0, s0 + 1 < a.nsplit ? s0 + 1 : -1);
-      else wgrad_tile<WN, WC, KSUB, NWC, 1>(a, s0, kb, ke, t, 0, n0, c0, s0 + 1 < a.nsplit ? s0 + 1 : -1);
+      else wgrad_tile<WN, WC, KSUB, NWC, 1, 2, 2, false, false>(a, s0, kb, ke, t, 0, n0, c0, s0 + 1 < a.nsplit ? s0 + 1 : -1);
       return;
     }
   }
@@ -1575,7 +1660,7 @@ __global__ __launch_bounds__(64 * NWN * NWC, (MW > 0 ? MW : (LINE && !PAIR) ? 4 
     tstep = ((t1 / a.K - t / a.K) * a.HPi + (t1 % a.K - t % a.K)) * a.Cin;
   }
   if constexpr (LINE) wgrad_tile_line<WN, WC, KSUB, NWC, TAPS, ILVW>(a, split, ks_begin, ks_end, t, tstep, n0, c0, -1);
-  else wgrad_tile<WN, WC, KSUB, NWC, TAPS, NS, NWN, UP>(a, split, ks_begin, ks_end, t, tstep, n0, c0, -1);
+  else wgrad_tile<WN, WC, KSUB, NWC, TAPS, NS, NWN, UP, !PAIR>(a, split, ks_begin, ks_end, t, tstep, n0, c0, -1);
 }
 
 constexpr int kWgradKsub = 1;

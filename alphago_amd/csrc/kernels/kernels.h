@@ -58,7 +58,37 @@ struct ConvWgradArgs {
   float* grad_b;
   float scale, beta;
   int cout_real;
+  // stepped staging addresses (filled by the launcher, wgrad_fill_steps): a lane's pixel advances by 32
+  // per sub-step = whole boards + st_q rows + st_r columns (st_q, st_r < S, so at most one column wrap
+  // and one row wrap per step at any board size); *_st / *_row / *_brd are the byte deltas of that step,
+  // of a column wrap (next row) and of a row wrap (next board) in each padded tensor.  x_last: byte
+  // offset of pixel M - 1 in x (tap (0, 0)), the source of lanes past the last pixel.
+  int st_q, st_r;
+  int dz_st, dz_row, dz_brd;
+  int x_st, x_row, x_brd;
+  unsigned x_last;
 };
+
+// The staging offsets are 32-bit byte offsets from a scalar base, so both tensors must stay below 4 GiB.
+// The guard is the op wrappers' check (conv_wgrad_impl, conv_wgrad_direct: numel < 2^31, "tensor too
+// large for int32 offsets"), the limit the int32 element offsets had before; nothing is checked here.
+inline void wgrad_fill_steps(ConvWgradArgs& a) {
+  const int S = a.S;
+  const int st_b = 32 / (S * S);
+  a.st_q = (32 % (S * S)) / S;
+  a.st_r = 32 % S;
+  a.dz_st = ((st_b * a.HPo + a.st_q) * a.HPo + a.st_r) * a.Cout * 2;
+  a.dz_row = (a.HPo - S) * a.Cout * 2;
+  a.dz_brd = (a.HPo - S) * a.HPo * a.Cout * 2;
+  a.x_st = ((st_b * a.HPi + a.st_q) * a.HPi + a.st_r) * a.Cin * 2;
+  a.x_row = (a.HPi - S) * a.Cin * 2;
+  a.x_brd = (a.HPi - S) * a.HPi * a.Cin * 2;
+  a.x_last = 0;
+  if (a.M > 0) {
+    const int m = a.M - 1, b = m / (S * S), rem = m % (S * S), ii = rem / S, jx = rem % S;
+    a.x_last = (unsigned)(((b * a.HPi + ii + a.offi) * a.HPi + jx + a.offi) * a.Cin) * 2u;
+  }
+}
 
 // fp8 wgrad (conv_wgrad_fp8.hip): e5m2 dZ x e4m3 X on the block-scaled MFMA, same slab as the bf16 wgrad
 struct ConvWgradFp8Args {
