@@ -90,7 +90,11 @@ def _init_model(argv):
     p.add_argument("--filters", type=int, default=None)
     p.add_argument("--layers", type=int, default=12)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--residual", action="store_true",
+                   help="pv only: a residual trunk (stem + two-layer blocks with a skip connection; --layers odd)")
     a = p.parse_args(argv)
+    if a.residual and a.kind != "pv":
+        p.error("--residual needs the dual net (init-model pv): a Keras Sequential cannot express a skip connection")
     import torch
 
     torch.manual_seed(a.seed)
@@ -99,7 +103,12 @@ def _init_model(argv):
         m = CNNPolicy(feats, board=a.board, filters_per_layer=a.filters or 128, layers=a.layers, device="cpu")
     elif a.kind == "pv":
         feats = a.features.split(",") if a.features else VALUE_FEATURES
-        m = CNNPolicyValue(feats, board=a.board, filters_per_layer=a.filters or 192, layers=a.layers, device="cpu")
+        kw = {"residual": 1} if a.residual else {}
+        try:
+            m = CNNPolicyValue(feats, board=a.board, filters_per_layer=a.filters or 192, layers=a.layers,
+                               device="cpu", **kw)
+        except ValueError as e:  # e.g. an even depth for a residual trunk
+            p.error(str(e))
     else:
         feats = a.features.split(",") if a.features else VALUE_FEATURES
         m = CNNValue(feats, board=a.board, filters_per_layer=a.filters or 152, layers=a.layers, device="cpu")

@@ -148,6 +148,21 @@ void launch_conv_fwd(const ConvFwdArgs& a_in, int mode, hipStream_t st) {
   ConvFwdArgs a = a_in;
   a.divSS = make_fastdiv((uint32_t)(a.S * a.S));
   a.divS = make_fastdiv((uint32_t)a.S);
+  if (a.res) {
+    // residual block: the skip operand selects the MODE_RES instantiations of the same kernels (a
+    // compile-time flag -- the kernels without it are untouched)
+    if (mode != MODE_BIAS_RELU && mode != MODE_MASKBITS)
+      throw std::invalid_argument("conv_fwd: a skip operand (res) goes with modes 0 (bias + ReLU) and 3 (bitmask dgrad)");
+    if (a.y_bf8) throw std::invalid_argument("conv_fwd: a skip operand (res) cannot be combined with the e5m2 copy");
+#ifdef AGK_KERNEL_LAB
+    throw std::invalid_argument("conv_fwd: the kernel-lab library has no skip operand (res)");
+#else
+    if (a.tile == 40) launch_conv_ws(a, mode | MODE_RES, 0, st);
+    else if (mode == MODE_BIAS_RELU) launch_fwd_mode<MODE_BIAS_RELU | MODE_RES>(a, st);
+    else launch_fwd_mode<MODE_MASKBITS | MODE_RES>(a, st);
+    return;
+#endif
+  }
   if (a.tile == 40) {  // weight-stationary small-batch kernel (conv_ws.hip)
     launch_conv_ws(a, mode, 0, st);
     return;

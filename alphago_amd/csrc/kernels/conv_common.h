@@ -174,8 +174,22 @@ __device__ __forceinline__ void glds16_so(const void* sbase, uint32_t voff, void
 // per-element branches, so the loads overlap instead of forming 24
 // load -> wait -> store round trips; the kernels call it a few K-steps before
 // the end of the main loop so the mask read hides under the last MFMAs.
+// MODE & MODE_RES (residual blocks): the skip operand a.res is added in fp32 before the ReLU / the mask.
+// It is loaded inside store() in groups of RG pixel rows (RG x NB x 8 bytes per lane, at most 36 VGPRs; RG below),
+// every load of a group issued before the group's first store: a preloaded NB x MB tile would cost what
+// MODE_MASK's mk[][] costs (2 NB MB VGPRs on top of the accumulators), while one row at a time is one
+// memory round trip per row (the compiler cannot move a row's loads above the previous row's stores: y
+// and res might alias for all it knows).  The pixel indices are clamped, so a row past M loads in range
+// and is not stored.  Interior pixels only, so the operand's border is never read.
 template <int NB, int MB, int MODE>
 struct ConvEpilogue {
+  static constexpr int BASE = MODE & 3;
+  static constexpr bool RES = (MODE & MODE_RES) != 0;
+  static_assert(!RES || BASE == MODE_BIAS_RELU || BASE == MODE_MASKBITS, "skip operand: bias + ReLU or bitmask dgrad");
+  static constexpr bool BF8 = BASE == MODE_MASKBITS && !RES;  // the e5m2 copy: not with a skip operand
+  // rows per skip-load group: 3 at NB = 6 on the 96-pixel wave tiles (MB = 6), whose accumulators leave the
+  // registers; the smaller tiles keep their accumulators next to 96 AGPRs and take one row at a time
+  static constexpr int RG = !(RES && MB >= 6) ? 1 : (18 / NB < 1 ? 1 : (18 / NB > MB ? MB : 18 / NB));
   int ooff[MB];
   int pix[MB];
   f32x4 bb[NB];
@@ -202,15 +216,15 @@ struct ConvEpilogue {
       pix[j] = (b * a.HPo + ii + a.Po) * a.HPo + jj + a.Po;
       ooff[j] = pix[j] * a.Cout + nbase;
     }
-    if constexpr (MODE == MODE_BIAS_RELU) {
+    if constexpr (BASE == MODE_BIAS_RELU) {
 #pragma unroll
       for (int i = 0; i < NB; ++i) bb[i] = *(const f32x4*)(a.bias + nbase + i * 16);
-    } else if constexpr (MODE == MODE_MASK) {
+    } else if constexpr (BASE == MODE_MASK) {
 #pragma unroll
       for (int j = 0; j < MB; ++j)
 #pragma unroll
         for (int i = 0; i < NB; ++i) mk[i][j] = *(const bf16x4*)(a.mask + ooff[j] + i * 16);
-    } else if constexpr (MODE == MODE_MASKBITS) {
+    } else if constexpr (BASE == MODE_MASKBITS) {
 #pragma unroll
       for (int j = 0; j < MB; ++j) mw[j] = a.mbits_in[(size_t)pix[j] * mwords + mslot];
     }
@@ -218,25 +232,45 @@ struct ConvEpilogue {
 
   __device__ __forceinline__ void store(const ConvFwdArgs& a, const f32x4 (&acc)[NB][MB], int mrow) const {
     float gmax = 0.f;  // MODE_MASKBITS with an e5m2 copy: max |dx| of the lane
-    const float gsc = (MODE == MODE_MASKBITS && a.y_bf8) ? *a.bf8_scale : 0.f;
+    const float gsc = (BF8 && a.y_bf8) ? *a.bf8_scale : 0.f;
+    bf16x4 rs[RG][RES ? NB : 1];
 #pragma unroll
     for (int j = 0; j < MB; ++j) {
+      if constexpr (RES) {
+        if (j % RG == 0) {
+#pragma unroll
+          for (int jg = 0; jg < RG; ++jg)
+#pragma unroll
+            for (int i = 0; i < NB; ++i)
+              if (j + jg < MB) rs[jg][i] = *(const bf16x4*)(a.res + ooff[j + jg < MB ? j + jg : j] + i * 16);
+        }
+      }
       if (mrow + j * 16 >= a.M) continue;
       uint32_t bits = 0u;
 #pragma unroll
       for (int i = 0; i < NB; ++i) {
         f32x4 v = acc[i][j];
-        if constexpr (MODE == MODE_BIAS_RELU) {
+        if constexpr (RES) {  // acc + bias + res (forward), acc + res (dgrad)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            v[r] = (BASE == MODE_BIAS_RELU ? v[r] + bb[i][r] : v[r]) + (float)rs[j % RG][i][r];
+        }
+        if constexpr (BASE == MODE_BIAS_RELU && RES) {
+          v[0] = fmaxf(v[0], 0.f);
+          v[1] = fmaxf(v[1], 0.f);
+          v[2] = fmaxf(v[2], 0.f);
+          v[3] = fmaxf(v[3], 0.f);
+        } else if constexpr (BASE == MODE_BIAS_RELU) {
           v[0] = fmaxf(v[0] + bb[i][0], 0.f);
           v[1] = fmaxf(v[1] + bb[i][1], 0.f);
           v[2] = fmaxf(v[2] + bb[i][2], 0.f);
           v[3] = fmaxf(v[3] + bb[i][3], 0.f);
-        } else if constexpr (MODE == MODE_MASK) {
+        } else if constexpr (BASE == MODE_MASK) {
           v[0] = (float)mk[i][j][0] > 0.f ? v[0] : 0.f;
           v[1] = (float)mk[i][j][1] > 0.f ? v[1] : 0.f;
           v[2] = (float)mk[i][j][2] > 0.f ? v[2] : 0.f;
           v[3] = (float)mk[i][j][3] > 0.f ? v[3] : 0.f;
-        } else if constexpr (MODE == MODE_MASKBITS) {
+        } else if constexpr (BASE == MODE_MASKBITS) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = ((mw[j] >> (4 * i + r)) & 1u) ? v[r] : 0.f;
         }
@@ -245,7 +279,7 @@ struct ConvEpilogue {
         o[1] = (__bf16)v[1];
         o[2] = (__bf16)v[2];
         o[3] = (__bf16)v[3];
-        if constexpr (MODE == MODE_BIAS_RELU) {
+        if constexpr (BASE == MODE_BIAS_RELU) {
           // the bit records what the bf16 value the dgrad would re-read says: y > 0
 #pragma unroll
           for (int r = 0; r < 4; ++r) bits |= ((float)o[r] > 0.f ? 1u : 0u) << (4 * i + r);
@@ -256,7 +290,7 @@ struct ConvEpilogue {
 #else
         *(bf16x4*)(a.y + ooff[j] + i * 16) = o;
 #endif
-        if constexpr (MODE == MODE_MASKBITS) {
+        if constexpr (BF8) {
           if (a.y_bf8) {  // wave-uniform
             float sv[4];
 #pragma unroll
@@ -270,10 +304,10 @@ struct ConvEpilogue {
           }
         }
       }
-      if constexpr (MODE == MODE_BIAS_RELU)
+      if constexpr (BASE == MODE_BIAS_RELU)
         if (a.mbits_out) a.mbits_out[(size_t)pix[j] * mwords + mslot] = bits;
     }
-    if constexpr (MODE == MODE_MASKBITS) {
+    if constexpr (BF8) {
       if (a.y_bf8 && a.bf8_amax) {
         gmax = wave_max(gmax);
         if ((threadIdx.x & 63) == 0 && gmax > 0.f) atomicMax(a.bf8_amax + (blockIdx.x & 63), __float_as_uint(gmax));
@@ -299,6 +333,9 @@ __device__ __forceinline__ void conv_store_tile(const ConvFwdArgs& a, const f32x
 // words blockIdx.y*8 + wn*4 + h (even g) and + 2 (odd g), bit 8 i + 4 (g / 2) + r.
 template <int NB, int MB, int MODE>
 struct ConvEpilogue32 {
+  static constexpr int BASE = MODE & 3;
+  static constexpr bool RES = (MODE & MODE_RES) != 0;  // skip operand, loaded per 4-channel group in store()
+  static_assert(!RES || BASE == MODE_BIAS_RELU || BASE == MODE_MASKBITS, "skip operand: bias + ReLU or bitmask dgrad");
   int ooff[MB];
   int pix[MB];
   f32x4 bb[NB][4];
@@ -322,19 +359,19 @@ struct ConvEpilogue32 {
       pix[j] = (b * a.HPo + ii + a.Po) * a.HPo + jj + a.Po;
       ooff[j] = pix[j] * a.Cout + nbase + 4 * h;
     }
-    if constexpr (MODE == MODE_BIAS_RELU) {
+    if constexpr (BASE == MODE_BIAS_RELU) {
 #pragma unroll
       for (int i = 0; i < NB; ++i)
 #pragma unroll
         for (int g = 0; g < 4; ++g) bb[i][g] = *(const f32x4*)(a.bias + nbase + 4 * h + i * 32 + g * 8);
-    } else if constexpr (MODE == MODE_MASK) {
+    } else if constexpr (BASE == MODE_MASK) {
 #pragma unroll
       for (int j = 0; j < MB; ++j)
 #pragma unroll
         for (int i = 0; i < NB; ++i)
 #pragma unroll
           for (int g = 0; g < 4; ++g) mk[i][j][g] = *(const bf16x4*)(a.mask + ooff[j] + i * 32 + g * 8);
-    } else if constexpr (MODE == MODE_MASKBITS) {
+    } else if constexpr (BASE == MODE_MASKBITS) {
 #pragma unroll
       for (int j = 0; j < MB; ++j) {
         const uint32_t* p = a.mbits_in + (size_t)pix[j] * mwords + mslot;
@@ -356,13 +393,22 @@ struct ConvEpilogue32 {
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = acc[i][j][4 * g + r];
           const int bit0 = 8 * i + 4 * (g >> 1);  // in word (g & 1)
-          if constexpr (MODE == MODE_BIAS_RELU) {
+          if constexpr (RES) {  // acc + bias + res (forward), acc + res (dgrad)
+            const bf16x4 rs = *(const bf16x4*)(a.res + ooff[j] + i * 32 + g * 8);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              v[r] = (BASE == MODE_BIAS_RELU ? v[r] + bb[i][g][r] : v[r]) + (float)rs[r];
+          }
+          if constexpr (BASE == MODE_BIAS_RELU && RES) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+          } else if constexpr (BASE == MODE_BIAS_RELU) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r] + bb[i][g][r], 0.f);
-          } else if constexpr (MODE == MODE_MASK) {
+          } else if constexpr (BASE == MODE_MASK) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = (float)mk[i][j][g][r] > 0.f ? v[r] : 0.f;
-          } else if constexpr (MODE == MODE_MASKBITS) {
+          } else if constexpr (BASE == MODE_MASKBITS) {
             const uint32_t w = (g & 1) ? mw[j].y : mw[j].x;
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = ((w >> (bit0 + r)) & 1u) ? v[r] : 0.f;
@@ -370,13 +416,13 @@ struct ConvEpilogue32 {
           bf16x4 o;
 #pragma unroll
           for (int r = 0; r < 4; ++r) o[r] = (__bf16)v[r];
-          if constexpr (MODE == MODE_BIAS_RELU) {
+          if constexpr (BASE == MODE_BIAS_RELU) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) bits[g & 1] |= ((float)o[r] > 0.f ? 1u : 0u) << (bit0 + r);
           }
           *(bf16x4*)(a.y + ooff[j] + i * 32 + g * 8) = o;
         }
-      if constexpr (MODE == MODE_BIAS_RELU)
+      if constexpr (BASE == MODE_BIAS_RELU)
         if (a.mbits_out) {
           uint32_t* p = a.mbits_out + (size_t)pix[j] * mwords + mslot;
           p[0] = bits[0];

@@ -681,13 +681,13 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_halo384_kernel(ConvFwdArgs a)
 // tile code 388: covers 3x3, Cin % 64 == 0, S <= 19 at BN = 192 in the bias + ReLU forward and the bitmask dgrad
 template <int BN, int MODE>
 static bool halo384_covers(const ConvFwdArgs& a) {
-  return BN == 192 && (MODE == MODE_BIAS_RELU || MODE == MODE_MASKBITS) && a.K == 3 && a.Cin % 64 == 0 &&
+  return BN == 192 && ((MODE & 3) == MODE_BIAS_RELU || (MODE & 3) == MODE_MASKBITS) && a.K == 3 && a.Cin % 64 == 0 &&
          a.Cin >= 64 && a.S <= H384_SMAX && a.offi >= 0 && 9ll * a.Cout * a.Cin < (1ll << 31);
 }
 
 template <int BN, int MODE>
 static void launch_fwd_halo384(const ConvFwdArgs& a, hipStream_t st) {
-  if constexpr (BN == 192 && (MODE == MODE_BIAS_RELU || MODE == MODE_MASKBITS)) {
+  if constexpr (BN == 192 && ((MODE & 3) == MODE_BIAS_RELU || (MODE & 3) == MODE_MASKBITS)) {
     constexpr int smem = 2 * H384_ROWS * 128 + 2 * BN * 128;
     static const hipError_t attr = hipFuncSetAttribute((const void*)conv_fwd_halo384_kernel<BN, MODE>,
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, smem);
@@ -705,6 +705,8 @@ static void launch_fwd_halo384(const ConvFwdArgs& a, hipStream_t st) {
 template <int MODE, int NB>
 __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(ConvFwdArgs a) {
   constexpr int BN = 32 * NB;
+  constexpr int BASE = MODE & 3;
+  constexpr bool RES = (MODE & MODE_RES) != 0;  // skip operand: added to the summed splits
   const int WPP = (a.Cout / BN) * 8;
   const long gid = (long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long)a.M * WPP) return;
@@ -725,26 +727,30 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(ConvFwdArgs a) 
   const int jj = rem - ii * a.S;
   const size_t pix = (size_t)(b * a.HPo + ii + a.Po) * a.HPo + jj + a.Po;
   uint32_t mw = 0u, bits = 0u;
-  if constexpr (MODE == MODE_MASKBITS) mw = a.mbits_in[pix * WPP + w];
+  if constexpr (BASE == MODE_MASKBITS) mw = a.mbits_in[pix * WPP + w];
 #pragma unroll
   for (int i = 0; i < NB; ++i) {
     float o4[4];
+    bf16x4 rs;
+    if constexpr (RES) rs = *(const bf16x4*)(a.res + pix * a.Cout + base + 16 * i);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float x = v[i][r];
-      if constexpr (MODE == MODE_BIAS_RELU) x = fmaxf(x + a.bias[base + 16 * i + r], 0.f);
-      if constexpr (MODE == MODE_MASKBITS) x = ((mw >> (4 * i + r)) & 1u) ? x : 0.f;
+      if constexpr (BASE == MODE_BIAS_RELU && RES) x = fmaxf(x + a.bias[base + 16 * i + r] + (float)rs[r], 0.f);
+      else if constexpr (RES) x += (float)rs[r];
+      else if constexpr (BASE == MODE_BIAS_RELU) x = fmaxf(x + a.bias[base + 16 * i + r], 0.f);
+      if constexpr (BASE == MODE_MASKBITS) x = ((mw >> (4 * i + r)) & 1u) ? x : 0.f;
       o4[r] = x;
     }
     bf16x4 o;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       o[r] = (__bf16)o4[r];
-      if constexpr (MODE == MODE_BIAS_RELU) bits |= ((float)o[r] > 0.f ? 1u : 0u) << (4 * i + r);
+      if constexpr (BASE == MODE_BIAS_RELU) bits |= ((float)o[r] > 0.f ? 1u : 0u) << (4 * i + r);
     }
     *(bf16x4*)(a.y + pix * a.Cout + base + 16 * i) = o;
   }
-  if constexpr (MODE == MODE_BIAS_RELU)
+  if constexpr (BASE == MODE_BIAS_RELU)
     if (a.mbits_out) a.mbits_out[pix * WPP + w] = bits;
 }
 
@@ -752,19 +758,21 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(ConvFwdArgs a) 
 // (BN = 160, the value width: STR straddled K-steps when Cin % 64 == 32, weight pieces dealt round-robin)
 template <int BN, int MODE, bool STR = false>
 static void launch_fwd_splitk(const ConvFwdArgs& a, hipStream_t st) {
-  if constexpr (MODE == MODE_MASK) {
+  if constexpr ((MODE & 3) == MODE_MASK) {
     throw std::invalid_argument("conv_fwd split-K: modes 0 (bias + ReLU), 2 (none) and 3 (bitmask dgrad)");
   } else {
     if (!a.sk_ws || a.sk_nsplit < 1 || a.y_bf8)
       throw std::invalid_argument("conv_fwd split-K (tile 38): needs a workspace and nsplit >= 1, no e5m2 copy");
     constexpr int BM = 32, MBW = 1;
     constexpr int smem = 2 * (BM * 128 + BN * 128);
+    // the split pass writes raw partial sums: a skip operand (MODE_RES) is the finish kernel's alone
+    constexpr int KMODE = MODE & 3;
     static const hipError_t attr = hipFuncSetAttribute(
-        (const void*)conv_fwd_kernel<BN, MODE, BM, MBW, true, true, false, false, STR, false, 2, true>,
+        (const void*)conv_fwd_kernel<BN, KMODE, BM, MBW, true, true, false, false, STR, false, 2, true>,
         hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
     dim3 grid((a.M + BM - 1) / BM, a.Cout / BN, a.sk_nsplit);
-    hipLaunchKernelGGL((conv_fwd_kernel<BN, MODE, BM, MBW, true, true, false, false, STR, false, 2, true>), grid,
+    hipLaunchKernelGGL((conv_fwd_kernel<BN, KMODE, BM, MBW, true, true, false, false, STR, false, 2, true>), grid,
                        dim3(BM / MBW * 8), smem, st, a);
     const long threads = (long)a.M * (a.Cout / BN) * 8;
     hipLaunchKernelGGL((conv_splitk_finish_kernel<MODE, BN / 32>), dim3((unsigned)((threads + 255) / 256)), dim3(256),

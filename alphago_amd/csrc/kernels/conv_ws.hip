@@ -81,6 +81,8 @@ constexpr unsigned WS_OOB = 0x80000000u;  // a byte offset past every buffer's e
 template <int NBLK, int KW, int NWV, int NE, int MODE, bool RING, int PROBE = 0>
 __global__ __launch_bounds__(64 * (NWV + NE), 1) void conv_ws_kernel(ConvFwdArgs a, WsParams p) {
   constexpr int RM = 6, IPR = 1;
+  constexpr int BASE = MODE & 3;
+  constexpr bool RES = (MODE & MODE_RES) != 0;  // skip operand (epilogue waves only)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = wave_id();
@@ -277,9 +279,11 @@ __global__ __launch_bounds__(64 * (NWV + NE), 1) void conv_ws_kernel(ConvFwdArgs
     constexpr int IPT = (NBLK + NE - 1) / NE, NI = 64 * NBLK;  // items per thread; items per chunk
     const int et = threadIdx.x - 64 * NWV;
     const __amdgpu_buffer_rsrc_t yr = ws_rsrc(a.y, (long long)(a.M / SS) * a.HPo * a.HPo * a.Cout * 2);
+    // the skip operand has y's layout: read at the store's own offset (past the last pixel: 0, unused)
+    const __amdgpu_buffer_rsrc_t rr = ws_rsrc(RES ? a.res : nullptr, (long long)(a.M / SS) * a.HPo * a.HPo * a.Cout * 2);
     const long long mbytes = (long long)(a.M / SS) * a.HPo * a.HPo * p.WPP * 4;
-    const __amdgpu_buffer_rsrc_t mo = ws_rsrc(MODE == MODE_BIAS_RELU ? a.mbits_out : nullptr, mbytes);
-    const __amdgpu_buffer_rsrc_t mi = ws_rsrc(MODE == MODE_MASKBITS ? a.mbits_in : nullptr, mbytes);
+    const __amdgpu_buffer_rsrc_t mo = ws_rsrc(BASE == MODE_BIAS_RELU ? a.mbits_out : nullptr, mbytes);
+    const __amdgpu_buffer_rsrc_t mi = ws_rsrc(BASE == MODE_MASKBITS ? a.mbits_in : nullptr, mbytes);
     auto out_pixel = [&](int m) -> int {
       const int bb = fdiv(m, a.divSS);
       const int rem = m - bb * SS;
@@ -299,7 +303,7 @@ __global__ __launch_bounds__(64 * (NWV + NE), 1) void conv_ws_kernel(ConvFwdArgs
       e_i[q] = e_gi[q] - e_wl[q] * p.NB;
       e_ch[q] = ws_word_base(slice * p.WS + e_wl[q], p.BN) + 16 * e_i[q];
       bias4[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if constexpr (MODE == MODE_BIAS_RELU) bias4[q] = *(const f32x4*)(a.bias + e_ch[q]);
+      if constexpr (BASE == MODE_BIAS_RELU) bias4[q] = *(const f32x4*)(a.bias + e_ch[q]);
     }
     // the dgrad's mask words, one chunk ahead (past the last pixel: out of range, read as 0)
     auto load_mw = [&](int c, uint32_t (&mw)[IPT]) {
@@ -311,8 +315,8 @@ __global__ __launch_bounds__(64 * (NWV + NE), 1) void conv_ws_kernel(ConvFwdArgs
       }
     };
     uint32_t mw_cur[IPT], mw_next[IPT];
-    if constexpr (MODE == MODE_MASKBITS) load_mw(c_begin, mw_cur);
-    if constexpr (MODE == MODE_BIAS_RELU)
+    if constexpr (BASE == MODE_MASKBITS) load_mw(c_begin, mw_cur);
+    if constexpr (BASE == MODE_BIAS_RELU)
       for (int k = et; k < 32 * p.WS; k += 64 * NE) bitw[k] = 0u;
     __syncthreads();  // the MFMA waves' prologue
     // write chunk c's assembled bitmask words (lanes < 16 * WS; others and c < c_begin: dropped), clear them
@@ -327,9 +331,9 @@ __global__ __launch_bounds__(64 * (NWV + NE), 1) void conv_ws_kernel(ConvFwdArgs
     };
     for (int j = 0; j < nc; ++j) {
       const int c = c_begin + j, buf = j & 1;
-      if constexpr (MODE == MODE_MASKBITS) load_mw(c + 1, mw_next);
+      if constexpr (BASE == MODE_MASKBITS) load_mw(c + 1, mw_next);
       __syncthreads();  // chunk j's partials are in LDS; chunk j - 1's bitmask ORs are done
-      if constexpr (MODE == MODE_BIAS_RELU) flush_bits(c - 1, buf ^ 1);
+      if constexpr (BASE == MODE_BIAS_RELU) flush_bits(c - 1, buf ^ 1);
       if constexpr (PROBE & 4) continue;
       const f32x4* pb = part + buf * PART;
 #pragma unroll
@@ -337,6 +341,11 @@ __global__ __launch_bounds__(64 * (NWV + NE), 1) void conv_ws_kernel(ConvFwdArgs
         if (IPT * NE > NBLK && et + 64 * NE * q >= NI) break;
         const int px = e_px[q], gi = e_gi[q];
         const int m = c * 16 + px;
+        bf16x4 rs;  // issued before the LDS sums it is added to
+        if constexpr (RES) {
+          const unsigned roff = m < a.M ? (unsigned)(out_pixel(m) * a.Cout + e_ch[q]) * 2u : WS_OOB;
+          rs = __builtin_bit_cast(bf16x4, __builtin_amdgcn_raw_buffer_load_b64(rr, roff, 0, 0));
+        }
         // partials added in wave order (deterministic), loaded 5 at a time
         const f32x4* src = pb + (gi >> 2) * 64 + 16 * (gi & 3) + px;
         f32x4 sum = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -350,28 +359,30 @@ __global__ __launch_bounds__(64 * (NWV + NE), 1) void conv_ws_kernel(ConvFwdArgs
           for (int u = 0; u < 5; ++u)
             if (q0 + u < NWV) sum = (q0 + u == 0) ? v[u] : sum + v[u];
         }
-        const uint32_t mw = MODE == MODE_MASKBITS ? mw_cur[q] >> (4 * e_i[q]) : 0u;
+        const uint32_t mw = BASE == MODE_MASKBITS ? mw_cur[q] >> (4 * e_i[q]) : 0u;
         bf16x4 o;
         uint32_t bits = 0u;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float x = sum[r];
-          if constexpr (MODE == MODE_BIAS_RELU) x = fmaxf(x + bias4[q][r], 0.f);
-          if constexpr (MODE == MODE_MASKBITS) x = ((mw >> r) & 1u) ? x : 0.f;
+          if constexpr (BASE == MODE_BIAS_RELU && RES) x = fmaxf(x + bias4[q][r] + (float)rs[r], 0.f);
+          else if constexpr (RES) x += (float)rs[r];
+          else if constexpr (BASE == MODE_BIAS_RELU) x = fmaxf(x + bias4[q][r], 0.f);
+          if constexpr (BASE == MODE_MASKBITS) x = ((mw >> r) & 1u) ? x : 0.f;
           o[r] = (__bf16)x;
           bits |= ((float)o[r] > 0.f ? 1u : 0u) << r;
         }
         const unsigned off = m < a.M ? (unsigned)(out_pixel(m) * a.Cout + e_ch[q]) * 2u : WS_OOB;
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(ws_u32x2, o), yr, off, 0, 0);
-        if constexpr (MODE == MODE_BIAS_RELU)
+        if constexpr (BASE == MODE_BIAS_RELU)
           if (bits) atomicOr(bitw + buf * 16 * p.WS + e_wl[q] * 16 + px, bits << (4 * e_i[q]));
       }
-      if constexpr (MODE == MODE_MASKBITS)
+      if constexpr (BASE == MODE_MASKBITS)
 #pragma unroll
         for (int q = 0; q < IPT; ++q) mw_cur[q] = mw_next[q];
     }
     __syncthreads();  // the last chunk's bitmask ORs are done
-    if constexpr (MODE == MODE_BIAS_RELU) flush_bits(c_end - 1, (nc - 1) & 1);
+    if constexpr (BASE == MODE_BIAS_RELU) flush_bits(c_end - 1, (nc - 1) & 1);
   }
 }
 
@@ -506,6 +517,12 @@ static void launch_ws_t(const ConvFwdArgs& a, int mode, WsParams p, hipStream_t 
   if (mode == MODE_BIAS_RELU) ws_go<conv_ws_kernel<NBLK, KW, NWV, NE, MODE_BIAS_RELU, RING>>(grid, block, smem, st, a, p);
   else if (mode == MODE_MASKBITS) ws_go<conv_ws_kernel<NBLK, KW, NWV, NE, MODE_MASKBITS, RING>>(grid, block, smem, st, a, p);
   else if (mode == MODE_NONE) ws_go<conv_ws_kernel<NBLK, KW, NWV, NE, MODE_NONE, RING>>(grid, block, smem, st, a, p);
+#ifndef AGK_KERNEL_LAB
+  else if (mode == (MODE_BIAS_RELU | MODE_RES))
+    ws_go<conv_ws_kernel<NBLK, KW, NWV, NE, MODE_BIAS_RELU | MODE_RES, RING>>(grid, block, smem, st, a, p);
+  else if (mode == (MODE_MASKBITS | MODE_RES))
+    ws_go<conv_ws_kernel<NBLK, KW, NWV, NE, MODE_MASKBITS | MODE_RES, RING>>(grid, block, smem, st, a, p);
+#endif
   else throw std::invalid_argument("conv_fwd tile 40: modes 0 (bias + ReLU), 2 (none) and 3 (bitmask dgrad)");
 }
 

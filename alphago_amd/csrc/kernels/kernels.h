@@ -10,6 +10,14 @@
 namespace agk {
 
 enum { MODE_BIAS_RELU = 0, MODE_MASK = 1, MODE_NONE = 2, MODE_MASKBITS = 3 };
+// Skip operand of a residual block (ConvFwdArgs::res): a flag on top of the two epilogues that take one.
+// The launchers set it when res is non-null, so a kernel template's MODE is the epilogue (MODE & 3) plus
+// this bit and the instantiations without a skip are the ones that existed before it.
+//   MODE_BIAS_RELU | MODE_RES: y = relu(acc + bias + res) (the ReLU' bit from the stored bf16, as always)
+//   MODE_MASKBITS  | MODE_RES: y = (acc + res) masked by mbits_in (the skip gradient joins before ReLU')
+enum { MODE_RES = 4 };
+constexpr int mode_base(int mode) { return mode & 3; }
+constexpr bool mode_res(int mode) { return (mode & MODE_RES) != 0; }
 
 struct ConvFwdArgs {
   const __bf16* x;     // padded NHWC input
@@ -35,6 +43,9 @@ struct ConvFwdArgs {
   // conv_splitk_finish_kernel (bias + ReLU + bitmask, or the bitmask of dgrad)
   float* sk_ws;
   int sk_nsplit;
+  // MODE_BIAS_RELU / MODE_MASKBITS only, optional: the skip operand of a residual block, a bf16 tensor in
+  // y's layout (never y itself), read at interior pixels only and added in fp32 before the ReLU / the mask
+  const __bf16* res;
 };
 
 struct ConvWgradArgs {

@@ -10,8 +10,8 @@ using namespace agk_ops;
 // x: (B, HPi, HPi, Cin) bf16; w: (T, Cout, Cin) bf16; y: (B, HPo, HPo, Cout) bf16
 void conv_fwd(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bias, const c10::optional<Tensor>& mask,
               const Tensor& y, int64_t K, int64_t S, int64_t Pin, int64_t Po, int64_t mode,
-              const c10::optional<Tensor>& mbits, int64_t tile) {
-  check_dev("conv_fwd", x, w, bias, mask, y, mbits);
+              const c10::optional<Tensor>& mbits, int64_t tile, const c10::optional<Tensor>& res) {
+  check_dev("conv_fwd", x, w, bias, mask, y, mbits, res);
   // production tilings only: 0 = automatic, or a fixed 64 / 128 / 256 / 384-pixel tile (385: 384 with the
   // LDS-DMA issue spread through the MFMAs; 386 / 387: 385 / 384 with the chunk-outer K order; 388: 386 with
   // the pixel rows staged once per 64-channel chunk, 386 where it does not apply)
@@ -19,7 +19,8 @@ void conv_fwd(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bia
                   tile == 384 || tile == 385 || tile == 386 || tile == 387 || tile == 388,
               "conv_fwd tile ", tile, " is not a production tiling (0, 36, 37, 40, 64, 128, 256, 384-388); kernel-lab "
               "variants are in torch.ops.alphago_amd_lab (alphago_amd.ops.lab())");
-  conv_fwd_impl(x, w, bias, mask, y, K, S, Pin, Po, mode, mbits, (int)tile);
+  conv_fwd_impl(x, w, bias, mask, y, K, S, Pin, Po, mode, mbits, (int)tile, nullptr, -1, c10::nullopt, c10::nullopt,
+                c10::nullopt, 0, c10::nullopt, 0, res);
 }
 
 // one draw per board from probs ** beta (probs: (B, NP) f32, has: (B,) bool / uint8, out: (B,) int64)
@@ -49,10 +50,10 @@ void sample_moves(const Tensor& probs, const Tensor& has, const Tensor& out, dou
 // ws (>= nsplit * M * Cout fp32), then one finishing pass (bias + ReLU + bitmask, or the bitmask dgrad)
 void conv_fwd_splitk(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bias, const Tensor& y, int64_t K,
                      int64_t S, int64_t Pin, int64_t Po, int64_t mode, const c10::optional<Tensor>& mbits,
-                     const Tensor& ws, int64_t nsplit) {
-  check_dev("conv_fwd_splitk", x, w, bias, y, mbits, ws);
+                     const Tensor& ws, int64_t nsplit, const c10::optional<Tensor>& res) {
+  check_dev("conv_fwd_splitk", x, w, bias, y, mbits, ws, res);
   conv_fwd_impl(x, w, bias, c10::nullopt, y, K, S, Pin, Po, mode, mbits, 38, nullptr, -1, c10::nullopt, c10::nullopt,
-                c10::nullopt, 0, ws, (int)nsplit);
+                c10::nullopt, 0, ws, (int)nsplit, res);
 }
 
 // slab: (nsplit, T, Cout, Cin) f32; dbslab: (nsplit, Cout) f32
@@ -1043,10 +1044,10 @@ void debug_conv_fwd_understated(const Tensor& x, const Tensor& w, const Tensor& 
 TORCH_LIBRARY(alphago_amd, m) {
   m.def(
       "conv_fwd(Tensor x, Tensor w, Tensor? bias, Tensor? mask, Tensor(a!) y, int K, int S, int Pin, int Po, int mode, "
-      "Tensor(b!)? mbits=None, int tile=0) -> ()");
+      "Tensor(b!)? mbits=None, int tile=0, Tensor? res=None) -> ()");
   m.def(
       "conv_fwd_splitk(Tensor x, Tensor w, Tensor? bias, Tensor(a!) y, int K, int S, int Pin, int Po, int mode, "
-      "Tensor(b!)? mbits, Tensor(c!) ws, int nsplit) -> ()");
+      "Tensor(b!)? mbits, Tensor(c!) ws, int nsplit, Tensor? res=None) -> ()");
   m.def("sample_moves(Tensor probs, Tensor has, Tensor(a!) out, float beta, int seed) -> ()");
   m.def("conv_wgrad(Tensor x, Tensor dz, Tensor(a!) slab, Tensor(b!) dbslab, int K, int S, int Pin, int Po, int cin_real=0, int variant=0) -> ()");
   m.def("conv_wgrad_reduce(Tensor slab, Tensor dbslab, Tensor(a!) grad_w, Tensor(b!)? grad_b, float scale, float beta) -> ()");

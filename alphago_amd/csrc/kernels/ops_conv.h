@@ -69,8 +69,9 @@ inline void conv_fwd_impl(const Tensor& x, const Tensor& w, const c10::optional<
                           const c10::optional<Tensor>& y_bf8 = c10::nullopt,
                           const c10::optional<Tensor>& bf8_scale = c10::nullopt,
                           const c10::optional<Tensor>& bf8_amax = c10::nullopt, int pk_cpt = 0,
-                          const c10::optional<Tensor>& sk_ws = c10::nullopt, int sk_nsplit = 0) {
-  check_dev("conv_fwd_impl", x, w, bias, mask, y, mbits, y_bf8, bf8_scale, bf8_amax, sk_ws);
+                          const c10::optional<Tensor>& sk_ws = c10::nullopt, int sk_nsplit = 0,
+                          const c10::optional<Tensor>& res = c10::nullopt) {
+  check_dev("conv_fwd_impl", x, w, bias, mask, y, mbits, y_bf8, bf8_scale, bf8_amax, sk_ws, res);
   CHECK_DEV(x); CHECK_DEV(w); CHECK_DEV(y);
   CHECK_CONTIG(x); CHECK_CONTIG(w); CHECK_CONTIG(y);
   CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(y);
@@ -136,6 +137,20 @@ inline void conv_fwd_impl(const Tensor& x, const Tensor& w, const c10::optional<
                       bf8_amax->is_contiguous(), "bf8_amax: int32[64]");
       a.bf8_amax = reinterpret_cast<unsigned*>(bf8_amax->data_ptr<int>());
     }
+  }
+  if (res.has_value()) {  // residual block: the skip operand, added before the ReLU / the ReLU' mask
+    TORCH_CHECK(mode == agk::MODE_BIAS_RELU || mode == agk::MODE_MASKBITS,
+                "res: modes 0 (bias + ReLU) and 3 (bitmask dgrad) only");
+    TORCH_CHECK(!y_bf8.has_value(), "res cannot be combined with the e5m2 copy (y_bf8)");
+    TORCH_CHECK(pk_cpt == 0 && dbg == nullptr, "res: not in the kernel-lab variants");
+    CHECK_DEV(*res); CHECK_BF16(*res); CHECK_CONTIG(*res);
+    TORCH_CHECK(res->sizes() == y.sizes(), "res must have y's shape (padded NHWC, Cout channels, output pad)");
+    // a workgroup would read pixels another one has already overwritten
+    const char* r0 = static_cast<const char*>(res->data_ptr());
+    const char* y0 = static_cast<const char*>(y.data_ptr());
+    const size_t nbytes = (size_t)y.numel() * 2;
+    TORCH_CHECK(r0 + nbytes <= y0 || y0 + nbytes <= r0, "res must not alias y");
+    a.res = bfp(*res);
   }
   if (sk_ws.has_value()) {  // split-K (tile 38): fp32 partials [nsplit][M][Cout]
     CHECK_F32(*sk_ws); CHECK_CONTIG(*sk_ws);

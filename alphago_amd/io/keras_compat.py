@@ -101,7 +101,8 @@ def model_from_keras_json(spec: str):
 
 
 def pv_spec(net: PolicyValueNet) -> Dict:
-    """The dual net's architecture (it is no Keras Sequential: a spec key of its own, ``pv_model``)."""
+    """The dual net's architecture (it is no Keras Sequential: a spec key of its own, ``pv_model``);
+    ``residual: 1`` only for a residual trunk, so the spec of a plain net is what it always was."""
     return dict(net.arch)
 
 

@@ -72,6 +72,13 @@ class HipTrunkInference:
             raise ValueError("precision must be bf16 or fp8")
         self.device = torch.device(device)
         tr = net.trunk
+        # residual trunk: the skip-add rides in the bf16 conv epilogue (conv_planned res=); three Y
+        # buffers in rotation instead of two, so the block input outlives the block's first layer
+        self.residual = bool(getattr(tr, "residual", False))
+        if self.residual and self.precision == "fp8":
+            raise ValueError("a residual trunk runs in bf16 only: the fp8 conv kernels have no skip operand "
+                             "(precision=\"fp8\" argument or ALPHAGO_AMD_PRECISION=fp8)")
+        self._ny = 3 if self.residual else 2
         self.S, self.L, self.K = net.board, tr.layers, list(tr.widths)
         self.C0, self.F = tr.in_planes, tr.filters
         self.C0p = ops.round_up(self.C0, 64)
@@ -175,7 +182,7 @@ class HipTrunkInference:
         bk.planes = torch.zeros((B, self.C0, S, S), dtype=torch.uint8, device=dev)
         bk.legal = torch.ones((B, S * S), dtype=torch.uint8, device=dev)
         bk.X0 = ops.padded_empty(Bt, S, self.P0, self.C0p, dev)
-        bk.Y = [ops.padded_empty(Bt, S, 1, self.Fp, dev) for _ in range(2)]
+        bk.Y = [ops.padded_empty(Bt, S, 1, self.Fp, dev) for _ in range(self._ny)]
         if self._sym:
             # trunk board g * B + b is position b under sym[g * B + b]; "random" refills sym per submission
             bk.sym = torch.arange(self.G, dtype=torch.int32, device=dev).repeat_interleave(B) if self.G > 1 \
@@ -241,9 +248,12 @@ class HipTrunkInference:
             return self._trunk_fp8(bk)
         x, pin = bk.X0, self.P0
         for l in range(self.L):
-            y = bk.Y[l % 2]
+            y = bk.Y[l % self._ny]
+            # residual trunk: layer l's input is Y[(l-1) % 3] and a block end's skip Y[(l-2) % 3], so the
+            # skip is never the buffer being written
+            res = bk.Y[(l - 2) % 3] if self.residual and l >= 2 and l % 2 == 0 else None
             ops.conv_planned(bk.plan[l], x, self.wf[l], self.wf_ws[l], self.bias_p[l], y, self.K[l], self.S, pin,
-                             sk_ws=bk.ws)
+                             sk_ws=bk.ws, res=res)
             if getattr(self, "_calibrating", False):
                 self._cal_amax[l] = max(self._cal_amax[l], float(y.amax()))
             x, pin = y, 1

@@ -38,10 +38,22 @@ def keras_uniform_(t: torch.Tensor, scale: float = KERAS_UNIFORM_SCALE, generato
 def he_uniform_(net: nn.Module, generator=None) -> nn.Module:
     """Fan-in scaled uniform init (He for the ReLU trunk and the 1x1 head conv, LeCun for the dense
     layers) of a PolicyNet / ValueNet, biases zero: the reference's ``uniform(-0.05, 0.05)`` shrinks a
-    12-layer trunk's signal ~30x (value.py:17,21), which plain SGD does not recover from."""
+    12-layer trunk's signal ~30x (value.py:17,21), which plain SGD does not recover from.
+
+    A residual trunk gets the Fixup rule for two-layer branches: the first conv of each block its He bound
+    times ``n_blocks ** -0.5``, the second conv of each block zero; the stem and the heads as above.  With
+    the zero biases every block is then the identity on its (non-negative) input, so the trunk's output
+    equals the stem's exactly."""
     with torch.no_grad():
-        for w in list(net.trunk.weights) + [net.head_w]:
+        residual = getattr(net.trunk, "residual", False)
+        n_blocks = (net.trunk.layers - 1) // 2
+        for l, w in enumerate(list(net.trunk.weights) + [net.head_w]):
             bound = (6.0 / (w.shape[1] * w.shape[2] * w.shape[3])) ** 0.5
+            if residual and 0 < l < net.trunk.layers:
+                if l % 2 == 0:  # block end
+                    w.zero_()
+                    continue
+                bound *= n_blocks ** -0.5
             w.uniform_(-bound, bound, generator=generator)
         vh = getattr(net, "vhead_w", None)  # PolicyValueNet's second 1x1 head
         if vh is not None:
@@ -56,11 +68,20 @@ def he_uniform_(net: nn.Module, generator=None) -> nn.Module:
 
 
 class ConvStack(nn.Module):
-    """Shared trunk: conv(k_1) + (L-1) conv(k_i), all ReLU, 'same' padding."""
+    """Shared trunk: conv(k_1) + (L-1) conv(k_i), all ReLU, 'same' padding.
 
-    def __init__(self, in_planes: int, filters: int, layers: int, widths: List[int]):
+    ``residual``: layer 0 is the stem and layers 1..L-1 form blocks of two, (1, 2), (3, 4), ...; the last
+    layer of a block adds the block's input before its ReLU, ``Y[l] = relu(conv_l(Y[l-1]) + b_l + Y[l-2])``
+    for even ``l >= 2``.  Parameter names, shapes and order are those of the plain stack."""
+
+    def __init__(self, in_planes: int, filters: int, layers: int, widths: List[int], residual: bool = False):
         super().__init__()
         assert len(widths) == layers
+        if residual and (layers < 3 or layers % 2 == 0):
+            lo = max(3, layers - 1 if layers % 2 == 0 else layers)
+            raise ValueError("a residual trunk is a stem plus whole two-layer blocks: layers must be odd and "
+                             ">= 3, not %d (nearest valid depths: %d and %d)" % (layers, lo, max(lo + 2, layers + 1)))
+        self.residual = bool(residual)
         for w in widths:
             if w % 2 != 1:
                 raise ValueError("filter widths must be odd")
@@ -81,8 +102,13 @@ class ConvStack(nn.Module):
             nn.init.zeros_(b)
 
     def forward_torch(self, x: torch.Tensor) -> torch.Tensor:
-        for w, b, k in zip(self.weights, self.biases, self.widths):
-            x = F.relu(F.conv2d(x, w.to(x.dtype), b.to(x.dtype), padding=k // 2))
+        skip = None  # the current block's input (residual trunks)
+        for l, (w, b, k) in enumerate(zip(self.weights, self.biases, self.widths)):
+            z = F.conv2d(x, w.to(x.dtype), b.to(x.dtype), padding=k // 2)
+            if self.residual and l % 2 == 0:  # the stem, or a block's last layer: the next block's input
+                x = skip = F.relu(z if l == 0 else z + skip)
+            else:
+                x = F.relu(z)
         return x
 
 
@@ -179,10 +205,11 @@ class ValueNet(nn.Module):
 class PolicyValueNet(nn.Module):
     """Dual-head network: one ConvStack, the policy head of PolicyNet (1x1 conv, softmax over S*S)
     and the value head of ValueNet (1x1 conv, Dense(dense, linear), Dense(1, tanh)) on its output.
-    Reads the value net's planes (49 with ``color``)."""
+    Reads the value net's planes (49 with ``color``).  ``residual``: a residual trunk (ConvStack), kept in
+    ``arch`` only when set; ``layers`` must then be odd."""
 
     def __init__(self, input_dim: int = 49, board: int = 19, filters_per_layer: int = 192, layers: int = 12,
-                 dense: int = 256, **kwargs):
+                 dense: int = 256, residual: int = 0, **kwargs):
         super().__init__()
         widths = [int(kwargs.get("filter_width_%d" % i, 5 if i == 1 else 3)) for i in range(1, layers + 1)]
         self.arch = dict(input_dim=input_dim, board=board, filters_per_layer=filters_per_layer, layers=layers,
@@ -190,8 +217,10 @@ class PolicyValueNet(nn.Module):
         for i, w in enumerate(widths, 1):
             if (i == 1 and w != 5) or (i > 1 and w != 3):
                 self.arch["filter_width_%d" % i] = w
+        if residual:
+            self.arch["residual"] = 1
         self.board = board
-        self.trunk = ConvStack(input_dim, filters_per_layer, layers, widths)
+        self.trunk = ConvStack(input_dim, filters_per_layer, layers, widths, residual=bool(residual))
         self.head_w = nn.Parameter(torch.empty(1, filters_per_layer, 1, 1))
         self.head_b = nn.Parameter(torch.zeros(1))
         self.vhead_w = nn.Parameter(torch.empty(1, filters_per_layer, 1, 1))

@@ -265,6 +265,9 @@ class CNNPolicyValue(_NetWrapper):
         """(CNNPolicy, CNNValue) carrying copies of the trunk and the respective head, both on this
         net's feature list: the pair computes what the two heads compute, each on its own trunk."""
         a, fl = self.model.arch, list(self.preprocessor.feature_list)
+        if self.model.trunk.residual:
+            raise ValueError("split(): a residual trunk has no single-head form (the Keras Sequential of "
+                             "CNNPolicy / CNNValue cannot express a skip connection)")
         kw = {k: v for k, v in a.items() if k.startswith("filter_width_")}
         pol = CNNPolicy(fl, device=self.device, board=a["board"], filters_per_layer=a["filters_per_layer"],
                         layers=a["layers"], **kw)

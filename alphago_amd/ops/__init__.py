@@ -122,15 +122,21 @@ def from_padded(y: torch.Tensor, P: int, C: Optional[int] = None) -> torch.Tenso
 
 # ----------------------------------------------------------------- op wrappers
 def conv_fwd(x, w_packed, bias, y, K: int, S: int, Pin: int, Po: int = 1, mode: int = MODE_BIAS_RELU, mask=None,
-             mbits=None, tile: int = 0):
+             mbits=None, tile: int = 0, res=None):
     """Conv + epilogue.  mode 0: bias + ReLU (mbits: also write the ReLU' bitmask);
     1: dgrad masked by ``mask`` > 0; 3: dgrad masked by the ``mbits`` bitmask.
+    ``res`` (modes 0 and 3, a bf16 tensor of ``y``'s shape that is not ``y``): the skip operand of a
+    residual block, ``relu(conv + bias + res)`` / ``(dgrad + res)`` under the bitmask, read at interior
+    pixels only.
     ``tile``: 0 = automatic, or a production tiling: 36 / 37 (32 pixels), 40 (weight-stationary), 64 /
     128 / 256, 384 (96 x 96 per wave), 385 (384 with the DMA issue spread through the MFMAs), 386 / 387
     (385 / 384 with the chunk-outer K order), 388 (386 with the pixel rows staged once per 64-channel
     chunk -- the compact halo; 3x3, 192-wide output tile, S <= 19, bias + ReLU and bitmask dgrad, else it
     runs 386; the automatic choice for large batches, bit-identical to 386)."""
-    _ops().conv_fwd(x, w_packed, bias, mask, y, K, S, Pin, Po, mode, mbits, tile)
+    if res is None:
+        _ops().conv_fwd(x, w_packed, bias, mask, y, K, S, Pin, Po, mode, mbits, tile)
+    else:
+        _ops().conv_fwd(x, w_packed, bias, mask, y, K, S, Pin, Po, mode, mbits, tile, res)
     return y
 
 
@@ -195,11 +201,16 @@ def ws_applies(M: int, cout_p: int, cin_p: int, K: int, training: bool = False) 
     return bool(_ops().conv_ws_supported(cout_p, cin_p, K))
 
 
-def conv_fwd_splitk(x, w_packed, bias, y, K: int, S: int, Pin: int, Po: int, mode: int, mbits, ws, nsplit: int):
+def conv_fwd_splitk(x, w_packed, bias, y, K: int, S: int, Pin: int, Po: int, mode: int, mbits, ws, nsplit: int,
+                    res=None):
     """conv_fwd on the 32-pixel tile with its K loop split over ``nsplit`` workgroups per tile (fp32
     partials in ``ws``, >= nsplit * M * Cout floats) and one finishing pass: modes 0 (bias + ReLU,
-    optional bitmask), 2 (none), 3 (bitmask dgrad)."""
-    _ops().conv_fwd_splitk(x, w_packed, bias, y, K, S, Pin, Po, mode, mbits, ws, nsplit)
+    optional bitmask), 2 (none), 3 (bitmask dgrad).  ``res``: conv_fwd's skip operand (modes 0 and 3),
+    added by the finishing pass."""
+    if res is None:
+        _ops().conv_fwd_splitk(x, w_packed, bias, y, K, S, Pin, Po, mode, mbits, ws, nsplit)
+    else:
+        _ops().conv_fwd_splitk(x, w_packed, bias, y, K, S, Pin, Po, mode, mbits, ws, nsplit, res)
     return y
 
 
@@ -233,11 +244,18 @@ def splitk_workspace_numel(plans, M: int, cout_p: int) -> int:
 
 
 def conv_planned(plan: ConvPlan, x, w, w_ws, bias, y, K: int, S: int, pin: int, mode: int = MODE_BIAS_RELU,
-                 mbits=None, sk_ws=None):
+                 mbits=None, sk_ws=None, res=None):
     """The one launch of a planned conv layer into ``y`` (output border 1).  ``w``: the standard pack,
     ``w_ws``: its weight-stationary copy ("ws" plans only), ``sk_ws``: the split-K workspace.  The bitmask
-    dgrad is ``mode=MODE_MASKBITS`` on the transposed packs without bias."""
-    if plan.kind == "splitk":
+    dgrad is ``mode=MODE_MASKBITS`` on the transposed packs without bias.  ``res``: the skip operand of a
+    residual block's last layer (conv_fwd), on every plan kind."""
+    if res is not None:
+        if plan.kind == "splitk":
+            _ops().conv_fwd_splitk(x, w, bias, y, K, S, pin, 1, mode, mbits, sk_ws, plan.nsplit, res)
+        else:
+            _ops().conv_fwd(x, w_ws if plan.kind == "ws" else w, bias, None, y, K, S, pin, 1, mode, mbits,
+                            plan.tile, res)
+    elif plan.kind == "splitk":
         _ops().conv_fwd_splitk(x, w, bias, y, K, S, pin, 1, mode, mbits, sk_ws, plan.nsplit)
     else:
         _ops().conv_fwd(x, w_ws if plan.kind == "ws" else w, bias, None, y, K, S, pin, 1, mode, mbits, plan.tile)

@@ -282,6 +282,15 @@ class HipConvTrainer:
         if precision not in ("bf16", "fp8"):
             raise ValueError("precision must be bf16 or fp8")
         self.precision = precision
+        # residual trunk (ConvStack residual=True): the skip-add is fused into the bf16 conv epilogues --
+        # forward of an even layer l >= 2 adds Y[l-2], dgrad of an odd layer l adds DZ[l+1]
+        self.residual = bool(getattr(net.trunk, "residual", False))
+        if self.residual and precision == "fp8":
+            raise ValueError("a residual trunk trains in bf16 only: the fp8 conv kernels have no skip operand "
+                             "(precision=\"fp8\")")
+        if self.residual and self.lab_tile:
+            raise ValueError("a residual trunk cannot run on a kernel-lab tiling: the kernel-lab library has no "
+                             "skip operand (ALPHAGO_AMD_LAB_TILE=%d)" % self.lab_tile)
         self.env = agdist.env()
         self.device = torch.device(device) if device is not None else self.env.device
         if self.device.type != "cuda":
@@ -612,8 +621,10 @@ class HipConvTrainer:
             ops.lab().conv_fwd(x, self.wf[l], self.bias_p[l], None, self.Y[l], 3, self.S, pin, 1, 0, mbits,
                                self.lab_tile)
         else:
+            # residual trunk: a block's last layer adds the block's input before its ReLU
+            res = self.Y[l - 2] if self.residual and l >= 2 and l % 2 == 0 else None
             ops.conv_planned(self.fwd_plan[l], x, self.wf[l], self.wf_ws[l], self.bias_p[l], self.Y[l], self.K[l],
-                             self.S, pin, ops.MODE_BIAS_RELU, mbits, self._sk_ws)
+                             self.S, pin, ops.MODE_BIAS_RELU, mbits, self._sk_ws, res=res)
 
     def _forward_fp8(self) -> None:
         x8, pin = self.X08, self.P0  # e4m3 input written by forward_trunk's pack_input (exact: 0/1 planes)
@@ -714,7 +725,8 @@ class HipConvTrainer:
             self.reducer.launch(self._bucket_after_layer[l])
 
     def _dgrad_layer(self, l: int) -> None:
-        """dgrad of layer l >= 1: DZ[l] (or its e5m2 copy) into DZ[l-1], ReLU' of Y[l-1] fused."""
+        """dgrad of layer l >= 1: DZ[l] (or its e5m2 copy) into DZ[l-1], ReLU' of Y[l-1] fused (and, in
+        a residual trunk, the skip gradient of the block that layer l opens)."""
         w8 = self.fp8_wgrad and self._g8_calibrated
         if w8 and self.fp8_dgrad and l in self._w8layers:
             # all-fp8 backward: the e5m2 dZ copy wgrad(l) read is also this dgrad's operand;
@@ -744,9 +756,13 @@ class HipConvTrainer:
             ops.lab().conv_fwd(self.DZ[l], self.wd[l], None, None, self.DZ[l - 1], 3, self.S, 1, 1,
                                ops.MODE_MASKBITS, self.MBITS[l - 1], self.lab_tile)
         else:  # ReLU' bitmask from the forward epilogue (bf16 and fp8 forwards write it); small batches
-            # on the weight-stationary or the split-K tile (dg_plan)
+            # on the weight-stationary or the split-K tile (dg_plan).  Residual trunk, odd l (a block's
+            # first layer): DZ[l-1] = (W_l^T DZ[l] + DZ[l+1]) * ReLU'(Y[l-1]) -- the skip carries the
+            # already-masked gradient at the block's output, which nothing writes again in this backward
+            # (the side-stream wgrad only reads it)
+            res = self.DZ[l + 1] if self.residual and l % 2 == 1 else None
             ops.conv_planned(self.dg_plan[l], self.DZ[l], self.wd[l], self.wd_ws[l], None, self.DZ[l - 1],
-                             self.K[l], self.S, 1, ops.MODE_MASKBITS, self.MBITS[l - 1], self._sk_ws)
+                             self.K[l], self.S, 1, ops.MODE_MASKBITS, self.MBITS[l - 1], self._sk_ws, res=res)
 
     def backward_trunk(self, reduce: bool = True) -> None:
         """dZ[L-1] (and head grads) must be ready on the current stream.
