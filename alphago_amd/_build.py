@@ -158,11 +158,9 @@ def _torch_paths():
     return incs, libdir, abi
 
 
-def build_hip(force: bool = False, verbose: bool = False, flavor: str = "prod") -> str:
-    srcs = _hip_sources(flavor)
-    # kernels include engine/ladder_bb.h (shared host/device ladder reader)
-    hdrs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.h")) + [os.path.join(CSRC, "engine", "ladder_bb.h")])
-    out = hip_path(flavor)
+def hip_compile_flags(flavor: str = "prod"):
+    """(common, hip_flags, inc_flags, libdir) of one HIP translation unit: what build_hip passes to
+    hipcc, shared with the tools that compile a kernel file to assembly (scripts/epilogue_listing.py)."""
     incs, libdir, abi = _torch_paths()
     common = [
         "-O3",
@@ -177,11 +175,20 @@ def build_hip(force: bool = False, verbose: bool = False, flavor: str = "prod") 
     ] + {"prod": [], "debug": ["-DAGK_DEBUG=1"],
          "lab": ["-DAGK_KERNEL_LAB=1", "-Dagk=agk_lab", "-Dagk_ops=agk_lab_ops"]}[flavor]
     hip_flags = ["--offload-arch=" + ARCH, "-fgpu-rdc" if False else "-fno-gpu-rdc", "-munsafe-fp-atomics"]
+    inc_flags = ["-I" + p for p in incs] + ["-I" + os.path.join(CSRC, "kernels"), "-I" + sysconfig.get_paths()["include"]]
+    return common, hip_flags, inc_flags, libdir
+
+
+def build_hip(force: bool = False, verbose: bool = False, flavor: str = "prod") -> str:
+    srcs = _hip_sources(flavor)
+    # kernels include engine/ladder_bb.h (shared host/device ladder reader)
+    hdrs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.h")) + [os.path.join(CSRC, "engine", "ladder_bb.h")])
+    out = hip_path(flavor)
+    common, hip_flags, inc_flags, libdir = hip_compile_flags(flavor)
     digest = _digest(srcs + hdrs, " ".join(common + hip_flags))
     if not force and _up_to_date(out, digest):
         return out
     os.makedirs(BUILD, exist_ok=True)
-    inc_flags = ["-I" + p for p in incs] + ["-I" + os.path.join(CSRC, "kernels"), "-I" + sysconfig.get_paths()["include"]]
     hipcc = os.path.join(ROCM, "bin", "hipcc")
 
     def compile_one(src):

@@ -195,6 +195,7 @@ struct ConvEpilogue {
   f32x4 bb[NB];
   bf16x4 mk[NB][MB];
   uint32_t mw[MB];
+  float gsc;  // MODE_MASKBITS with an e5m2 copy: *a.bf8_scale
   int mslot, mwords;
 
   // ReLU' bitmask layout: per padded pixel, (Cout/BN)*8 32-bit words; word
@@ -227,13 +228,129 @@ struct ConvEpilogue {
     } else if constexpr (BASE == MODE_MASKBITS) {
 #pragma unroll
       for (int j = 0; j < MB; ++j) mw[j] = a.mbits_in[(size_t)pix[j] * mwords + mslot];
+      if constexpr (BF8) gsc = a.y_bf8 ? *a.bf8_scale : 0.f;
     }
   }
 
+  // Retires every operand load of load() once, after the K loop and before the first store: each
+  // loaded register passes through an empty asm, so the compiler waits for it here and knows it
+  // complete afterwards.  Without this the rows' exec-masked `continue` makes the waitcnt
+  // insertion re-emit the operand waits at every row's join, and since vmcnt retires in issue
+  // order those waits bind on the previous row's stores: one store round trip per pixel row.
+  // Kernels that call load() inside the K loop call this after the loop (their in-loop waits are
+  // inline asm, invisible to the compiler; the loads have long landed and the wait costs nothing).
+  __device__ __forceinline__ void settle() {
+    // with a skip operand the rows load in groups between their stores anyway, and pinning the bias
+    // registers ahead of the first group costs the 384-pixel tiles 14 spilled VGPRs
+    if constexpr (RES) return;
+    if constexpr (BASE == MODE_BIAS_RELU) {
+#pragma unroll
+      for (int i = 0; i < NB; ++i) asm volatile("" : "+v"(bb[i]));
+    } else if constexpr (BASE == MODE_MASK) {
+#pragma unroll
+      for (int i = 0; i < NB; ++i)
+#pragma unroll
+        for (int j = 0; j < MB; ++j) asm volatile("" : "+v"(mk[i][j]));
+    } else if constexpr (BASE == MODE_MASKBITS) {
+#pragma unroll
+      for (int j = 0; j < MB; ++j) asm volatile("" : "+v"(mw[j]));
+      if constexpr (BF8) {
+        asm volatile("" : "+v"(gsc));
+        gsc = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(gsc)));  // wave-uniform: a scalar
+      }
+    }
+  }
+
+  // blocks stored in pairs (store_rows): all but an odd last one; none with a skip operand, whose row
+  // groups already fill the registers (paired, the 384-pixel residual tiles spill 14-16 VGPRs)
+  static constexpr int NBP = RES ? 0 : NB;
+  // 8-byte-aligned 16-byte store / 4-byte-aligned 8-byte store (global memory takes both at dword alignment)
+  typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
+  typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+
   __device__ __forceinline__ void store(const ConvFwdArgs& a, const f32x4 (&acc)[NB][MB], int mrow) const {
     float gmax = 0.f;  // MODE_MASKBITS with an e5m2 copy: max |dx| of the lane
-    const float gsc = (BF8 && a.y_bf8) ? *a.bf8_scale : 0.f;
+    // the wave-uniform choices are made once, not per row or per store
+    if constexpr (BF8) {
+      if (a.y_bf8) store_rows<0, true>(a, acc, mrow, gmax);
+      else store_rows<0, false>(a, acc, mrow, gmax);
+      if (a.y_bf8 && a.bf8_amax) {
+        gmax = wave_max(gmax);
+        if ((threadIdx.x & 63) == 0 && gmax > 0.f) atomicMax(a.bf8_amax + (blockIdx.x & 63), __float_as_uint(gmax));
+      }
+    } else if constexpr (BASE == MODE_BIAS_RELU && RES) {
+      store_rows<2, false>(a, acc, mrow, gmax);  // (two copies of the row groups spill on the 384-pixel tiles)
+    } else if constexpr (BASE == MODE_BIAS_RELU) {
+      if (a.mbits_out) store_rows<1, false>(a, acc, mrow, gmax);
+      else store_rows<0, false>(a, acc, mrow, gmax);
+    } else {
+      store_rows<0, false>(a, acc, mrow, gmax);
+    }
+  }
+
+  // Channel blocks i, i + 1 are stored as a pair.  Lanes l and l ^ 16 hold the same pixel; a
+  // v_permlane16_swap per packed dword (odd 16-lane rows of block i <-> even rows of block i + 1) leaves
+  // the even rows with 8 consecutive channels of block i and the odd rows with 8 of block i + 1: one
+  // 16-byte store per lane and pair, 64 contiguous bytes per pixel and instruction, where the unpaired
+  // form writes 16 separate 32-byte segments per instruction.  An odd NB keeps its last block on the
+  // 8-byte store.  Both lanes of a pair share the pixel, hence the row-past-M test.
+  // BITS: the ReLU' words are written (1), not written (0) or written where a.mbits_out is set (2); they
+  // are computed before the swap, so their layout is the unpaired one.
+  // E5M2: the e5m2 copy is written, paired the same way (two 4-byte words -> one 8-byte store).
+  template <int BITS, bool E5M2>
+  __device__ __forceinline__ void store_rows(const ConvFwdArgs& a, const f32x4 (&acc)[NB][MB], int mrow,
+                                             float& gmax) const {
+    const int po = (threadIdx.x & 16) ? 12 : 0;  // odd row: block i + 1, from the even partner's channel
     bf16x4 rs[RG][RES ? NB : 1];
+    // block i of row j: epilogue arithmetic, the packed bf16 pair of dwords, the e5m2 word, the ReLU' bits
+    auto block = [&](int i, int j, uint2& ow, uint32_t& pk, uint32_t& bits) {
+      f32x4 v = acc[i][j];
+      if constexpr (RES) {  // acc + bias + res (forward), acc + res (dgrad)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          v[r] = (BASE == MODE_BIAS_RELU ? v[r] + bb[i][r] : v[r]) + (float)rs[j % RG][i][r];
+      }
+      if constexpr (BASE == MODE_BIAS_RELU && RES) {
+        v[0] = fmaxf(v[0], 0.f);
+        v[1] = fmaxf(v[1], 0.f);
+        v[2] = fmaxf(v[2], 0.f);
+        v[3] = fmaxf(v[3], 0.f);
+      } else if constexpr (BASE == MODE_BIAS_RELU) {
+        v[0] = fmaxf(v[0] + bb[i][0], 0.f);
+        v[1] = fmaxf(v[1] + bb[i][1], 0.f);
+        v[2] = fmaxf(v[2] + bb[i][2], 0.f);
+        v[3] = fmaxf(v[3] + bb[i][3], 0.f);
+      } else if constexpr (BASE == MODE_MASK) {
+        v[0] = (float)mk[i][j][0] > 0.f ? v[0] : 0.f;
+        v[1] = (float)mk[i][j][1] > 0.f ? v[1] : 0.f;
+        v[2] = (float)mk[i][j][2] > 0.f ? v[2] : 0.f;
+        v[3] = (float)mk[i][j][3] > 0.f ? v[3] : 0.f;
+      } else if constexpr (BASE == MODE_MASKBITS) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = ((mw[j] >> (4 * i + r)) & 1u) ? v[r] : 0.f;
+      }
+      bf16x4 o;
+      o[0] = (__bf16)v[0];
+      o[1] = (__bf16)v[1];
+      o[2] = (__bf16)v[2];
+      o[3] = (__bf16)v[3];
+      if constexpr (BASE == MODE_BIAS_RELU) {
+        // the bit records what the bf16 value the dgrad would re-read says: y > 0
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bits |= ((float)o[r] > 0.f ? 1u : 0u) << (4 * i + r);
+      }
+      ow = __builtin_bit_cast(uint2, o);
+      if constexpr (E5M2) {
+        float sv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          gmax = fmaxf(gmax, fabsf(v[r]));
+          sv[r] = fminf(fmaxf(v[r] * gsc, -57344.f), 57344.f);
+        }
+        int p = __builtin_amdgcn_cvt_pk_bf8_f32(sv[0], sv[1], 0, false);
+        pk = (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(sv[2], sv[3], p, true);
+      }
+    };
 #pragma unroll
     for (int j = 0; j < MB; ++j) {
       if constexpr (RES) {
@@ -248,70 +365,47 @@ struct ConvEpilogue {
       if (mrow + j * 16 >= a.M) continue;
       uint32_t bits = 0u;
 #pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        f32x4 v = acc[i][j];
-        if constexpr (RES) {  // acc + bias + res (forward), acc + res (dgrad)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            v[r] = (BASE == MODE_BIAS_RELU ? v[r] + bb[i][r] : v[r]) + (float)rs[j % RG][i][r];
+      for (int i = 0; i + 1 < NBP; i += 2) {
+        uint2 o0, o1;
+        uint32_t p0 = 0u, p1 = 0u;
+        block(i, j, o0, p0, bits);
+        block(i + 1, j, o1, p1, bits);
+        const auto sx = __builtin_amdgcn_permlane16_swap(o0.x, o1.x, false, false);
+        const auto sy = __builtin_amdgcn_permlane16_swap(o0.y, o1.y, false, false);
+        u32x4_a8 q;
+        q[0] = sx[0];
+        q[1] = sy[0];
+        q[2] = sx[1];
+        q[3] = sy[1];
+#ifdef AGK_DEBUG
+        const long long yo = (long long)ooff[j] + i * 16 + po;
+        if (AGK_DCHECK(yo >= 0 && yo + 8 <= a.y_elems, DBG_FWD_Y)) *(u32x4_a8*)(a.y + yo) = q;
+#else
+        *(u32x4_a8*)(a.y + ooff[j] + i * 16 + po) = q;
+#endif
+        if constexpr (E5M2) {
+          const auto sp = __builtin_amdgcn_permlane16_swap(p0, p1, false, false);
+          u32x2_a4 q8;
+          q8[0] = sp[0];
+          q8[1] = sp[1];
+          *(u32x2_a4*)(a.y_bf8 + ooff[j] + i * 16 + po) = q8;
         }
-        if constexpr (BASE == MODE_BIAS_RELU && RES) {
-          v[0] = fmaxf(v[0], 0.f);
-          v[1] = fmaxf(v[1], 0.f);
-          v[2] = fmaxf(v[2], 0.f);
-          v[3] = fmaxf(v[3], 0.f);
-        } else if constexpr (BASE == MODE_BIAS_RELU) {
-          v[0] = fmaxf(v[0] + bb[i][0], 0.f);
-          v[1] = fmaxf(v[1] + bb[i][1], 0.f);
-          v[2] = fmaxf(v[2] + bb[i][2], 0.f);
-          v[3] = fmaxf(v[3] + bb[i][3], 0.f);
-        } else if constexpr (BASE == MODE_MASK) {
-          v[0] = (float)mk[i][j][0] > 0.f ? v[0] : 0.f;
-          v[1] = (float)mk[i][j][1] > 0.f ? v[1] : 0.f;
-          v[2] = (float)mk[i][j][2] > 0.f ? v[2] : 0.f;
-          v[3] = (float)mk[i][j][3] > 0.f ? v[3] : 0.f;
-        } else if constexpr (BASE == MODE_MASKBITS) {
+      }
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = ((mw[j] >> (4 * i + r)) & 1u) ? v[r] : 0.f;
-        }
-        bf16x4 o;
-        o[0] = (__bf16)v[0];
-        o[1] = (__bf16)v[1];
-        o[2] = (__bf16)v[2];
-        o[3] = (__bf16)v[3];
-        if constexpr (BASE == MODE_BIAS_RELU) {
-          // the bit records what the bf16 value the dgrad would re-read says: y > 0
-#pragma unroll
-          for (int r = 0; r < 4; ++r) bits |= ((float)o[r] > 0.f ? 1u : 0u) << (4 * i + r);
-        }
+      for (int i = NBP / 2 * 2; i < NB; ++i) {  // unpaired blocks: the last one of an odd NB, all with a skip operand
+        uint2 o0;
+        uint32_t p0 = 0u;
+        block(i, j, o0, p0, bits);
 #ifdef AGK_DEBUG
         const long long yo = (long long)ooff[j] + i * 16;
-        if (AGK_DCHECK(yo >= 0 && yo + 4 <= a.y_elems, DBG_FWD_Y)) *(bf16x4*)(a.y + yo) = o;
+        if (AGK_DCHECK(yo >= 0 && yo + 4 <= a.y_elems, DBG_FWD_Y)) *(uint2*)(a.y + yo) = o0;
 #else
-        *(bf16x4*)(a.y + ooff[j] + i * 16) = o;
+        *(uint2*)(a.y + ooff[j] + i * 16) = o0;
 #endif
-        if constexpr (BF8) {
-          if (a.y_bf8) {  // wave-uniform
-            float sv[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              gmax = fmaxf(gmax, fabsf(v[r]));
-              sv[r] = fminf(fmaxf(v[r] * gsc, -57344.f), 57344.f);
-            }
-            int pk = __builtin_amdgcn_cvt_pk_bf8_f32(sv[0], sv[1], 0, false);
-            pk = __builtin_amdgcn_cvt_pk_bf8_f32(sv[2], sv[3], pk, true);
-            *(int*)(a.y_bf8 + ooff[j] + i * 16) = pk;
-          }
-        }
+        if constexpr (E5M2) *(uint32_t*)(a.y_bf8 + ooff[j] + i * 16) = p0;
       }
-      if constexpr (BASE == MODE_BIAS_RELU)
-        if (a.mbits_out) a.mbits_out[(size_t)pix[j] * mwords + mslot] = bits;
-    }
-    if constexpr (BF8) {
-      if (a.y_bf8 && a.bf8_amax) {
-        gmax = wave_max(gmax);
-        if ((threadIdx.x & 63) == 0 && gmax > 0.f) atomicMax(a.bf8_amax + (blockIdx.x & 63), __float_as_uint(gmax));
-      }
+      if constexpr (BITS != 0)
+        if (BITS == 1 || a.mbits_out) a.mbits_out[(size_t)pix[j] * mwords + mslot] = bits;
     }
   }
 };
@@ -321,6 +415,7 @@ __device__ __forceinline__ void conv_store_tile(const ConvFwdArgs& a, const f32x
                                                 int nbase, int wn) {
   ConvEpilogue<NB, MB, MODE> ep;
   ep.load(a, mrow, nbase, wn);
+  ep.settle();
   ep.store(a, acc, mrow);
 }
 

@@ -510,6 +510,7 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_pp_kernel(ConvFwdArgs a) {
     }
   }
   if (grp == 0) __builtin_amdgcn_s_barrier();  // equal barrier counts
+  ep.settle();
   ep.store(a, acc, ep_mrow);
 }
 
@@ -701,6 +702,7 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_halo2_kernel(ConvFwdArgs a) {
     t = tn;
     c = cn;
   }
+  ep.settle();
   ep.store(a, acc, ep_mrow);
 }
 
@@ -935,6 +937,7 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_hpp_kernel(ConvFwdArgs a) {
   }
 #undef HPP_STAMP
   if (grp == 0) __builtin_amdgcn_s_barrier();
+  ep.settle();
   ep.store(a, acc, ep_mrow);
 }
 

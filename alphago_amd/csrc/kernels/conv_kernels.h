@@ -239,6 +239,7 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_kernel(ConvFwdArgs a
       mfmas(xb, wb);
       __builtin_amdgcn_s_setprio(0);
     }
+    ep.settle();
     ep.store(a, acc, ep_mrow);
     return;
   }
@@ -395,6 +396,7 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_kernel(ConvFwdArgs a
       __syncthreads();
     }
     ep.load(a, ep_mrow, ep_nbase, wn);
+    ep.settle();
     ep.store(a, acc, ep_mrow);
     return;
   }
@@ -414,6 +416,7 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_kernel(ConvFwdArgs a
       __syncthreads();
     }
     ep.load(a, ep_mrow, ep_nbase, wn);
+    ep.settle();
     ep.store(a, acc, ep_mrow);
     return;
   }
@@ -436,6 +439,7 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_kernel(ConvFwdArgs a
   }
 
   // --- epilogue: lane owns channels n..n+3 of pixel m for every (i, j) block
+  ep.settle();
   ep.store(a, acc, ep_mrow);
 }
 
@@ -482,7 +486,8 @@ struct IntC {
   static constexpr int value = V;
 };
 
-template <int BN, int MODE>
+// STAMP (kernel lab, the op's stamp buffer): four cycle counts per wave around the epilogue, see the end
+template <int BN, int MODE, bool STAMP = false>
 __global__ __launch_bounds__(512, 1) void conv_fwd_halo384_kernel(ConvFwdArgs a) {
   constexpr int BM = H384_BM, MB = 6, NW = 8;
   constexpr int NB = BN / 32;
@@ -498,6 +503,8 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_halo384_kernel(ConvFwdArgs a)
   char* const hbuf = smem;
   char* const wbuf = smem + 2 * H_BYTES;
 
+  unsigned long long t_begin = 0;
+  if constexpr (STAMP) t_begin = __builtin_amdgcn_s_memtime();
   const int lane = threadIdx.x & 63;
   const int wave = wave_id();
   const int wm = wave >> 1, wn = wave & 1;
@@ -674,7 +681,33 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_halo384_kernel(ConvFwdArgs a)
   asm volatile("" : "+v"(ep_mrow));
   const int ep_nbase = n0 + wn * (BN / 2) + ((lane >> 4) << 2);
   ConvEpilogue<NB, MB, MODE> ep;
+  if constexpr (STAMP) {
+    // diagnostic instantiation: cycles from the K loop's last barrier to (1) the operands settled, (2) the
+    // last store issued, (3) every store acknowledged, and the wave's whole time; the debug buffer only
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+    __builtin_amdgcn_sched_barrier(0);
+    ep.load(a, ep_mrow, ep_nbase, wn);
+    ep.settle();
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+    __builtin_amdgcn_sched_barrier(0);
+    ep.store(a, acc, ep_mrow);
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned long long t2 = __builtin_amdgcn_s_memtime();
+    wait_vmcnt0();
+    const unsigned long long t3 = __builtin_amdgcn_s_memtime();
+    if (lane == 0) {
+      unsigned long long* d = a.dbg + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * NW + wave) * 4;
+      d[0] = t1 - t0;
+      d[1] = t2 - t0;
+      d[2] = t3 - t0;
+      d[3] = t3 - t_begin;
+    }
+    return;
+  }
   ep.load(a, ep_mrow, ep_nbase, wn);
+  ep.settle();
   ep.store(a, acc, ep_mrow);
 }
 
@@ -693,6 +726,15 @@ static void launch_fwd_halo384(const ConvFwdArgs& a, hipStream_t st) {
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
     dim3 grid((a.M + H384_BM - 1) / H384_BM, a.Cout / BN);
+#ifdef AGK_KERNEL_LAB
+    if (a.dbg) {  // diagnostic instantiation with epilogue stamps: 4 counts per wave, 8 waves per workgroup
+      static const hipError_t attr_d = hipFuncSetAttribute((const void*)conv_fwd_halo384_kernel<BN, MODE, true>,
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+      hip_check(attr_d, "hipFuncSetAttribute(max dynamic LDS)");
+      hipLaunchKernelGGL((conv_fwd_halo384_kernel<BN, MODE, true>), grid, dim3(512), smem, st, a);
+      return;
+    }
+#endif
     hipLaunchKernelGGL((conv_fwd_halo384_kernel<BN, MODE>), grid, dim3(512), smem, st, a);
   } else {
     throw std::invalid_argument("conv_fwd: tile 388 is the 192-wide forward / bitmask dgrad");
@@ -927,6 +969,7 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_pk_kernel(ConvFwdArg
     __syncthreads();
   }
   ep.load(a, ep_mrow, ep_nbase, wn);
+  ep.settle();
   ep.store(a, acc, ep_mrow);
 }
 

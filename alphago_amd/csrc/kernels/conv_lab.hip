@@ -172,6 +172,7 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_ga_kernel(ConvFwdArgs a) {
       for (int j = 0; j < MB; ++j) ah[i][j] = acc[h * NH + i][j];
     ConvEpilogue<NH, MB, MODE> ep;
     ep.load(a, mrow, n0 + h * (BN / 2) + ((lane >> 4) << 2), h);
+    ep.settle();
     ep.store(a, ah, mrow);
   }
 }
