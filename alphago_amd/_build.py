@@ -174,7 +174,7 @@ def hip_compile_flags(flavor: str = "prod"):
         "-Wno-deprecated-declarations",
     ] + {"prod": [], "debug": ["-DAGK_DEBUG=1"],
          "lab": ["-DAGK_KERNEL_LAB=1", "-Dagk=agk_lab", "-Dagk_ops=agk_lab_ops"]}[flavor]
-    hip_flags = ["--offload-arch=" + ARCH, "-fgpu-rdc" if False else "-fno-gpu-rdc", "-munsafe-fp-atomics"]
+    hip_flags = ["--offload-arch=" + ARCH, "-fno-gpu-rdc", "-munsafe-fp-atomics"]
     inc_flags = ["-I" + p for p in incs] + ["-I" + os.path.join(CSRC, "kernels"), "-I" + sysconfig.get_paths()["include"]]
     return common, hip_flags, inc_flags, libdir
 

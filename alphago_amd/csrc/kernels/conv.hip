@@ -16,6 +16,9 @@
 //   consecutive output channels of one pixel: the epilogue (bias + ReLU, or the
 //   ReLU-derivative mask for dgrad) stores 8 bytes per lane.
 //   The same kernel computes dgrad with flipped/transposed packed weights.
+//   A tile code names one tile description (conv_kernels.h: Tile36 ... Tile388; pixels per workgroup,
+//   wave tile, K loop, K order, LDS slots); FwdTiles below lists the codes of each output width,
+//   fwd_resolve_tile holds the automatic rule, conv_fwd_tile_info reports the tile that runs.
 //
 // conv_wgrad_kernel dW_t[n][c] = sum_m dZ[m][n] * X[m + shift_t][c]
 //   K = pixels (split over workgroups), tile 192(n) x 192(c) per workgroup for
@@ -31,6 +34,8 @@
 //   stage's MFMAs are issued; the DMA takes a scalar base and a 32-bit lane offset, the
 //   fragment reads immediate offsets.  The bias pixel sums are dealt out over the taps'
 //   workgroups: one 16-channel block per (tap, wave column) of the c0 == 0 column.
+//   A wgrad tile is one description too (WgradTap, WgradRow, WgradRow48, ...); the launcher run without
+//   launching (wgrad_choose) is what wgrad_plan tells the trainers.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,104 +49,112 @@ namespace agk {
 
 // ----------------------------------------------------------------- forward launchers
 
-// 160-wide output tile (value net: 152 filters padded to 160 instead of 192);
-// Cin % 64 == 32 uses straddled K-steps
-template <int MODE, bool STR>
-static void launch_fwd_160(const ConvFwdArgs& a, int bm, hipStream_t st) {
-  if (bm == 384) launch_fwd_bm<160, MODE, 384, 6, false, false, false, false, STR>(a, st);
-  else if (bm == 385) launch_fwd_bm<160, MODE, 384, 6, false, false, false, true, STR>(a, st);
-  else if (bm == 386 || bm == 388) launch_fwd_bm<160, MODE, 384, 6, false, false, false, true, STR, true>(a, st);  // 388: not covered
-  else if (bm == 387) launch_fwd_bm<160, MODE, 384, 6, false, false, false, false, STR, true>(a, st);
-  else if (bm == 256) launch_fwd_bm<160, MODE, 256, 4, true, true, false, false, STR>(a, st);
-  else if (bm == 128) launch_fwd_bm<160, MODE, 128, 4, true, true, false, false, STR>(a, st);
-  else if (bm == 64) launch_fwd_bm<160, MODE, 64, 2, true, true, false, false, STR>(a, st);
-#ifdef AGK_KERNEL_LAB  // LDS-ring tiles (round 4: slower or equal at small batches, kernel lab)
-  else if (bm == 65) launch_fwd_bm<160, MODE, 64, 2, true, true, false, false, STR, false, 4>(a, st);
-  else if (bm == 130) launch_fwd_bm<160, MODE, 128, 4, true, true, false, false, STR, false, 3>(a, st);
+// The dispatch table: the tile codes an output width takes (conv_kernels.h has the types, docs/ARCHITECTURE.md
+// the table in words).  160-wide (the value net: 152 filters padded to 160, straddled K-steps when
+// Cin % 64 == 32) has no 37 and no compact-halo tile (388 runs 386 there, fwd_resolve_tile); 65 / 130 exist in
+// the kernel lab only.
+// ORDER: dispatch does not depend on it, but the code object does.  The compiler emits the kernels in the order
+// with_tile's left fold names them, and scripts/isa_compare.py pairs the kernels of two builds by position.
+// Reordering a list (or turning the fold around) changes no kernel and still fails that comparison against an
+// older build, so both lists keep the order of the if-chains they replaced.
+template <class... T>
+struct TileList {};
+#ifdef AGK_KERNEL_LAB
+#define AGK_LAB_RING_TILES Tile65, Tile130,
+#else
+#define AGK_LAB_RING_TILES
 #endif
-  else if (bm == 38) launch_fwd_splitk<160, MODE, STR>(a, st);  // split-K (small value-net batches)
-  else if (bm == 36) launch_fwd_bm<160, MODE, 32, 1, true, true, false, false, STR>(a, st);  // 32 pixels, 4 waves
-  else throw std::invalid_argument("conv_fwd: 160-wide tiles support tile codes 36 / 38 / 64 / 128 / 256 / 384-387");
+template <int BN>
+struct FwdTiles {
+  using type = TileList<Tile384, Tile256, Tile128, Tile64, Tile36, Tile38, Tile37, AGK_LAB_RING_TILES Tile385, Tile386,
+                        Tile387, Tile388>;
+};
+template <>
+struct FwdTiles<160> {
+  using type = TileList<Tile384, Tile385, Tile386, Tile387, Tile256, Tile128, Tile64, AGK_LAB_RING_TILES Tile38, Tile36>;
+};
+#undef AGK_LAB_RING_TILES
+
+// f(Tile{}) for the list's tile with this code; false when the list has none
+template <class F, class... T>
+static bool with_tile(TileList<T...>, int code, F&& f) {
+  return (... || (code == T::CODE ? (f(T{}), true) : false));
 }
 
+// f(IntC<BN>{}) for the output-width tile of a layer: 160 (the value net), else the largest of 192 / 128 / 64
+// that divides Cout
+template <class F>
+static auto with_n_tile(int Cout, F&& f) {
+  if (Cout == 160) return f(IntC<160>{});
+  if (Cout % 192 == 0) return f(IntC<192>{});
+  if (Cout % 128 == 0) return f(IntC<128>{});
+  return f(IntC<64>{});
+}
+
+// The automatic rule (tile 0) and the one substitution of an explicit code.  Every threshold is a measured
+// crossover; the measurements are in profiles/: r2_dma_spread.md (385), r3_chunk_outer.md (386),
+// r3_small_batch.md (64 below 128 x 256 pixels), r4/README.md and r4/raw/tiles_160_graph.txt (36, and where
+// the 160-wide layers take it), r8/README.md (388 where 386 was).
+int fwd_resolve_tile(const FwdShape& g, int mode, int tile) {
+  const int bn = with_n_tile(g.Cout, [](auto bnc) { return decltype(bnc)::value; });
+  const bool halo = halo384_covers(bn, mode, g.S, g.K, g.Cin, g.Cout, g.offi);
+  if (tile == 388) return halo ? 388 : 386;  // shapes the compact-halo kernel does not cover run 386
+  if (tile != 0) return tile;
+  if (g.M < (bn == 160 ? 8192 : 64 * 256)) return 36;
+  if (g.M >= 384 * 512) return halo ? 388 : 386;
+  return g.M >= 256 * 512 ? 256 : g.M >= 128 * 256 ? 128 : 64;
+}
+
+[[noreturn]] static void fwd_unknown_tile(int bn, int code) {
+  if (bn == 160)
+    throw std::invalid_argument("conv_fwd: 160-wide tiles support tile codes 36 / 38 / 64 / 128 / 256 / 384-387");
+  throw std::invalid_argument("conv_fwd: unknown tile code " + std::to_string(code));
+}
+
+template <int BN, int MODE, bool STR>
+static void launch_fwd_code(const ConvFwdArgs& a, int code, hipStream_t st) {
+  if (with_tile(typename FwdTiles<BN>::type{}, code,
+                [&](auto tile) { launch_fwd_tile<BN, MODE, decltype(tile), STR>(a, st); }))
+    return;
+#ifdef AGK_KERNEL_LAB
+  // kernel-lab tile codes (conv_lab.hip, profiles/r1_fwd_kernel_experiments.md)
+  if (BN != 160 && launch_conv_fwd_lab(code, a, BN, MODE, st)) return;
+#endif
+  fwd_unknown_tile(BN, code);
+}
 
 template <int BN, int MODE>
 static void launch_fwd_t(const ConvFwdArgs& a, hipStream_t st) {
-  int bm = a.tile;
-  // forward and dgrad: 96x96-per-wave tiles (147 KB LDS).  dgrad used to keep
-  // a 112-KB tile so that a wgrad workgroup (48 KB) could share its CU, but the
-  // concurrent pair is bound by the same per-CU operand delivery either way;
-  // the larger tile moves fewer bytes per MFMA (bench: 106.2k -> 108.5k pos/s,
-  // scripts/bench_variants.sh).
-  // automatic: 385 (the 384 tile with its DMA spread through the MFMAs);
-  // alternating A/B, serial backward: SL 121.5-121.9k vs 120.0-120.7k pos/s,
-  // value (160-wide, straddled K-steps) 140.1k vs 136.7k bf16 (profiles/r2_dma_spread.md)
-  // automatic (round 3): 386 = 385 with the chunk-outer K order.  10 s power-limited runs at
-  // B = 2176 (profiles/r3_chunk_outer.md): 3x3 forward 515 -> 480 us, bitmask dgrad 497 -> 463 us;
-  // bench 120.8k -> 126.0k positions/s.  The 160-wide straddled tiles run the same order with the
-  // 32-channel tail chunk's steps pairing two taps.
-  // Small batches (round 3): below 128 x 256 pixels (B < 91 at 19 x 19) a 64-pixel tile on 4 waves
-  // (32 x BN/2 per wave) -- B = 16 fills 91 workgroups instead of 46 (profiles/r3_small_batch.md)
-  if (bm == 0) bm = (a.M >= 384 * 512) ? 386 : (a.M >= 256 * 512) ? 256 : (a.M >= 128 * 256) ? 128 : 64;
-  // 388 = 386 with the pixel rows staged once per 64-channel chunk (conv_fwd_halo384_kernel): 4 DMA
-  // pieces per wave and K-step instead of 9, bit-identical outputs.  Shapes it does not cover (not 3x3,
-  // S > 19, BN != 192, other epilogues) run 386.
-  // automatic (round 8) where 386 was: 10 s power-limited runs at B = 2176, 3x3 forward 484 -> 465 us,
-  // bitmask dgrad 468 -> 449 us; bench, three alternating pairs against the parent commit on one box,
-  // 126.7-127.0k -> 129.5-129.9k positions/s (+2.3 %, profiles/r8/README.md).  tile 386 keeps the old kernel.
-  if (a.tile == 0 && bm == 386 && halo384_covers<BN, MODE>(a)) bm = 388;
-  if (bm == 388 && !halo384_covers<BN, MODE>(a)) bm = 386;
-  // round 4: below 64 x 256 pixels (B <= 45 at 19 x 19) the 32-pixel tile on 4 waves (tile 36) -- twice
-  // the workgroups of the 64 tile; SL step at B = 16: 18.6k -> 19.7k positions/s (profiles/r4/README.md)
-  if (BN != 160 && a.tile == 0 && a.M < 64 * 256) bm = 36;
-  // the 160-wide value layers: 32-pixel tile below 8192 pixels (B <= 22); graph-timed per layer at
-  // B = 1 / 16 15.0 / 16.1 us vs 16.4 / 17.0 (tile 64), but 18.9 vs 17.7 at B = 32
-  // (profiles/r4/raw/tiles_160_graph.txt)
-  if (BN == 160 && a.tile == 0 && a.M < 8192) bm = 36;
+  const int code = fwd_resolve_tile({a.M, a.S, a.K, a.Cin, a.Cout, a.offi}, MODE, a.tile);
   if constexpr (BN == 160) {
-    if (a.Cin % 64 == 32) launch_fwd_160<MODE, true>(a, bm, st);
-    else launch_fwd_160<MODE, false>(a, bm, st);
+    if (a.Cin % 64 == 32) launch_fwd_code<160, MODE, true>(a, code, st);
+    else launch_fwd_code<160, MODE, false>(a, code, st);
   } else {
     if (a.Cin % 64 != 0) throw std::invalid_argument("conv_fwd: Cin % 64 == 32 needs the 160-wide tile");
-    // production tile codes: 128 / 256 (64-pixel waves), 384 / 385 (96x96 per wave;
-    // 385 = default, DMA spread through the MFMAs)
-    if (bm == 384) launch_fwd_bm<BN, MODE, 384, 6, false, false>(a, st);
-    else if (bm == 256) launch_fwd_bm<BN, MODE, 256, 4>(a, st);
-    else if (bm == 128) launch_fwd_bm<BN, MODE, 128, 4>(a, st);
-    else if (bm == 64) launch_fwd_bm<BN, MODE, 64, 2>(a, st);
-    // 32-pixel tiles (twice the workgroups of the 64 tile at small batches): 36 = 4 waves of 16 x BN/2,
-    // 37 = 2 waves of 32 x BN/2; same ReLU' bitmask layout
-    else if (bm == 36) launch_fwd_bm<BN, MODE, 32, 1>(a, st);
-    else if (bm == 38) launch_fwd_splitk<BN, MODE>(a, st);  // 36 with split-K (conv_fwd_splitk op)
-    else if (bm == 37) launch_fwd_bm<BN, MODE, 32, 2>(a, st);
-#ifdef AGK_KERNEL_LAB
-    // small batches: 65 / 130 = the 64 / 128-pixel tiles on a 4 / 3-slot LDS ring (NS above); measured
-    // slower or equal (round 4), kernel lab only
-    else if (bm == 65) launch_fwd_bm<BN, MODE, 64, 2, true, true, false, false, false, false, 4>(a, st);
-    else if (bm == 130) launch_fwd_bm<BN, MODE, 128, 4, true, true, false, false, false, false, 3>(a, st);
-#endif
-    // 385: the 384 tile with the next stage's LDS-DMA spread through the first
-    // k-half's MFMAs instead of issued as one burst (kernel-lab tile 9)
-    else if (bm == 385) launch_fwd_bm<BN, MODE, 384, 6, false, false, false, true>(a, st);
-    // 386 / 387: 385 / 384 with the chunk-outer K order (CO above)
-    else if (bm == 386) launch_fwd_bm<BN, MODE, 384, 6, false, false, false, true, false, true>(a, st);
-    else if (bm == 387) launch_fwd_bm<BN, MODE, 384, 6, false, false, false, false, false, true>(a, st);
-    else if (bm == 388) launch_fwd_halo384<BN, MODE>(a, st);
-#ifdef AGK_KERNEL_LAB
-    // kernel-lab tile codes (conv_lab.hip, profiles/r1_fwd_kernel_experiments.md)
-    else if (launch_conv_fwd_lab(bm, a, BN, MODE, st)) return;
-#endif
-    else throw std::invalid_argument("conv_fwd: unknown tile code " + std::to_string(bm));
+    launch_fwd_code<BN, MODE, false>(a, code, st);
   }
 }
 
+// {resolved code, BM, waves, threads, LDS bytes, loop kind (FwdLoop), chunk-outer, LDS slots} of the tile
+// launch_conv_fwd would run -- read from the type the launcher instantiates.  The codes of this file only: the
+// kernel lab's own codes (conv_lab.hip: 7 - 10, 2560, 2568 and the variant kernels) raise here though they launch
+void conv_fwd_tile_info(const FwdShape& g, int mode, int tile, int out[8]) {
+  const int code = fwd_resolve_tile(g, mode, tile);
+  with_n_tile(g.Cout, [&](auto bnc) {
+    constexpr int BN = decltype(bnc)::value;
+    const bool known = with_tile(typename FwdTiles<BN>::type{}, code, [&](auto tile) {
+      using T = decltype(tile);
+      using G = FwdGeo<T, BN>;
+      const int v[8] = {T::CODE, T::BM, G::WAVES, G::THREADS, G::LDS_BYTES, (int)T::LOOP, T::CHUNK_OUTER, T::SLOTS};
+      std::copy(v, v + 8, out);
+    });
+    if (!known) fwd_unknown_tile(BN, code);
+  });
+}
 
 template <int MODE>
 static void launch_fwd_mode(const ConvFwdArgs& a, hipStream_t st) {
-  if (a.Cout == 160) launch_fwd_t<160, MODE>(a, st);
-  else if (a.Cout % 192 == 0) launch_fwd_t<192, MODE>(a, st);
-  else if (a.Cout % 128 == 0) launch_fwd_t<128, MODE>(a, st);
-  else launch_fwd_t<64, MODE>(a, st);
+  with_n_tile(a.Cout, [&](auto bnc) { launch_fwd_t<decltype(bnc)::value, MODE>(a, st); });
 }
 
 void launch_conv_fwd(const ConvFwdArgs& a_in, int mode, hipStream_t st) {
@@ -185,12 +198,8 @@ void launch_conv_fwd(const ConvFwdArgs& a_in, int mode, hipStream_t st) {
 template <int BN>
 static void launch_fwd_pk_t(const ConvFwdArgs& a, int cpt, hipStream_t st) {
   constexpr int BM = 384, MBW = 6;
-  constexpr int smem = 2 * (BM * 128 + BN * 128);
-  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_fwd_pk_kernel<BN, BM, MBW>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
-  dim3 grid((a.M + BM - 1) / BM, a.Cout / BN);
-  hipLaunchKernelGGL((conv_fwd_pk_kernel<BN, BM, MBW>), grid, dim3(BM / MBW * 8), smem, st, a, cpt);
+  const dim3 grid((a.M + BM - 1) / BM, a.Cout / BN);
+  launch_dyn_lds<conv_fwd_pk_kernel<BN, BM, MBW>, BM / MBW * 8, 2 * (BM * 128 + BN * 128)>(grid, st, a, cpt);
 }
 
 void launch_conv_fwd_pk(const ConvFwdArgs& a_in, int cpt, hipStream_t st) {
@@ -198,94 +207,51 @@ void launch_conv_fwd_pk(const ConvFwdArgs& a_in, int cpt, hipStream_t st) {
   a.divSS = make_fastdiv((uint32_t)(a.S * a.S));
   a.divS = make_fastdiv((uint32_t)a.S);
   if (cpt < 4 || cpt > 8 || a.Cin != 64) throw std::invalid_argument("conv_fwd_pk: 32 < cin_real <= 64 in a 64-channel input");
-  if (a.Cout == 160) launch_fwd_pk_t<160>(a, cpt, st);
-  else if (a.Cout % 192 == 0) launch_fwd_pk_t<192>(a, cpt, st);
-  else if (a.Cout % 128 == 0) launch_fwd_pk_t<128>(a, cpt, st);
-  else launch_fwd_pk_t<64>(a, cpt, st);
+  with_n_tile(a.Cout, [&](auto bnc) { launch_fwd_pk_t<decltype(bnc)::value>(a, cpt, st); });
 }
 #endif  // AGK_KERNEL_LAB
 
-// ----------------------------------------------------------------- wgrad launchers
+// ----------------------------------------------------------------- wgrad: choice and launchers
+// launch_conv_wgrad and wgrad_choose are ONE walk over the launchers below.  A launch runs the kernel of the
+// tile it arrives at; a choice (WgradRun::plan) records that tile's constants and its grid instead, so what
+// wgrad_plan tells the trainers is what the launch does.
+struct WgradRun {
+  const ConvWgradArgs& a;
+  hipStream_t st;
+  WgradChoice* plan;  // non-null: record the choice, launch nothing
+};
 
+template <class C>
+static void wgrad_run(const WgradRun& r, dim3 grid) {
+  if (r.plan) *r.plan = {C::TAPS, (int)(grid.y * grid.z), C::PER_CU, WgradGeo<C>::THREADS, C::WN, C::WC, WgradGeo<C>::LDS_BYTES};
+  else launch_wgrad_cfg<C>(r.a, grid, r.st);
+}
 
-
-// The thin first layer's kernel rows run one workgroup per CU (180 VGPRs on 6 waves): ~1.16 us per
-// 32-pixel stage, 26-29 % MFMA busy (profiles/r3_final/pmc).  Round-4 variants, kernel lab only since
-// round 5 (torch.ops.alphago_amd_lab.conv_wgrad variant argument; in-step times at B = 2176,
-// profiles/r4/README.md):
-//   10: 12 waves (4 n x 3 c, 48 x 48 per wave per tap, 104 VGPRs): 559 us vs 556 us;
-//   11: the 6 waves with unit pipelining (wgrad_tile UP: the next tap's x fragments are read under
-//       the current tap's MFMAs; after the barrier only the dz fragments and tap 0 are exposed): 557 us;
-//   12: 12 waves with unit pipelining: 556 us.
-// Measured and removed: the 6 waves on a 4-slot LDS ring (601 us), 12 waves + UP capped at 85 VGPRs
-// for two workgroups per CU (56 B spilled, bench -4.5 %), UP on the 3x3 per-tap kernel (517 vs 500 us).
-template <int WN, int TAPS, int MW, int NWN = 2, int NS = 2, bool UP = false>
-static void launch_wgrad_taps48(const ConvWgradArgs& a_in, hipStream_t st) {
-  constexpr int smem = NS * (WN + 48 * TAPS) * 64 * kWgradKsub;
-  constexpr int threads = 64 * 3 * NWN;
-  static const hipError_t attr48 = hipFuncSetAttribute(
-      (const void*)conv_wgrad_kernel<WN, 48, kWgradKsub, 3, TAPS, false, false, false, NS, MW, NWN, UP>,
-      hipFuncAttributeMaxDynamicSharedMemorySize, smem);  // once per instantiation (thread-safe static)
-  hip_check(attr48, "hipFuncSetAttribute(max dynamic LDS)");
-  const ConvWgradArgs& a = a_in;
-  dim3 grid(a.nsplit, a.T / TAPS, a.Cout / WN);
-  hipLaunchKernelGGL((conv_wgrad_kernel<WN, 48, kWgradKsub, 3, TAPS, false, false, false, NS, MW, NWN, UP>), grid,
-                     dim3(threads), smem, st, a);
+// kernel rows: grid = splits x rows x channel blocks (the 48-wide c tile covers the layer's real planes)
+template <class C>
+static void wgrad_run_rows(const WgradRun& r) {
+  const ConvWgradArgs& a = r.a;
+  wgrad_run<C>(r, dim3(a.nsplit, a.T / C::TAPS, (a.Cout / C::WN) * (C::WC == 48 ? 1 : a.Cin / C::WC)));
 }
 
 template <int WN, int TAPS>
-static void launch_wgrad_taps(const ConvWgradArgs& a, hipStream_t st) {
-  if (a.cin_real <= 48) {
-    // thin first layer (48 real planes padded to 64): a 48-wide c tile on 6
-    // waves (2 n x 3 c) skips the zero channels -- 25% fewer MFMAs and x bytes
-    // on the backward's serial tail; the slab columns 48..63 stay unwritten
-    // (the reduce reads only cin_real of them)
+static void launch_wgrad_rows(const WgradRun& r) {
+  if (r.a.cin_real <= 48) {  // thin first layer (48 real planes padded to 64): the slab columns 48..63 stay
+                             // unwritten (the reduce reads only cin_real of them)
 #ifdef AGK_KERNEL_LAB  // round-4 re-cuts of this kernel (equal or slower): variants 10-12, 13 = two per CU
-    if (TAPS == 5 && a.variant == 13) {
-      launch_wgrad_taps48<WN, TAPS, 3>(a, st);
-      return;
-    }
+    if (TAPS == 5 && r.a.variant == 13) return wgrad_run_rows<WgradRow48TwoPerCu<WN, TAPS>>(r);
     if constexpr (TAPS == 5 && (WN / 16) % 4 == 0) {
-      if (a.variant == 10) {
-        launch_wgrad_taps48<WN, TAPS, 0, 4>(a, st);
-        return;
-      }
-      if (a.variant == 12) {
-        launch_wgrad_taps48<WN, TAPS, 0, 4, 2, true>(a, st);
-        return;
-      }
-
+      if (r.a.variant == 10) return wgrad_run_rows<WgradRow48Waves12<WN, TAPS, false>>(r);
+      if (r.a.variant == 12) return wgrad_run_rows<WgradRow48Waves12<WN, TAPS, true>>(r);
     }
     if constexpr (TAPS == 5) {
-      if (a.variant == 11) {
-        launch_wgrad_taps48<WN, TAPS, 0, 2, 2, true>(a, st);
-        return;
-      }
+      if (r.a.variant == 11) return wgrad_run_rows<WgradRow48UnitPipe<WN, TAPS>>(r);
     }
 #endif
-    if constexpr (TAPS == 5 && WN == 192) {
-      // round 5: the 5x5 first layer as 96-channel halves of the output rows -- half the accumulators
-      // per wave (104 VGPRs instead of 180), so two workgroups share a CU and one resident round covers
-      // the grid (51 splits instead of two rounds of 102): 552.9 -> 489.8 us in the B = 2176 step, its
-      // split-K slab halved (reduce 205.5 -> 188.3 us per step), bench +0.6 % (profiles/r5/README.md)
-      launch_wgrad_taps48<96, TAPS, 0>(a, st);
-      return;
-    }
-    launch_wgrad_taps48<WN, TAPS, 0>(a, st);
-    return;
+    if constexpr (TAPS == 5 && WN == 192) return wgrad_run_rows<WgradRow48<96, TAPS>>(r);  // as 96-wide halves
+    return wgrad_run_rows<WgradRow48<WN, TAPS>>(r);
   }
-  constexpr int smem = 2 * (WN + 64 * TAPS) * 64 * kWgradKsub;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_wgrad_kernel<WN, 64, kWgradKsub, 4, TAPS>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, smem);  // once per instantiation (thread-safe static)
-  hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
-  dim3 grid(a.nsplit, a.T / TAPS, (a.Cout / WN) * (a.Cin / 64));
-  hipLaunchKernelGGL((conv_wgrad_kernel<WN, 64, kWgradKsub, 4, TAPS>), grid, dim3(512), smem, st, a);
-}
-
-int wgrad_tap_group(int Cout, int Cin, int K, int variant) {
-  const bool c64 = (Cin != 160 && Cin % 192 != 0 && Cin % 128 != 0) || variant == kWgradSmall;
-  (void)Cout;
-  return (c64 && (variant == 0 || variant == kWgradSmall) && (K == 3 || K == 5)) ? K : 1;
+  wgrad_run_rows<WgradRow<WN, TAPS>>(r);
 }
 
 #ifdef AGK_KERNEL_LAB
@@ -293,20 +259,12 @@ int wgrad_tap_group(int Cout, int Cin, int K, int variant) {
 // tile geometries whose waves stage equal piece counts (192 x 192, 128 x 128, 160 x 160); the SL step at
 // B = 16 measured 0.901 ms with it against 0.863 ms without (round 4): kernel lab only
 template <int WN, int WC, int NWC>
-static bool launch_wgrad_ring(const ConvWgradArgs& a, dim3 grid, hipStream_t st) {
-  constexpr int KS = kWgradKsub;
+static bool launch_wgrad_ring(const WgradRun& r, dim3 grid) {
   constexpr int NWAVES = 2 * NWC;
   constexpr int NINSTR = WN / 16 + WC / 16;
   constexpr int IPW = (NINSTR + NWAVES - 1) / NWAVES;
   if constexpr ((WN / 16) % IPW == 0 && NINSTR == NWAVES * IPW) {
-    constexpr int NS = 4;
-    constexpr int smem = NS * (WN + WC) * 64 * KS;
-    static const hipError_t attr = hipFuncSetAttribute(
-        (const void*)conv_wgrad_kernel<WN, WC, KS, NWC, 1, false, false, false, NS>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
-    hipLaunchKernelGGL((conv_wgrad_kernel<WN, WC, KS, NWC, 1, false, false, false, NS>), grid, dim3(64 * NWAVES),
-                       smem, st, a);
+    wgrad_run<WgradRing<WN, WC, NWC>>(r, grid);
     return true;
   }
   return false;
@@ -314,46 +272,35 @@ static bool launch_wgrad_ring(const ConvWgradArgs& a, dim3 grid, hipStream_t st)
 #endif  // AGK_KERNEL_LAB
 
 template <int WN, int WC>
-static void launch_wgrad_t(const ConvWgradArgs& a, hipStream_t st) {
+static void launch_wgrad_t(const WgradRun& r) {
+  const ConvWgradArgs& a = r.a;
   dim3 grid(a.nsplit, a.T, (a.Cout / WN) * (a.Cin / WC));
-  constexpr int KS = kWgradKsub;
-  constexpr int smem = 2 * (WN + WC) * 64 * KS;
 #ifdef AGK_KERNEL_LAB
-  if (WC != 64 && a.variant == 9 && launch_wgrad_ring<WN, WC, 4>(a, grid, st)) return;
-  if (a.variant != 9 && launch_conv_wgrad_lab(a, WN, WC, grid, st)) return;  // lab variants 2 / 3 / 4 (conv_lab.hip)
+  if (WC != 64 && a.variant == 9 && launch_wgrad_ring<WN, WC, 4>(r, grid)) return;
+  // lab variants 2 / 3 / 4 (conv_lab.hip)
+  if (a.variant != 9 && !r.plan && launch_conv_wgrad_lab(a, WN, WC, grid, r.st)) return;
 #else
-  if (a.variant != 0)
+  if (a.variant != 0 && !r.plan)
     throw std::invalid_argument("conv_wgrad: variant " + std::to_string(a.variant) + " is a kernel-lab variant");
 #endif
   if constexpr (WC == 64) {
     // tap-merged kernel rows (see conv_wgrad_kernel); lab variant 1 forces one tap per workgroup
     if (a.variant != 1 && (a.K == 3 || a.K == 5)) {
-      if (a.K == 3) launch_wgrad_taps<WN, 3>(a, st);
-      else launch_wgrad_taps<WN, 5>(a, st);
+      if (a.K == 3) launch_wgrad_rows<WN, 3>(r);
+      else launch_wgrad_rows<WN, 5>(r);
       return;
     }
   }
-  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_wgrad_kernel<WN, WC, KS>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     smem);  // once per instantiation (thread-safe static)
-  hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
-  hipLaunchKernelGGL((conv_wgrad_kernel<WN, WC, KS>), grid, dim3(512), smem, st, a);
+  wgrad_run<WgradTap<WN, WC>>(r, grid);
 }
 
-// 160 x 160 tile on 4 waves (2 n x 2 c, 80 x 80 per wave): the value net's
-// padded width; 40 KB of LDS, so several workgroups share a CU
-static void launch_wgrad_160x160(const ConvWgradArgs& a, hipStream_t st) {
+static void launch_wgrad_160x160(const WgradRun& r) {
+  const ConvWgradArgs& a = r.a;
 #ifdef AGK_KERNEL_LAB
-  if (a.variant == 9 && launch_wgrad_ring<160, 160, 2>(a, dim3(a.nsplit, a.T, 1), st)) return;
+  if (a.variant == 9 && launch_wgrad_ring<160, 160, 2>(r, dim3(a.nsplit, a.T, 1))) return;
 #endif
-  if (a.variant != 0) throw std::invalid_argument("conv_wgrad: 160-wide tiles have no production variants");
-  constexpr int KS = kWgradKsub;
-  constexpr int smem = 2 * (160 + 160) * 64 * KS;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_wgrad_kernel<160, 160, KS, 2>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
-  dim3 grid(a.nsplit, a.T, 1);
-  hipLaunchKernelGGL((conv_wgrad_kernel<160, 160, KS, 2>), grid, dim3(256), smem, st, a);
+  if (a.variant != 0 && !r.plan) throw std::invalid_argument("conv_wgrad: 160-wide tiles have no production variants");
+  wgrad_run<WgradTap160x160>(r, dim3(a.nsplit, a.T, 1));
 }
 
 int wgrad_stage_pixels() { return 32 * kWgradKsub; }
@@ -366,15 +313,13 @@ int wgrad_stage_pixels() { return 32 * kWgradKsub; }
 // pixels through an LDS double buffer of KS 32-pixel sub-steps (one barrier per 32 KS pixels) and
 // writes its fp32 sums straight into the OIHW gradient (wgrad_store, grad_w != nullptr): deterministic
 // (one workgroup per output element, fixed pixel order), no slab and no reduce launch.
-template <int WC, int NWC, int KS>
-static void launch_wgrad_direct_t(const ConvWgradArgs& a, hipStream_t st) {
-  constexpr int WN = 32;
-  constexpr int smem = 2 * (WN + WC) * 64 * KS;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_wgrad_kernel<WN, WC, KS, NWC>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
-  dim3 grid(1, a.T, (a.Cout / WN) * (a.Cin / WC));
-  hipLaunchKernelGGL((conv_wgrad_kernel<WN, WC, KS, NWC>), grid, dim3(64 * 2 * NWC), smem, st, a);
+template <int WC>
+static void launch_wgrad_direct_t(const ConvWgradArgs& a, int ksub, hipStream_t st) {
+  const dim3 grid(1, a.T, (a.Cout / 32) * (a.Cin / WC));
+  if (ksub == 1) launch_wgrad_cfg<WgradDirect<WC, 1>>(a, grid, st);
+  else if (ksub == 2) launch_wgrad_cfg<WgradDirect<WC, 2>>(a, grid, st);
+  else if (ksub == 8) launch_wgrad_cfg<WgradDirect<WC, 8>>(a, grid, st);
+  else launch_wgrad_cfg<WgradDirect<WC, 4>>(a, grid, st);
 }
 
 // c tile of the split-free plan: 48 (192-multiple widths; the first layer's 48 real planes of 64), else 32
@@ -398,23 +343,8 @@ void launch_conv_wgrad_direct(const ConvWgradArgs& a_in, int ksub, hipStream_t s
   wgrad_fill_steps(a);
   if (!a.grad_w || !wgrad_direct_supported(a.Cout, a.Cin, a.cin_real, a.K))
     throw std::invalid_argument("conv_wgrad_direct: needs grad_w, Cout % 32 == 0 and a 48 / 32 c tile");
-  const int wc = wgrad_direct_wc(a.Cin, a.cin_real);
-  if (wc == 48) {
-    if (ksub == 1) launch_wgrad_direct_t<48, 3, 1>(a, st);
-    else if (ksub == 2) launch_wgrad_direct_t<48, 3, 2>(a, st);
-    else if (ksub == 8) launch_wgrad_direct_t<48, 3, 8>(a, st);
-    else launch_wgrad_direct_t<48, 3, 4>(a, st);
-  } else {
-    if (ksub == 1) launch_wgrad_direct_t<32, 2, 1>(a, st);
-    else if (ksub == 2) launch_wgrad_direct_t<32, 2, 2>(a, st);
-    else if (ksub == 8) launch_wgrad_direct_t<32, 2, 8>(a, st);
-    else launch_wgrad_direct_t<32, 2, 4>(a, st);
-  }
-}
-
-// tap-pair / line-staged wgrads (variants 6-8): kernel lab (conv_lab.hip, profiles/r3_wgrad_pair.md)
-static bool wgrad_pair_applies(int Cout, int Cin, int cin_real, int K) {
-  return K == 3 && Cout == 192 && Cin == 192 && cin_real == Cin;
+  if (wgrad_direct_wc(a.Cin, a.cin_real) == 48) launch_wgrad_direct_t<48>(a, ksub, st);
+  else launch_wgrad_direct_t<32>(a, ksub, st);
 }
 
 #ifdef AGK_DEBUG
@@ -427,48 +357,76 @@ unsigned debug_error_fetch_and_clear(hipStream_t st) {
 }
 #endif
 
-void wgrad_plan(int Cout, int Cin, int cin_real, int K, int variant, int out[4]) {
-  if ((variant == 6 || variant == 8) && wgrad_pair_applies(Cout, Cin, cin_real, K)) {
-    // tap pairs: 4.5 workgroups per split (9 per two splits), one per CU -- reported as 9 per
-    // split pair and 2 per CU so that nsplit = CUs * out[2] / out[1] stays an integer division
-    out[0] = 2;
-    out[1] = 9;
-    out[2] = 2;
-    out[3] = 512;
+// the tile for a layer's widths (and, inside launch_wgrad_t, its kernel size and real planes)
+static void wgrad_dispatch(const WgradRun& r) {
+  const ConvWgradArgs& a = r.a;
+  if (a.variant == kWgradSmall) {
+    // small batches (ops.wgrad_config): 64 x 64 output tiles with the kernel row's taps merged -- three
+    // times the workgroups per pixel split of a 192 -> 192 layer
+    if (!r.plan && (a.Cout % 64 || a.Cin % 64 || a.cin_real != a.Cin || (a.K != 3 && a.K != 5)))
+      throw std::invalid_argument("conv_wgrad: the small-batch tiles need 64-multiple widths and a 3x3 / 5x5 kernel");
+    ConvWgradArgs s = a;
+    s.variant = 0;
+    s.cin_real = s.Cin;
+    launch_wgrad_t<64, 64>({s, r.st, r.plan});
     return;
   }
+  const bool n192 = a.Cout % 192 == 0, c192 = a.Cin % 192 == 0;
+  const bool n128 = a.Cout % 128 == 0, c128 = a.Cin % 128 == 0;
+  if (a.Cout == 160) {  // value net (152 filters padded to 160)
+    if (a.Cin == 160) launch_wgrad_160x160(r);
+    else if (a.Cin % 64 == 0 && a.Cin % 128 != 0 && a.Cin % 192 != 0) launch_wgrad_t<160, 64>(r);
+    else throw std::invalid_argument("conv_wgrad: Cout 160 supports Cin 160 or an odd multiple of 64");
+  } else if (a.Cin == 160) {
+    throw std::invalid_argument("conv_wgrad: Cin 160 needs Cout 160");
+  } else if (n192 && c192) launch_wgrad_t<192, 192>(r);
+  else if (n192 && c128) launch_wgrad_t<192, 128>(r);
+  else if (n192) launch_wgrad_t<192, 64>(r);
+  else if (n128 && c128) launch_wgrad_t<128, 128>(r);
+  else if (n128 && c192) launch_wgrad_t<128, 192>(r);
+  else if (n128) launch_wgrad_t<128, 64>(r);
+  else if (c192) launch_wgrad_t<64, 192>(r);
+  else if (c128) launch_wgrad_t<64, 128>(r);
+  else launch_wgrad_t<64, 64>(r);
+}
+
+// tap-pair / line-staged wgrads (variants 6-8): kernel lab (conv_lab.hip, profiles/r3_wgrad_pair.md)
+static bool wgrad_pair_applies(int Cout, int Cin, int cin_real, int K) {
+  return K == 3 && Cout == 192 && Cin == 192 && cin_real == Cin;
+}
+
+WgradChoice wgrad_choose(int Cout, int Cin, int cin_real, int K, int variant) {
+  // The kernel-lab variants, in this one place.  The production library answers for them as it always has
+  // (its launch raises for them): 6 / 8 where they apply are the tap pairs, 4.5 workgroups per split (9 per
+  // two splits) and one per CU -- reported as 9 per split pair and 2 per CU so that nsplit = CUs * per_cu /
+  // wgs_per_split stays an integer division; 1-4 are one tap per workgroup; 9 with one tap per workgroup is
+  // the 4-slot ring, one workgroup per CU; 5 where the kernel lab has a row geometry is one kernel row per
+  // workgroup, one per CU (~170 VGPRs, 8 or 6 waves); every other one is planned as the production tile.
+  if ((variant == 6 || variant == 8) && wgrad_pair_applies(Cout, Cin, cin_real, K)) return {2, 9, 2, 512, 192, 192, 147456};
 #ifdef AGK_KERNEL_LAB
-  const int code = variant == 5 ? wgrad_row_code(Cout, Cin, cin_real, K) : 0;
-  if (code) {  // one kernel row per workgroup, one workgroup per CU (~170 VGPRs, 8 or 6 waves)
-    out[0] = K;
-    out[1] = wgrad_row_wgs_per_split(code, Cout, Cin, cin_real, K);
-    out[2] = 1;
-    out[3] = 256;
-    return;
-  }
+  if (const int code = variant == 5 ? wgrad_row_code(Cout, Cin, cin_real, K) : 0)
+    return {K, wgrad_row_wgs_per_split(code, Cout, Cin, cin_real, K), 1, 256, 0, 0, 0};
 #endif
-  if (variant == kWgradSmall) {  // small batches: 64 x 64 tiles, tap-merged kernel rows (launch_conv_wgrad)
-    out[0] = wgrad_tap_group(Cout, Cin, K, variant);
-    out[1] = (K * K / out[0]) * (Cout / 64) * (Cin / 64);
-    out[2] = 2;
-    out[3] = 512;
-    return;
-  }
-  // per-tap kernel: tap-merged rows for 64-wide c tiles, else one tap; two workgroups per CU
-  const int taps = wgrad_tap_group(Cout, Cin, K, (variant >= 5 && variant <= 13) ? 0 : variant);
-  const bool c48 = cin_real <= 48 && Cin == 64;
-  int wn = Cout == 160 ? 160 : Cout % 192 == 0 ? 192 : Cout % 128 == 0 ? 128 : 64;
-  if (c48 && taps == 5 && wn == 192) wn = 96;  // the first layer's 96-wide halves (launch_wgrad_taps)
-  const int wc = Cout == 160 && Cin == 160 ? 160 : Cin % 192 == 0 ? 192 : Cin % 128 == 0 ? 128 : 64;
-  out[0] = taps;
-  out[1] = (K * K / taps) * (Cout / wn) * (c48 ? 1 : Cin / wc);
-  // resident workgroups per CU: two, except the 5x5 tap-merged 160 x 64 kernel (value layer 0,
-  // 49 planes), whose 154 VGPRs leave room for one 8-wave workgroup -- a grid sized for two ran
-  // as two rounds (251 us per step, profiles/r3_fp8_wgrad.md)
-  out[2] = (taps == 5 && wn == 160 && !c48) ? 1 : 2;
-  if (variant == 9 && taps == 1) out[2] = 1;  // the 4-slot ring: one workgroup per CU
-  // threads per workgroup
-  out[3] = c48 ? 384 : (wn == 160 && wc == 160) ? 256 : 512;
+  ConvWgradArgs a{};
+  a.Cout = Cout, a.Cin = Cin, a.cin_real = cin_real, a.K = K, a.T = K * K, a.nsplit = 1;
+  a.variant = variant == kWgradSmall ? variant : (variant >= 1 && variant <= 4) ? 1 : 0;
+  WgradChoice c{};
+  wgrad_dispatch({a, nullptr, &c});
+  if (variant == 9 && c.taps == 1) c.per_cu = 1;
+  // a thin layer that runs one tap per workgroup (no such layer in either net) has always been reported
+  // with the thin rows' 6 waves, though the 8-wave per-tap kernel runs it; nothing sizes a launch from it
+  if (c.taps == 1 && Cin == 64 && cin_real <= 48 && variant != kWgradSmall) c.threads = 384;
+  return c;
+}
+
+int wgrad_tap_group(int Cout, int Cin, int K, int variant) {
+  // (asked with a kernel-lab variant: one tap, as this has always answered)
+  return (variant == 0 || variant == kWgradSmall) ? wgrad_choose(Cout, Cin, Cin, K, variant).taps : 1;
+}
+
+void wgrad_plan(int Cout, int Cin, int cin_real, int K, int variant, int out[4]) {
+  const WgradChoice c = wgrad_choose(Cout, Cin, cin_real, K, variant);
+  out[0] = c.taps, out[1] = c.wgs_per_split, out[2] = c.per_cu, out[3] = c.threads;
 }
 
 void launch_conv_wgrad(const ConvWgradArgs& a_in, hipStream_t st) {
@@ -489,39 +447,12 @@ void launch_conv_wgrad(const ConvWgradArgs& a_in, hipStream_t st) {
     }
     a.variant = 0;
   }
-#endif
-#ifdef AGK_KERNEL_LAB
   if (a.variant >= 6 && a.variant <= 8) {  // tap pairs (8: DMA spread) / line-staged per-tap kernel
     if (wgrad_pair_applies(a.Cout, a.Cin, a.cin_real, a.K) && launch_conv_wgrad_line_lab(a, st)) return;
     a.variant = 0;
   }
 #endif
-  if (a.variant == kWgradSmall) {
-    // small batches (ops.wgrad_config): 64 x 64 output tiles with the kernel row's taps merged -- three
-    // times the workgroups per pixel split of a 192 -> 192 layer
-    if (a.Cout % 64 || a.Cin % 64 || a.cin_real != a.Cin || (a.K != 3 && a.K != 5))
-      throw std::invalid_argument("conv_wgrad: the small-batch tiles need 64-multiple widths and a 3x3 / 5x5 kernel");
-    a.variant = 0;
-    launch_wgrad_t<64, 64>(a, st);
-    return;
-  }
-  const bool n192 = a.Cout % 192 == 0, c192 = a.Cin % 192 == 0;
-  const bool n128 = a.Cout % 128 == 0, c128 = a.Cin % 128 == 0;
-  if (a.Cout == 160) {  // value net (152 filters padded to 160)
-    if (a.Cin == 160) launch_wgrad_160x160(a, st);
-    else if (a.Cin % 64 == 0 && a.Cin % 128 != 0 && a.Cin % 192 != 0) launch_wgrad_t<160, 64>(a, st);
-    else throw std::invalid_argument("conv_wgrad: Cout 160 supports Cin 160 or an odd multiple of 64");
-  } else if (a.Cin == 160) {
-    throw std::invalid_argument("conv_wgrad: Cin 160 needs Cout 160");
-  } else if (n192 && c192) launch_wgrad_t<192, 192>(a, st);
-  else if (n192 && c128) launch_wgrad_t<192, 128>(a, st);
-  else if (n192) launch_wgrad_t<192, 64>(a, st);
-  else if (n128 && c128) launch_wgrad_t<128, 128>(a, st);
-  else if (n128 && c192) launch_wgrad_t<128, 192>(a, st);
-  else if (n128) launch_wgrad_t<128, 64>(a, st);
-  else if (c192) launch_wgrad_t<64, 192>(a, st);
-  else if (c128) launch_wgrad_t<64, 128>(a, st);
-  else launch_wgrad_t<64, 64>(a, st);
+  wgrad_dispatch({a, st, nullptr});
 }
 
 // Sum split partials into the fp32 OIHW gradient (real channel counts) + bias.

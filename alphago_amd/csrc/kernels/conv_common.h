@@ -30,20 +30,6 @@ enum : unsigned {
   DBG_WG_DZ = 1u << 4,   // conv_wgrad: gradient staging offset
 };
 
-template <int N>
-__device__ __forceinline__ void vmcnt_wait() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-  else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else static_assert(N < 0, "unsupported vmcnt");
-}
-
 // s_waitcnt vmcnt(N) for any immediate N (gfx950: 0..63)
 template <int N>
 __device__ __forceinline__ void vmcnt_n() {
@@ -64,15 +50,15 @@ __device__ __forceinline__ void ring_wait(int later) {
 
 __device__ __forceinline__ void vmcnt_wait_dyn(int n) {
   switch (n) {
-    case 0: vmcnt_wait<0>(); break;
-    case 1: vmcnt_wait<1>(); break;
-    case 2: vmcnt_wait<2>(); break;
-    case 3: vmcnt_wait<3>(); break;
-    case 4: vmcnt_wait<4>(); break;
-    case 5: vmcnt_wait<5>(); break;
-    case 6: vmcnt_wait<6>(); break;
-    case 7: vmcnt_wait<7>(); break;
-    default: vmcnt_wait<8>(); break;
+    case 0: vmcnt_n<0>(); break;
+    case 1: vmcnt_n<1>(); break;
+    case 2: vmcnt_n<2>(); break;
+    case 3: vmcnt_n<3>(); break;
+    case 4: vmcnt_n<4>(); break;
+    case 5: vmcnt_n<5>(); break;
+    case 6: vmcnt_n<6>(); break;
+    case 7: vmcnt_n<7>(); break;
+    default: vmcnt_n<8>(); break;
   }
 }
 
@@ -84,42 +70,34 @@ __device__ __forceinline__ void lgkm_wait_pair(bf16x4& a, bf16x4& b) {
   asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(CNT));
 }
 
+// (operand lists of lgkm_fence: read pair i, four pairs from i)
+#define AGK_P(i) "+v"(a[i]), "+v"(b[i])
+#define AGK_P4(i) AGK_P(i), AGK_P(i + 1), AGK_P(i + 2), AGK_P(i + 3)
+#define AGK_FENCE(...) asm volatile("s_waitcnt lgkmcnt(0)" : __VA_ARGS__)
 // s_waitcnt lgkmcnt(0) with every listed read result as an in/out operand:
 // nothing that uses them can be scheduled above the wait.
 template <int N>
 __device__ __forceinline__ void lgkm_fence(bf16x4 (&a)[N], bf16x4 (&b)[N]) {
   static_assert(N >= 1 && N <= 15, "lgkm_fence supports 1..15 pairs (30 asm operands)");
-  if constexpr (N == 15)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]), "+v"(a[3]), "+v"(b[3]), "+v"(a[4]), "+v"(b[4]), "+v"(a[5]), "+v"(b[5]), "+v"(a[6]), "+v"(b[6]), "+v"(a[7]), "+v"(b[7]), "+v"(a[8]), "+v"(b[8]), "+v"(a[9]), "+v"(b[9]), "+v"(a[10]), "+v"(b[10]), "+v"(a[11]), "+v"(b[11]), "+v"(a[12]), "+v"(b[12]), "+v"(a[13]), "+v"(b[13]), "+v"(a[14]), "+v"(b[14]));
-  else if constexpr (N == 14)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]), "+v"(a[3]), "+v"(b[3]), "+v"(a[4]), "+v"(b[4]), "+v"(a[5]), "+v"(b[5]), "+v"(a[6]), "+v"(b[6]), "+v"(a[7]), "+v"(b[7]), "+v"(a[8]), "+v"(b[8]), "+v"(a[9]), "+v"(b[9]), "+v"(a[10]), "+v"(b[10]), "+v"(a[11]), "+v"(b[11]), "+v"(a[12]), "+v"(b[12]), "+v"(a[13]), "+v"(b[13]));
-  else if constexpr (N == 13)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]), "+v"(a[3]), "+v"(b[3]), "+v"(a[4]), "+v"(b[4]), "+v"(a[5]), "+v"(b[5]), "+v"(a[6]), "+v"(b[6]), "+v"(a[7]), "+v"(b[7]), "+v"(a[8]), "+v"(b[8]), "+v"(a[9]), "+v"(b[9]), "+v"(a[10]), "+v"(b[10]), "+v"(a[11]), "+v"(b[11]), "+v"(a[12]), "+v"(b[12]));
-  else if constexpr (N == 12)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]), "+v"(a[3]), "+v"(b[3]), "+v"(a[4]), "+v"(b[4]), "+v"(a[5]), "+v"(b[5]), "+v"(a[6]), "+v"(b[6]), "+v"(a[7]), "+v"(b[7]), "+v"(a[8]), "+v"(b[8]), "+v"(a[9]), "+v"(b[9]), "+v"(a[10]), "+v"(b[10]), "+v"(a[11]), "+v"(b[11]));
-  else if constexpr (N == 11)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]), "+v"(a[3]), "+v"(b[3]), "+v"(a[4]), "+v"(b[4]), "+v"(a[5]), "+v"(b[5]), "+v"(a[6]), "+v"(b[6]), "+v"(a[7]), "+v"(b[7]), "+v"(a[8]), "+v"(b[8]), "+v"(a[9]), "+v"(b[9]), "+v"(a[10]), "+v"(b[10]));
-  else if constexpr (N == 10)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]), "+v"(a[3]), "+v"(b[3]), "+v"(a[4]), "+v"(b[4]), "+v"(a[5]), "+v"(b[5]), "+v"(a[6]), "+v"(b[6]), "+v"(a[7]), "+v"(b[7]), "+v"(a[8]), "+v"(b[8]), "+v"(a[9]), "+v"(b[9]));
-  else if constexpr (N == 9)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]), "+v"(a[3]), "+v"(b[3]), "+v"(a[4]), "+v"(b[4]), "+v"(a[5]), "+v"(b[5]), "+v"(a[6]), "+v"(b[6]), "+v"(a[7]), "+v"(b[7]), "+v"(a[8]), "+v"(b[8]));
-  else if constexpr (N == 8)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]), "+v"(a[3]), "+v"(b[3]), "+v"(a[4]), "+v"(b[4]), "+v"(a[5]), "+v"(b[5]), "+v"(a[6]), "+v"(b[6]), "+v"(a[7]), "+v"(b[7]));
-  else if constexpr (N == 7)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]), "+v"(a[3]), "+v"(b[3]), "+v"(a[4]), "+v"(b[4]), "+v"(a[5]), "+v"(b[5]), "+v"(a[6]), "+v"(b[6]));
-  else if constexpr (N == 6)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]), "+v"(a[3]), "+v"(b[3]), "+v"(a[4]), "+v"(b[4]), "+v"(a[5]), "+v"(b[5]));
-  else if constexpr (N == 5)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]), "+v"(a[3]), "+v"(b[3]), "+v"(a[4]), "+v"(b[4]));
-  else if constexpr (N == 4)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]), "+v"(a[3]), "+v"(b[3]));
-  else if constexpr (N == 3)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(a[2]), "+v"(b[2]));
-  else if constexpr (N == 2)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]));
-  else if constexpr (N == 1)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(b[0]));
+  if constexpr (N == 15) AGK_FENCE(AGK_P4(0), AGK_P4(4), AGK_P4(8), AGK_P(12), AGK_P(13), AGK_P(14));
+  else if constexpr (N == 14) AGK_FENCE(AGK_P4(0), AGK_P4(4), AGK_P4(8), AGK_P(12), AGK_P(13));
+  else if constexpr (N == 13) AGK_FENCE(AGK_P4(0), AGK_P4(4), AGK_P4(8), AGK_P(12));
+  else if constexpr (N == 12) AGK_FENCE(AGK_P4(0), AGK_P4(4), AGK_P4(8));
+  else if constexpr (N == 11) AGK_FENCE(AGK_P4(0), AGK_P4(4), AGK_P(8), AGK_P(9), AGK_P(10));
+  else if constexpr (N == 10) AGK_FENCE(AGK_P4(0), AGK_P4(4), AGK_P(8), AGK_P(9));
+  else if constexpr (N == 9) AGK_FENCE(AGK_P4(0), AGK_P4(4), AGK_P(8));
+  else if constexpr (N == 8) AGK_FENCE(AGK_P4(0), AGK_P4(4));
+  else if constexpr (N == 7) AGK_FENCE(AGK_P4(0), AGK_P(4), AGK_P(5), AGK_P(6));
+  else if constexpr (N == 6) AGK_FENCE(AGK_P4(0), AGK_P(4), AGK_P(5));
+  else if constexpr (N == 5) AGK_FENCE(AGK_P4(0), AGK_P(4));
+  else if constexpr (N == 4) AGK_FENCE(AGK_P4(0));
+  else if constexpr (N == 3) AGK_FENCE(AGK_P(0), AGK_P(1), AGK_P(2));
+  else if constexpr (N == 2) AGK_FENCE(AGK_P(0), AGK_P(1));
+  else if constexpr (N == 1) AGK_FENCE(AGK_P(0));
 }
+#undef AGK_FENCE
+#undef AGK_P4
+#undef AGK_P
 
 // ds_read_b64_tr_b16 through inline asm.  The builtin form makes hipcc wait
 // vmcnt(0) before every such read while any LDS-DMA is outstanding (it cannot

@@ -130,10 +130,10 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_halo_kernel(ConvFwdArgs a) {
     }
     // the next K-step needs W(ks+1) (and the halo if a new chunk starts); the
     // loads issued this iteration may stay in flight across the barrier
-    if (issue_w && issue_halo) vmcnt_wait<NW_PW + HALO_PW>();
-    else if (issue_w) vmcnt_wait<NW_PW>();
-    else if (issue_halo) vmcnt_wait<HALO_PW>();
-    else vmcnt_wait<0>();
+    if (issue_w && issue_halo) vmcnt_n<NW_PW + HALO_PW>();
+    else if (issue_w) vmcnt_n<NW_PW>();
+    else if (issue_halo) vmcnt_n<HALO_PW>();
+    else vmcnt_n<0>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   }
@@ -417,13 +417,13 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_pp_kernel(ConvFwdArgs a) {
   // retire the oldest phase in flight, leaving `ahead` younger phases' pieces outstanding
   auto retire = [&](int ahead) {
     if (BP_MAX == BP_MIN || bfull) {
-      if (ahead >= 2) vmcnt_wait<2 * (2 + BP_MAX)>();
-      else if (ahead == 1) vmcnt_wait<2 + BP_MAX>();
-      else vmcnt_wait<0>();
+      if (ahead >= 2) vmcnt_n<2 * (2 + BP_MAX)>();
+      else if (ahead == 1) vmcnt_n<2 + BP_MAX>();
+      else vmcnt_n<0>();
     } else {
-      if (ahead >= 2) vmcnt_wait<2 * (2 + BP_MIN)>();
-      else if (ahead == 1) vmcnt_wait<2 + BP_MIN>();
-      else vmcnt_wait<0>();
+      if (ahead >= 2) vmcnt_n<2 * (2 + BP_MIN)>();
+      else if (ahead == 1) vmcnt_n<2 + BP_MIN>();
+      else vmcnt_n<0>();
     }
   };
 
@@ -1127,11 +1127,11 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_h32_kernel(ConvFwdArgs a) {
         stage_w(t2, c2, wslot == 0 ? 2 : wslot - 1);
       }
       if (w2) {
-        if (nh) vmcnt_wait<HP_STEP + WP>();
-        else vmcnt_wait<WP>();
+        if (nh) vmcnt_n<HP_STEP + WP>();
+        else vmcnt_n<WP>();
       } else {
-        if (nh) vmcnt_wait<HP_STEP>();
-        else vmcnt_wait<0>();
+        if (nh) vmcnt_n<HP_STEP>();
+        else vmcnt_n<0>();
       }
     }
     H32_STAMP(2);

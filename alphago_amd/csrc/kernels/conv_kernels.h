@@ -12,6 +12,110 @@
 
 namespace agk {
 
+// ----------------------------------------------------------------- forward: tile descriptions
+// A forward / dgrad tile is one type: its tile code, BM pixels per workgroup as waves of 16 MBW pixels x
+// BN/2 channels, the K loop it runs and the loop's options.  conv_fwd_kernel<BN, MODE, Tile, STR>, the
+// launchers, the dispatch (conv.hip) and the conv_fwd_tile_info op all read the same type.
+enum class FwdLoop {
+  Pipelined,        // two fragment sets: step ks + 1's first k-half is read under step ks's MFMAs; the epilogue
+                    // operands ride along with the last stages
+  PipelinedLateEp,  // the same loop, epilogue operands loaded after it (kernel lab)
+  Plain,            // one fragment set (large wave tiles): read, then MFMA, per k-half
+  DmaSpread,        // Plain with the next stage's LDS-DMA spread through the first k-half's MFMAs
+  Mfma32,           // Plain on v_mfma_f32_32x32x16_bf16 (kernel lab)
+  Ring,             // Pipelined on a SLOTS-deep LDS ring (kernel lab)
+  CompactHalo,      // conv_fwd_halo384_kernel: the pixel rows staged once per 64-channel chunk
+};
+
+struct FwdTileDefaults {
+  // chunk outer: the K loop runs the 64-channel chunk in the outer loop and the taps inside it, instead of
+  // all chunks of one tap before the next tap.  A tile's pixel rows for one chunk (BM + 2 halo rows x
+  // 128 B) are then re-read by the 9 taps while they are hot in the XCD's L2, where the tap-outer order
+  // cycles through every chunk of the tile (BM x Cin x 2 B per tile, ~5 MB for the 32 tiles of an XCD at
+  // Cin 192 -- more than its 4 MB L2).
+  static constexpr bool CHUNK_OUTER = false;
+  // split-K (small batches): blockIdx.z = split z of gridDim.z; the workgroup runs K-steps
+  // [nK z / nz, nK (z+1) / nz) and writes its raw fp32 partial tile to a.sk_ws[z][m][n];
+  // conv_splitk_finish_kernel sums the splits and applies the epilogue.  At B = 16 a 3x3 layer is 181
+  // 32-pixel tiles of 27 serial K-steps (~0.7 us each, whatever the DMA scheme): splitting K shortens
+  // that chain and fills the CUs.
+  static constexpr bool SPLITK = false;
+  // LDS stage buffers.  More than 2 (small batches): a ring, the DMA of step ks + SLOTS - 1 issued while
+  // step ks computes.  With few workgroups per CU nothing else hides the global->LDS latency of a
+  // 2-buffer loop (~0.75 us per K-step at B = 16, 27 steps per 3x3 layer: profiles/r3_small_batch/).
+  static constexpr int SLOTS = 2;
+};
+template <int CODE_, int BM_, int MBW_, FwdLoop LOOP_>
+struct FwdTileOf : FwdTileDefaults {
+  static constexpr int CODE = CODE_, BM = BM_, MBW = MBW_;
+  static constexpr FwdLoop LOOP = LOOP_;
+};
+
+// one type per tile code (docs/ARCHITECTURE.md has the table)
+struct Tile36 : FwdTileOf<36, 32, 1, FwdLoop::Pipelined> {};  // 32 pixels on 4 waves of 16 x BN/2
+struct Tile37 : FwdTileOf<37, 32, 2, FwdLoop::Pipelined> {};  // 32 pixels on 2 waves of 32 x BN/2
+struct Tile38 : FwdTileOf<38, 32, 1, FwdLoop::Pipelined> { static constexpr bool SPLITK = true; };  // 36 with split-K
+struct Tile64 : FwdTileOf<64, 64, 2, FwdLoop::Pipelined> {};
+struct Tile128 : FwdTileOf<128, 128, 4, FwdLoop::Pipelined> {};
+struct Tile256 : FwdTileOf<256, 256, 4, FwdLoop::Pipelined> {};
+struct Tile384 : FwdTileOf<384, 384, 6, FwdLoop::Plain> {};  // 96 x BN/2 per wave
+struct Tile385 : FwdTileOf<385, 384, 6, FwdLoop::DmaSpread> {};
+struct Tile386 : FwdTileOf<386, 384, 6, FwdLoop::DmaSpread> { static constexpr bool CHUNK_OUTER = true; };
+struct Tile387 : FwdTileOf<387, 384, 6, FwdLoop::Plain> { static constexpr bool CHUNK_OUTER = true; };
+struct Tile388 : FwdTileOf<388, 384, 6, FwdLoop::CompactHalo> {  // 386's MFMA sequence, compact-halo staging
+  static constexpr bool CHUNK_OUTER = true;
+};
+#ifdef AGK_KERNEL_LAB
+// measured slower or equal, kernel lab only: the 64 / 128-pixel tiles on a 4 / 3-slot LDS ring (round 4), the
+// epilogue operands loaded late, 128-pixel waves, the DMA spread and the 32x32 MFMA on other tiles
+// (profiles/r1_fwd_kernel_experiments.md)
+struct Tile65 : FwdTileOf<65, 64, 2, FwdLoop::Ring> { static constexpr int SLOTS = 4; };
+struct Tile130 : FwdTileOf<130, 128, 4, FwdLoop::Ring> { static constexpr int SLOTS = 3; };
+struct Tile2560 : FwdTileOf<2560, 256, 4, FwdLoop::PipelinedLateEp> {};
+struct Tile2568 : FwdTileOf<2568, 256, 8, FwdLoop::Pipelined> {};
+struct Tile7 : FwdTileOf<7, 384, 6, FwdLoop::Mfma32> {};
+struct Tile8 : FwdTileOf<8, 256, 4, FwdLoop::Mfma32> {};
+struct Tile10 : FwdTileOf<10, 256, 4, FwdLoop::DmaSpread> {};  // (lab code 9 is Tile385)
+#endif
+
+// compact-halo tile (conv_fwd_halo384_kernel below)
+constexpr int H384_BM = 384;
+constexpr int H384_SMAX = 19;                                          // largest board side covered
+constexpr int H384_DATA = (H384_BM + 2 * (H384_SMAX + 1) + 7) / 8 * 8;  // data rows (whole 1-KB pieces): 424
+constexpr int H384_ROWS = H384_DATA + 8;                               // + 8 zero rows
+constexpr int H384_PIECES = H384_DATA / 8;                             // 53
+
+// Launch geometry of a tile at output width BN, and what a tile may combine (the only place that says).
+// STR: straddled K-steps (Cin % 64 == 32), a run-time property of the layer.
+template <class T, int BN, bool STR = false>
+struct FwdGeo {
+  static constexpr bool HALO = T::LOOP == FwdLoop::CompactHalo;
+  static constexpr int WAVES = T::BM / (16 * T::MBW) * 2;  // (BM / (16 MBW)) x 2, each 16 MBW (m) x BN/2 (n)
+  static constexpr int THREADS = 64 * WAVES;
+  static constexpr int LDS_BYTES = HALO ? 2 * H384_ROWS * 128 + 2 * BN * 128 : T::SLOTS * (T::BM * 128 + BN * 128);
+  // per-wave weight rows that are no multiple of 8 (BN = 160): 8-row pieces dealt round-robin over the waves
+  static constexpr bool BDIST = (BN / WAVES) % 8 != 0;
+  static_assert(BN % 32 == 0 && (T::BM / WAVES) % 8 == 0, "tile geometry");
+  static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+  static_assert((T::SLOTS > 2) == (T::LOOP == FwdLoop::Ring), "more than two LDS slots: the ring loop, and only it");
+  static_assert(T::LOOP != FwdLoop::Ring || !BDIST, "ring: the pipelined 16x16 loop, contiguous weight staging");
+  static_assert(T::LOOP != FwdLoop::Mfma32 || (!BDIST && !STR && T::MBW % 2 == 0 && BN % 64 == 0),
+                "32x32 loop: whole 32x32 tiles, no round-robin weight staging, no straddled K-steps");
+  static_assert(!T::SPLITK || (T::LOOP == FwdLoop::Pipelined && !T::CHUNK_OUTER), "split-K: the pipelined 2-buffer loop, tap-outer order");
+  static_assert(!HALO || (T::BM == H384_BM && T::MBW == 6 && T::CHUNK_OUTER && !STR), "compact halo: the 384-pixel chunk-outer tile");
+  static dim3 grid(const ConvFwdArgs& a, int nz = 1) { return dim3((a.M + T::BM - 1) / T::BM, a.Cout / BN, nz); }
+};
+
+// MFMAs f0 <= f < f1 of a wave tile's NB x MB blocks (f = block (f / MB, f % MB)), unrolled: the DMA-spread
+// loops issue them in runs between DMA pieces
+template <int NB, int MB>
+__device__ __forceinline__ void mfma_range(f32x4 (&acc)[NB][MB], const bf16x8 (&wa)[NB], const bf16x8 (&xa)[MB], int f0,
+                                           int f1) {
+#pragma unroll
+  for (int f = 0; f < NB * MB; ++f)
+    if (f >= f0 && f < f1) acc[f / MB][f % MB] = mfma16x16x32(wa[f / MB], xa[f % MB], acc[f / MB][f % MB]);
+}
+
 // ----------------------------------------------------------------- forward
 // STR (Cin % 64 == 32, e.g. the value net's 152 filters padded to 160): a
 // 64-channel K-step may straddle two taps -- the 32-channel half h of every
@@ -19,27 +123,17 @@ namespace agk {
 // the row piece's logical chunk, so no MFMA multiplies padding.  The last
 // step's second half (K = taps * Cin is an odd multiple of 32) reads an extra
 // all-zero weight tap (packed weights then hold K*K + 1 taps).
-// BN whose per-wave weight rows are not a multiple of 8 (BN = 160) stage the
-// weight tile as 8-row pieces dealt round-robin over the waves.
-// CO (chunk outer): the K loop runs the 64-channel chunk in the outer loop and
-// the taps inside it, instead of all chunks of one tap before the next tap.
-// A tile's pixel rows for one chunk (BM + 2 halo rows x 128 B) are then re-read
-// by the 9 taps while they are hot in the XCD's L2, where the tap-outer order
-// cycles through every chunk of the tile (BM x Cin x 2 B per tile, ~5 MB for
-// the 32 tiles of an XCD at Cin 192 -- more than its 4 MB L2).
-// NS > 2 (small batches): an NS-slot LDS ring, the DMA of step ks + NS - 1 issued while step ks
-// computes.  With few workgroups per CU nothing else hides the global->LDS latency of a 2-buffer
-// loop (~0.75 us per K-step at B = 16, 27 steps per 3x3 layer: profiles/r3_small_batch/).
-// SK (split-K, small batches): blockIdx.z = split z of gridDim.z; the workgroup runs K-steps
-// [nK z / nz, nK (z+1) / nz) and writes its raw fp32 partial tile to a.sk_ws[z][m][n];
-// conv_splitk_finish_kernel sums the splits and applies the epilogue.  At B = 16 a 3x3 layer is 181
-// 32-pixel tiles of 27 serial K-steps (~0.7 us each, whatever the DMA scheme): splitting K shortens
-// that chain and fills the CUs.
-template <int BN, int MODE, int BM, int MBW, bool EPF = true, bool PIPE = true, bool M32 = false, bool ILV = false,
-          bool STR = false, bool CO = false, int NS = 2, bool SK = false>
-__global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_kernel(ConvFwdArgs a) {
-  // (BM / (16 MBW)) x 2 waves; each wave owns a 16*MBW (m) x BN/2 (n) output tile
-  constexpr int NW = BM / (16 * MBW) * 2;  // waves per workgroup
+template <int BN, int MODE, class Tile, bool STR = false>
+__global__ __launch_bounds__((FwdGeo<Tile, BN, STR>::THREADS), 1) void conv_fwd_kernel(ConvFwdArgs a) {
+  using G = FwdGeo<Tile, BN, STR>;
+  constexpr int BM = Tile::BM, MBW = Tile::MBW, NS = Tile::SLOTS;
+  constexpr FwdLoop LOOP = Tile::LOOP;
+  constexpr bool EPF = LOOP == FwdLoop::Pipelined || LOOP == FwdLoop::Ring;  // epilogue operands prefetched
+  constexpr bool PIPE = EPF || LOOP == FwdLoop::PipelinedLateEp;
+  constexpr bool M32 = LOOP == FwdLoop::Mfma32, ILV = LOOP == FwdLoop::DmaSpread;
+  constexpr bool CO = Tile::CHUNK_OUTER, SK = Tile::SPLITK;
+  static_assert(!G::HALO, "the compact-halo tile has its own kernel");
+  constexpr int NW = G::WAVES;  // waves per workgroup
   constexpr int NB = BN / 32;  // 16-wide n blocks per wave (a wave covers BN/2 channels)
   constexpr int MB = MBW;      // 16-wide m blocks per wave
   constexpr int A_BYTES = BM * 128;
@@ -47,12 +141,9 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_kernel(ConvFwdArgs a
   constexpr int STAGE = A_BYTES + B_BYTES;
   constexpr int A_ROWS_PW = BM / NW;   // pixel rows staged per wave
   constexpr int A_INSTR = A_ROWS_PW / 8;
-  constexpr bool BDIST = (BN / NW) % 8 != 0;  // weight pieces dealt round-robin
+  constexpr bool BDIST = G::BDIST;  // weight pieces dealt round-robin
   constexpr int B_ROWS_PW = BN / NW;   // weight rows staged per wave (contiguous layout)
   constexpr int B_INSTR = BDIST ? (BN / 8 + NW - 1) / NW : B_ROWS_PW / 8;  // glds instructions per wave
-  static_assert(BN % 32 == 0 && BN % 8 == 0 && A_ROWS_PW % 8 == 0, "tile geometry");
-  static_assert(!(BDIST && M32), "round-robin weight staging: not in the 32x32 loop");
-  static_assert(!(STR && M32), "straddled K-steps: not in the 32x32 loop");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int lane = threadIdx.x & 63;
@@ -125,22 +216,14 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_kernel(ConvFwdArgs a
   auto st_piece = [&](int d, char* base, int xo0, int xo1, size_t wo0, size_t wo1) {
     if (d < A_INSTR) {
       const int xo = arow[d] + ((STR && ahi[d]) ? xo1 : xo0);
-#ifdef AGK_DEBUG
       const bool ok = AGK_DCHECK(xo >= 0 && (long long)xo + 8 <= a.x_elems, DBG_FWD_X);
       glds16(a.x + (ok ? xo : 0), base + (wave * A_ROWS_PW + d * 8) * 128);
-#else
-      glds16(a.x + xo, base + (wave * A_ROWS_PW + d * 8) * 128);
-#endif
     } else {
       const int i = d - A_INSTR;
       if (BDIST && wave + i * NW >= BN / 8) return;  // wave-uniform: fewer pieces on the last waves
       const size_t wo = ((STR && bhi[i]) ? wo1 : wo0) + brow[i];
-#ifdef AGK_DEBUG
       const bool ok = AGK_DCHECK((long long)wo + 8 <= a.w_elems, DBG_FWD_W);
       glds16(ok ? a.w + wo : a.w, base + A_BYTES + bldsrow[i] * 128);
-#else
-      glds16(a.w + wo, base + A_BYTES + bldsrow[i] * 128);
-#endif
     }
   };
   // branch-free cursor advance (selects), so a caller can interleave the
@@ -217,7 +300,6 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_kernel(ConvFwdArgs a
   ConvEpilogue<NB, MB, MODE> ep;
   const int ep_at = EPF ? (nK > 2 ? nK - 2 : 0) : nK - 1;
   if constexpr (NS > 2) {
-    static_assert(PIPE && !M32 && !ILV && !BDIST, "ring: the pipelined 16x16 loop");
     // DMA instructions per wave per stage (the vmcnt unit of one stage)
     constexpr int PW = A_INSTR + B_INSTR;
     static_assert(PW * (NS - 2) <= 63, "vmcnt range");
@@ -244,7 +326,6 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_kernel(ConvFwdArgs a
     return;
   }
   if constexpr (SK) {
-    static_assert(PIPE && !M32 && !ILV && !CO, "split-K: the pipelined 2-buffer loop, tap-outer order");
     const int z = blockIdx.z, nz = gridDim.z;
     const int kb = (int)((long)nK * z / nz), ke = (int)((long)nK * (z + 1) / nz);
     for (int i = 0; i < kb; ++i) st_advance();  // scalar cursor to step kb
@@ -292,7 +373,6 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_kernel(ConvFwdArgs a
     // for its LDS reads and DMA issue.  Wave tile 16*MBW pixels x BN/2 channels
     // as (MBW/2) x (BN/64) 32x32 tiles; epilogue in the 32x32 C/D layout.
     constexpr int NB2 = BN / 64, MB2 = MBW / 2;
-    static_assert(MBW % 2 == 0 && BN % 64 == 0, "32x32 tiles");
     f32x16 acc2[NB2][MB2];
 #pragma unroll
     for (int i = 0; i < NB2; ++i)
@@ -347,11 +427,6 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_kernel(ConvFwdArgs a
     constexpr int NDMA = A_INSTR + B_INSTR;
     constexpr int NMF = NB * MB;
     constexpr int MPD = NMF / (NDMA + 1);
-    auto mfma_range = [&](int f0, int f1) {
-#pragma unroll
-      for (int f = 0; f < NMF; ++f)
-        if (f >= f0 && f < f1) acc[f / MB][f % MB] = mfma16x16x32(wa[f / MB], xa[f % MB], acc[f / MB][f % MB]);
-    };
     // The last step re-stages its own (in-range) operands into the idle buffer instead of
     // branching around each DMA piece: a uniform `if (more)` compiled to one s_cbranch per piece
     // inside the MFMA stream.
@@ -379,12 +454,12 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_kernel(ConvFwdArgs a
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int d = 0; d < NDMA; ++d) {
-        mfma_range(d * MPD, (d + 1) * MPD);
+        mfma_range(acc, wa, xa, d * MPD, (d + 1) * MPD);
         __builtin_amdgcn_sched_barrier(0);
         st_piece(d, nb, xo0, xo1, wo0, wo1);
         __builtin_amdgcn_sched_barrier(0);
       }
-      mfma_range(NDMA * MPD, NMF);
+      mfma_range(acc, wa, xa, NDMA * MPD, NMF);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
       st_advance();
@@ -443,18 +518,19 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_kernel(ConvFwdArgs a
   ep.store(a, acc, ep_mrow);
 }
 
-template <int BN, int MODE, int BM, int MBW, bool EPF = true, bool PIPE = true, bool M32 = false, bool ILV = false,
-          bool STR = false, bool CO = false, int NS = 2>
-static void launch_fwd_bm(const ConvFwdArgs& a, hipStream_t st) {
-  constexpr int smem = NS * (BM * 128 + BN * 128);
-  static_assert(smem <= 160 * 1024, "LDS");
-  static const hipError_t attr = hipFuncSetAttribute(
-      (const void*)conv_fwd_kernel<BN, MODE, BM, MBW, EPF, PIPE, M32, ILV, STR, CO, NS>,
-      hipFuncAttributeMaxDynamicSharedMemorySize, smem);  // once per instantiation (thread-safe static)
+// Launch KERNEL with LDS bytes of dynamic LDS: the limit is raised once per kernel (thread-safe static) and checked
+template <auto KERNEL, int THREADS, int LDS, class... Args>
+static void launch_dyn_lds(dim3 grid, hipStream_t st, const Args&... args) {
+  static const hipError_t attr = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
   hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
-  dim3 grid((a.M + BM - 1) / BM, a.Cout / BN);
-  hipLaunchKernelGGL((conv_fwd_kernel<BN, MODE, BM, MBW, EPF, PIPE, M32, ILV, STR, CO, NS>), grid,
-                     dim3(BM / MBW * 8), smem, st, a);
+  hipLaunchKernelGGL(KERNEL, grid, dim3(THREADS), LDS, st, args...);
+}
+
+// one launch of conv_fwd_kernel: threads, LDS and grid are the tile's (FwdGeo)
+template <int BN, int MODE, class Tile, bool STR>
+static void launch_fwd_kernel(const ConvFwdArgs& a, dim3 grid, hipStream_t st) {
+  using G = FwdGeo<Tile, BN, STR>;
+  launch_dyn_lds<conv_fwd_kernel<BN, MODE, Tile, STR>, G::THREADS, G::LDS_BYTES>(grid, st, a);
 }
 
 // ----------------------------------------------------------------- forward, compact-halo 384 tile (code 388)
@@ -475,16 +551,9 @@ static void launch_fwd_bm(const ConvFwdArgs& a, hipStream_t st) {
 // ascending, k-halves ascending; zero rows for the zero border), so the outputs are bit-identical.
 // The nine taps are unrolled: tap offsets, the border test and the DMA schedule of a step are
 // compile-time, and the MFMA stream has no branch.  LDS: 2 halo buffers + 2 weight slots.
-constexpr int H384_BM = 384;
-constexpr int H384_SMAX = 19;                                          // largest board side covered
-constexpr int H384_DATA = (H384_BM + 2 * (H384_SMAX + 1) + 7) / 8 * 8;  // data rows (whole 1-KB pieces): 424
-constexpr int H384_ROWS = H384_DATA + 8;                               // + 8 zero rows
-constexpr int H384_PIECES = H384_DATA / 8;                             // 53
 
 template <int V>
-struct IntC {
-  static constexpr int value = V;
-};
+struct IntC { static constexpr int value = V; };
 
 // STAMP (kernel lab, the op's stamp buffer): four cycle counts per wave around the epilogue, see the end
 template <int BN, int MODE, bool STAMP = false>
@@ -535,12 +604,8 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_halo384_kernel(ConvFwdArgs a)
   auto halo_piece = [&](int i, int c, int buf) {
     const int k = i * NW + wave < H384_PIECES ? i * NW + wave : H384_PIECES - 1;
     const int xo = hoff[i] + c * 64;
-#ifdef AGK_DEBUG
     const bool ok = AGK_DCHECK(xo >= 0 && (long long)xo + 8 <= a.x_elems, DBG_FWD_X);
     glds16(a.x + (ok ? xo : 0), hbuf + buf * H_BYTES + k * 1024);
-#else
-    glds16(a.x + xo, hbuf + buf * H_BYTES + k * 1024);
-#endif
   };
   int wrow[WP];
 #pragma unroll
@@ -551,12 +616,8 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_halo384_kernel(ConvFwdArgs a)
   const int wtap = a.Cout * a.Cin;  // 32-bit weight offsets (the launcher checks 9 taps fit)
   auto w_piece = [&](int i, int wo, int slot) {  // wo: (tap, chunk) offset of the step
     const int o = wo + wrow[i];
-#ifdef AGK_DEBUG
     const bool ok = AGK_DCHECK((long long)o + 8 <= a.w_elems, DBG_FWD_W);
     glds16(ok ? a.w + o : a.w, wbuf + slot * W_BYTES + (wave * WP + i) * 1024);
-#else
-    glds16(a.w + o, wbuf + slot * W_BYTES + (wave * WP + i) * 1024);
-#endif
   };
 
   // --- the lane's pixels: block j holds pixel m0 + 96 wm + 16 j + pix16; bit 6 t + j of okm (taps 0-4
@@ -589,11 +650,6 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_halo384_kernel(ConvFwdArgs a)
   const int kq = lane >> 4;  // the lane's 16-B chunk of a k-half
   const int wfrag0 = (wn * (BN / 2) + (lane & 15)) * 128 + ((kq ^ ((lane & 15) >> 1)) << 4);
   bf16x8 xa[MB], wa[NB];
-  auto mfma_range = [&](int f0, int f1) {
-#pragma unroll
-    for (int f = 0; f < NMF; ++f)
-      if (f >= f0 && f < f1) acc[f / MB][f % MB] = mfma16x16x32(wa[f / MB], xa[f % MB], acc[f / MB][f % MB]);
-  };
 
   // prologue: the zero rows of both halo buffers, chunk 0's halo, W(tap 0, chunk 0)
   if (wave < 2) *(uint4*)(hbuf + wave * H_BYTES + H384_DATA * 128 + lane * 16) = make_uint4(0u, 0u, 0u, 0u);
@@ -640,13 +696,13 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_halo384_kernel(ConvFwdArgs a)
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int d = 0; d < NDMA; ++d) {
-      mfma_range(d * MPD, (d + 1) * MPD);
+      mfma_range(acc, wa, xa, d * MPD, (d + 1) * MPD);
       __builtin_amdgcn_sched_barrier(0);
       if (d < NWP) w_piece(d, wo, ws ^ 1);
       else halo_piece(T, c + 1, (c + 1) & 1);
       __builtin_amdgcn_sched_barrier(0);
     }
-    mfma_range(NDMA * MPD, NMF);
+    mfma_range(acc, wa, xa, NDMA * MPD, NMF);
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     // second k-half: chunk index ^ 4 = byte offset ^ 64
@@ -655,7 +711,7 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_halo384_kernel(ConvFwdArgs a)
 #pragma unroll
     for (int i = 0; i < NB; ++i) wa[i] = *(const bf16x8*)(wbuf + ws * W_BYTES + (wfrag0 ^ 64) + i * 16 * 128);
     __builtin_amdgcn_s_setprio(1);
-    mfma_range(0, NMF);
+    mfma_range(acc, wa, xa, 0, NMF);
     __builtin_amdgcn_s_setprio(0);
     wait_vmcnt0();
     __syncthreads();
@@ -712,30 +768,21 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_halo384_kernel(ConvFwdArgs a)
 }
 
 // tile code 388: covers 3x3, Cin % 64 == 0, S <= 19 at BN = 192 in the bias + ReLU forward and the bitmask dgrad
-template <int BN, int MODE>
-static bool halo384_covers(const ConvFwdArgs& a) {
-  return BN == 192 && ((MODE & 3) == MODE_BIAS_RELU || (MODE & 3) == MODE_MASKBITS) && a.K == 3 && a.Cin % 64 == 0 &&
-         a.Cin >= 64 && a.S <= H384_SMAX && a.offi >= 0 && 9ll * a.Cout * a.Cin < (1ll << 31);
+static inline bool halo384_covers(int bn, int mode, int S, int K, int Cin, int Cout, int offi) {
+  return bn == 192 && ((mode & 3) == MODE_BIAS_RELU || (mode & 3) == MODE_MASKBITS) && K == 3 && Cin % 64 == 0 &&
+         Cin >= 64 && S <= H384_SMAX && offi >= 0 && 9ll * Cout * Cin < (1ll << 31);
 }
 
 template <int BN, int MODE>
 static void launch_fwd_halo384(const ConvFwdArgs& a, hipStream_t st) {
   if constexpr (BN == 192 && ((MODE & 3) == MODE_BIAS_RELU || (MODE & 3) == MODE_MASKBITS)) {
-    constexpr int smem = 2 * H384_ROWS * 128 + 2 * BN * 128;
-    static const hipError_t attr = hipFuncSetAttribute((const void*)conv_fwd_halo384_kernel<BN, MODE>,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
-    dim3 grid((a.M + H384_BM - 1) / H384_BM, a.Cout / BN);
+    using G = FwdGeo<Tile388, BN>;
+    auto plain = [&] { launch_dyn_lds<conv_fwd_halo384_kernel<BN, MODE>, G::THREADS, G::LDS_BYTES>(G::grid(a), st, a); };
 #ifdef AGK_KERNEL_LAB
-    if (a.dbg) {  // diagnostic instantiation with epilogue stamps: 4 counts per wave, 8 waves per workgroup
-      static const hipError_t attr_d = hipFuncSetAttribute((const void*)conv_fwd_halo384_kernel<BN, MODE, true>,
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-      hip_check(attr_d, "hipFuncSetAttribute(max dynamic LDS)");
-      hipLaunchKernelGGL((conv_fwd_halo384_kernel<BN, MODE, true>), grid, dim3(512), smem, st, a);
-      return;
-    }
+    if (a.dbg)  // diagnostic instantiation with epilogue stamps: 4 counts per wave, 8 waves per workgroup
+      return launch_dyn_lds<conv_fwd_halo384_kernel<BN, MODE, true>, G::THREADS, G::LDS_BYTES>(G::grid(a), st, a);
 #endif
-    hipLaunchKernelGGL((conv_fwd_halo384_kernel<BN, MODE>), grid, dim3(512), smem, st, a);
+    plain();
   } else {
     throw std::invalid_argument("conv_fwd: tile 388 is the 192-wide forward / bitmask dgrad");
   }
@@ -798,28 +845,27 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(ConvFwdArgs a) 
 
 // tile code 38: the 32-pixel tile (36) with split-K over a.sk_nsplit workgroups per tile, then the finish
 // (BN = 160, the value width: STR straddled K-steps when Cin % 64 == 32, weight pieces dealt round-robin)
-template <int BN, int MODE, bool STR = false>
+template <int BN, int MODE, class Tile, bool STR>
 static void launch_fwd_splitk(const ConvFwdArgs& a, hipStream_t st) {
   if constexpr ((MODE & 3) == MODE_MASK) {
     throw std::invalid_argument("conv_fwd split-K: modes 0 (bias + ReLU), 2 (none) and 3 (bitmask dgrad)");
   } else {
     if (!a.sk_ws || a.sk_nsplit < 1 || a.y_bf8)
       throw std::invalid_argument("conv_fwd split-K (tile 38): needs a workspace and nsplit >= 1, no e5m2 copy");
-    constexpr int BM = 32, MBW = 1;
-    constexpr int smem = 2 * (BM * 128 + BN * 128);
     // the split pass writes raw partial sums: a skip operand (MODE_RES) is the finish kernel's alone
-    constexpr int KMODE = MODE & 3;
-    static const hipError_t attr = hipFuncSetAttribute(
-        (const void*)conv_fwd_kernel<BN, KMODE, BM, MBW, true, true, false, false, STR, false, 2, true>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
-    dim3 grid((a.M + BM - 1) / BM, a.Cout / BN, a.sk_nsplit);
-    hipLaunchKernelGGL((conv_fwd_kernel<BN, KMODE, BM, MBW, true, true, false, false, STR, false, 2, true>), grid,
-                       dim3(BM / MBW * 8), smem, st, a);
+    launch_fwd_kernel<BN, MODE & 3, Tile, STR>(a, FwdGeo<Tile, BN>::grid(a, a.sk_nsplit), st);
     const long threads = (long)a.M * (a.Cout / BN) * 8;
     hipLaunchKernelGGL((conv_splitk_finish_kernel<MODE, BN / 32>), dim3((unsigned)((threads + 255) / 256)), dim3(256),
                        0, st, a);
   }
+}
+
+// launch a tile: the split-K pair, the compact-halo kernel, or conv_fwd_kernel over the tile's grid
+template <int BN, int MODE, class Tile, bool STR = false>
+static void launch_fwd_tile(const ConvFwdArgs& a, hipStream_t st) {
+  if constexpr (Tile::SPLITK) launch_fwd_splitk<BN, MODE, Tile, STR>(a, st);
+  else if constexpr (FwdGeo<Tile, BN>::HALO) launch_fwd_halo384<BN, MODE>(a, st);
+  else launch_fwd_kernel<BN, MODE, Tile, STR>(a, FwdGeo<Tile, BN>::grid(a), st);
 }
 
 // ----------------------------------------------------------------- packed-tap forward (thin first layer)
@@ -911,12 +957,8 @@ __global__ __launch_bounds__(BM / MBW * 8, 1) void conv_fwd_pk_kernel(ConvFwdArg
 #pragma unroll
     for (int i = 0; i < B_INSTR; ++i) {
       if (BDIST && wave + i * NW >= BN / 8) continue;  // wave-uniform
-#ifdef AGK_DEBUG
       const bool ok = AGK_DCHECK((long long)(st_w + brow[i]) + 8 <= a.w_elems, DBG_FWD_W);
       glds16(ok ? a.w + st_w + brow[i] : a.w, base + A_BYTES + bldsrow[i] * 128);
-#else
-      glds16(a.w + st_w + brow[i], base + A_BYTES + bldsrow[i] * 128);
-#endif
     }
     // advance by 8 chunks (at most two tap boundaries when cpt >= 4)
     st_w += wstep;
@@ -1182,7 +1224,6 @@ __device__ __forceinline__ void wgrad_tile(const ConvWgradArgs& a, int split, in
       if constexpr (ONE) {
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
-#ifdef AGK_DEBUG
           const int pc = wave * IPW + i, xj = pc - WN / 16;
           const long long e =
               (long long)(o[0] >> 1) + (wdz ? n0 + pc * 16 : toff + (xj / XP) * tstep + (xj % XP) * 16);
@@ -1190,7 +1231,6 @@ __device__ __forceinline__ void wgrad_tile(const ConvWgradArgs& a, int split, in
             glds16(wdz ? a.dz : a.x, base + (wave * IPW + i) * 1024);
             continue;
           }
-#endif
           glds16_so(pb[i], o[0], base + (wave * IPW + i) * 1024);
         }
         continue;
@@ -1202,13 +1242,11 @@ __device__ __forceinline__ void wgrad_tile(const ConvWgradArgs& a, int split, in
       for (int i = 0; i < IPW; ++i) {
         const int jj = wave * IPW + i - sub * (NINSTR / KSUB);
         if (jj >= 0 && jj < WN / 16) {
-#ifdef AGK_DEBUG
           const long long e = (long long)(o[0] >> 1) + n0 + jj * 16;
           if (!AGK_DCHECK(e + 8 <= a.dz_elems, DBG_WG_DZ)) {
             glds16(a.dz, base + sub * SUB + jj * 1024);
             continue;
           }
-#endif
           glds16_so(dzpiece(jj), o[0], base + sub * SUB + jj * 1024);
         }
         // LDS ring with unequal piece counts: a wave past the last piece re-issues dz piece 0 (same
@@ -1223,13 +1261,11 @@ __device__ __forceinline__ void wgrad_tile(const ConvWgradArgs& a, int split, in
         const int jj = wave * IPW + i - sub * (NINSTR / KSUB);
         if (jj >= WN / 16 && jj < NINSTR / KSUB) {
           const int xj = jj - WN / 16;
-#ifdef AGK_DEBUG
           const long long e = (long long)(o[NT - 1] >> 1) + toff + (xj / XP) * tstep + (xj % XP) * 16;
           if (!AGK_DCHECK(e + 8 <= a.x_elems, DBG_WG_X)) {
             glds16(a.x, base + sub * SUB + jj * 1024);
             continue;
           }
-#endif
           glds16_so(xpiece(xj), o[NT - 1], base + sub * SUB + jj * 1024);
         }
       }
@@ -1459,12 +1495,8 @@ __device__ __forceinline__ void wgrad_tile_line(const ConvWgradArgs& a, int spli
       if (idx >= DZP / 4) continue;
       const int sub = idx / NCN, cc = idx - sub * NCN;
       const int o = (KSUB == 2 && sub ? dzr[KSUB - 1] : dzr[0]) + cc * 64;
-#ifdef AGK_DEBUG
       const bool ok = AGK_DCHECK(o >= 0 && (long long)o + 8 <= a.dz_elems, DBG_WG_DZ);
       glds16(ok ? a.dz + o : a.dz, base + sub * SUB + cc * 4096);
-#else
-      glds16(a.dz + o, base + sub * SUB + cc * 4096);
-#endif
     }
 #pragma unroll
     for (int d = 0; d < NPW; ++d) {
@@ -1474,12 +1506,8 @@ __device__ __forceinline__ void wgrad_tile_line(const ConvWgradArgs& a, int spli
       const int sub = idx / (TAPS * NCC), rem = idx - sub * (TAPS * NCC);
       const int tp = rem / NCC, cc = rem - tp * NCC;
       const int o = (KSUB == 2 && sub ? xr[KSUB - 1] : xr[0]) + tp * tstep + cc * 64;
-#ifdef AGK_DEBUG
       const bool ok = AGK_DCHECK(o >= 0 && (long long)o + 8 <= a.x_elems, DBG_WG_X);
       glds16(ok ? a.x + o : a.x, base + sub * SUB + DZ_BYTES + (tp * NCC + cc) * 4096);
-#else
-      glds16(a.x + o, base + sub * SUB + DZ_BYTES + (tp * NCC + cc) * 4096);
-#endif
     }
   };
   auto stage = [&](int ks, int buf) {
@@ -1655,17 +1683,100 @@ __device__ __forceinline__ void wgrad_tile_line(const ConvWgradArgs& a, int spli
   wgrad_store<WN, WC, NWC, TAPS>(a, acc, dbs, do_bias ? (1u << NBn) - 1u : 0u, split, t, n0, c0, wn, wc, lane, zero_split);
 }
 
-// LINE && !PAIR: two 8-wave workgroups per CU like the production per-tap kernel (<= 128 VGPRs)
-// MW: minimum waves per SIMD the register allocation must allow (0: the default -- 4 for the line-staged
-// lab kernel, else 1).  The thin first layer's tap-merged rows (48-wide c tile, 6 waves) take 180 VGPRs,
-// which fits ONE workgroup per CU; MW = 3 caps them at 168 (11 dwords spilled) so that two share a CU
-// (AGK_WGRAD0_OCC3=1, round 4 A/B).
-template <int WN, int WC, int KSUB, int NWC = 4, int TAPS = 1, bool PAIR = false, bool LINE = false, bool ILVW = false,
-          int NS = 2, int MW = 0, int NWN = 2, bool UP = false>
-__global__ __launch_bounds__(64 * NWN * NWC, (MW > 0 ? MW : (LINE && !PAIR) ? 4 : 1)) void conv_wgrad_kernel(
-    ConvWgradArgs a) {
-  static_assert(!PAIR || TAPS == 2, "PAIR: two taps per workgroup");
-  static_assert(NWN == 2 || (!PAIR && !LINE), "NWN != 2: the plain per-tap / tap-merged body only");
+// ----------------------------------------------------------------- wgrad: tile descriptions
+// A wgrad workgroup tile is one type; conv_wgrad_kernel<Cfg>, the launchers and wgrad_plan (through
+// wgrad_choose, conv.hip) read the same one.
+struct WgradDefaults {
+  static constexpr int KSUB = 1;          // 32-pixel sub-steps per pipeline stage
+  static constexpr int NWN = 2, NWC = 4;  // waves along n and along c
+  static constexpr int TAPS = 1;          // taps per workgroup (tap-merged kernel rows: K)
+  static constexpr int SLOTS = 2;         // LDS stage buffers; more: a ring (wgrad_tile NS)
+  // minimum waves per SIMD the register allocation must allow (0: the default -- 4 for the line-staged lab
+  // kernel, else 1)
+  static constexpr int MIN_WAVES = 0;
+  static constexpr bool PAIR = false, LINE = false, LINE_DMA_SPREAD = false, UNIT_PIPE = false;  // see wgrad_tile*
+  // Resident workgroups per CU the trainers size the split count for.  Stated, not derived: two 8-wave
+  // workgroups of <= 128 VGPRs and 48 KB of LDS share a CU.
+  static constexpr int PER_CU = 2;
+};
+// one tap per workgroup: WN x WC on 8 waves (2 n x 4 c)
+template <int WN_, int WC_>
+struct WgradTap : WgradDefaults { static constexpr int WN = WN_, WC = WC_; };
+// 160 x 160 on 4 waves (2 n x 2 c, 80 x 80 per wave): the value net's padded width; 40 KB of LDS
+struct WgradTap160x160 : WgradTap<160, 160> { static constexpr int NWC = 2; };
+// tap-merged kernel row (64-wide c tile): the K taps of a row per workgroup
+template <int WN_, int TAPS_>
+struct WgradRow : WgradTap<WN_, 64> {
+  static constexpr int TAPS = TAPS_;
+  // the 5x5 rows of the 160-wide n tile (value layer 0, 49 planes) take 154 VGPRs, which leaves room for one
+  // 8-wave workgroup -- a grid sized for two ran as two rounds (251 us per step, profiles/r3_fp8_wgrad.md)
+  static constexpr int PER_CU = (WN_ == 160 && TAPS_ == 5) ? 1 : 2;
+};
+// the thin first layer (48 real planes of 64): a 48-wide c tile on 6 waves (2 n x 3 c) skips the zero
+// channels -- 25% fewer MFMAs and x bytes on the backward's serial tail.  The 5x5 rows of a 192-wide layer
+// run as 96-wide halves (WN 96): half the accumulators per wave (104 VGPRs instead of 180), so two
+// workgroups share a CU and one resident round covers the grid (profiles/r5/README.md); the 192-wide
+// rows stay compiled beside them.
+template <int WN_, int TAPS_>
+struct WgradRow48 : WgradTap<WN_, 48> { static constexpr int TAPS = TAPS_, NWC = 3; };
+// split-free small-batch plan (launch_conv_wgrad_direct): 32 x WC per tap over all pixels, one per CU
+template <int WC_, int KSUB_>
+struct WgradDirect : WgradTap<32, WC_> {
+  static constexpr int KSUB = KSUB_, NWC = WC_ / 16, PER_CU = 1;
+};
+#ifdef AGK_KERNEL_LAB
+// kernel-lab re-cuts (equal or slower, profiles/r3_wgrad_pair.md, profiles/r4/README.md)
+template <int WN_, int WC_, int NWC_>
+struct WgradRing : WgradTap<WN_, WC_> {  // variant 9: 4-slot LDS ring, one workgroup per CU
+  static constexpr int NWC = NWC_, SLOTS = 4, PER_CU = 1;
+};
+template <int WN_, int WC_>
+struct WgradTap4Waves : WgradTap<WN_, WC_> {  // variant 2: 256-thread tile
+  static constexpr int NWC = 2;
+};
+// The thin first layer's rows run one workgroup per CU (180 VGPRs on 6 waves): ~1.16 us per 32-pixel stage,
+// 26-29 % MFMA busy (profiles/r3_final/pmc).  Variant 13 caps them at 168 VGPRs (11 dwords spilled) so that
+// two share a CU; 10: 12 waves (4 n x 3 c, 48 x 48 per wave per tap, 104 VGPRs): 559 us vs 556 us; 11: the 6
+// waves with unit pipelining (wgrad_tile UP): 557 us; 12: 12 waves with unit pipelining: 556 us.  Measured and
+// removed: the 6 waves on a 4-slot LDS ring (601 us), 12 waves + UP capped at 85 VGPRs for two workgroups
+// per CU (56 B spilled, bench -4.5 %), UP on the 3x3 per-tap kernel (517 vs 500 us).
+template <int WN_, int TAPS_>
+struct WgradRow48TwoPerCu : WgradRow48<WN_, TAPS_> {
+  static constexpr int MIN_WAVES = 3;
+};
+template <int WN_, int TAPS_, bool UP_>
+struct WgradRow48Waves12 : WgradRow48<WN_, TAPS_> {
+  static constexpr int NWN = 4;
+  static constexpr bool UNIT_PIPE = UP_;
+};
+template <int WN_, int TAPS_>
+struct WgradRow48UnitPipe : WgradRow48<WN_, TAPS_> {
+  static constexpr bool UNIT_PIPE = true;
+};
+// variants 6 / 8: tap pairs, 64-pixel stages, line staging (8: DMA spread); 7: per tap, line staging
+template <bool SPREAD_>
+struct WgradPair : WgradTap<192, 192> {
+  static constexpr int KSUB = 2, TAPS = 2, PER_CU = 1;
+  static constexpr bool PAIR = true, LINE = true, LINE_DMA_SPREAD = SPREAD_;
+};
+struct WgradLine : WgradTap<192, 192> { static constexpr bool LINE = true; };
+#endif
+
+// launch geometry of a wgrad tile, and what it may combine
+template <class C>
+struct WgradGeo {
+  static constexpr int THREADS = 64 * C::NWN * C::NWC;
+  static constexpr int LDS_BYTES = C::SLOTS * (C::WN + C::WC * C::TAPS) * 64 * C::KSUB;
+  static constexpr int MIN_WAVES = C::MIN_WAVES > 0 ? C::MIN_WAVES : (C::LINE && !C::PAIR) ? 4 : 1;
+  static_assert(!C::PAIR || C::TAPS == 2, "PAIR: two taps per workgroup");
+  static_assert(C::NWN == 2 || (!C::PAIR && !C::LINE), "NWN != 2: the plain per-tap / tap-merged body only");
+  static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+};
+
+template <class C>
+__global__ __launch_bounds__((WgradGeo<C>::THREADS), (WgradGeo<C>::MIN_WAVES)) void conv_wgrad_kernel(ConvWgradArgs a) {
+  constexpr int WN = C::WN, WC = C::WC, KSUB = C::KSUB, NWC = C::NWC, TAPS = C::TAPS, NS = C::SLOTS, NWN = C::NWN;
+  constexpr bool PAIR = C::PAIR, LINE = C::LINE, ILVW = C::LINE_DMA_SPREAD, UP = C::UNIT_PIPE;
   // workgroup -> (split, tap group, channel block).  xcd_group (tap-merged rows): the hardware
   // deals workgroups to the 8 XCDs round robin in launch order, which puts the K kernel-row
   // workgroups of a split -- all reading the same dZ rows -- on K different L2s, so every dZ
@@ -1714,7 +1825,14 @@ __global__ __launch_bounds__(64 * NWN * NWC, (MW > 0 ? MW : (LINE && !PAIR) ? 4 
   else wgrad_tile<WN, WC, KSUB, NWC, TAPS, NS, NWN, UP, !PAIR>(a, split, ks_begin, ks_end, t, tstep, n0, c0, -1);
 }
 
-constexpr int kWgradKsub = 1;
+// one launch of conv_wgrad_kernel: threads and LDS are the tile's; the grid (splits x tap groups x channel
+// blocks) is the caller's
+template <class C>
+static void launch_wgrad_cfg(const ConvWgradArgs& a, dim3 grid, hipStream_t st) {
+  launch_dyn_lds<conv_wgrad_kernel<C>, WgradGeo<C>::THREADS, WgradGeo<C>::LDS_BYTES>(grid, st, a);
+}
+
+constexpr int kWgradKsub = WgradDefaults::KSUB;
 // ConvWgradArgs::variant: 0 = production 2-buffer kernel (tap-merged rows for
 // 64-wide c tiles); kernel-lab build only: 1 = one tap per workgroup,
 // 2 = 256-thread tile, 3 / 4 = LDS ring with that many slots

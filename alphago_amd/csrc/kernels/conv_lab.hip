@@ -367,14 +367,14 @@ static bool lab_fwd_t(int bm, const ConvFwdArgs& a, hipStream_t st) {
   // (32x32x16 MFMA)
   const bool var = bm == -1 || bm == 2 || bm == 4 || bm == 5 || bm == 6 || bm == 32;
   if (var && launch_conv_fwd_variant(bm, a, MODE, st)) return true;
-  if (var) launch_fwd_bm<BN, MODE, 128, 4>(a, st);
-  else if (bm == 2560) launch_fwd_bm<BN, MODE, 256, 4, false>(a, st);
-  else if (bm == 2568) launch_fwd_bm<BN, MODE, 256, 8>(a, st);
+  if (var) launch_fwd_tile<BN, MODE, Tile128>(a, st);
+  else if (bm == 2560) launch_fwd_tile<BN, MODE, Tile2560>(a, st);
+  else if (bm == 2568) launch_fwd_tile<BN, MODE, Tile2568>(a, st);
   else if (bm == 11) launch_fwd_ga<BN, MODE>(a, st);
-  else if (bm == 9) launch_fwd_bm<BN, MODE, 384, 6, false, false, false, true>(a, st);
-  else if (bm == 10) launch_fwd_bm<BN, MODE, 256, 4, false, false, false, true>(a, st);
-  else if (bm == 7) launch_fwd_bm<BN, MODE, 384, 6, false, false, true>(a, st);
-  else if (bm == 8) launch_fwd_bm<BN, MODE, 256, 4, false, false, true>(a, st);
+  else if (bm == 9) launch_fwd_tile<BN, MODE, Tile385>(a, st);
+  else if (bm == 10) launch_fwd_tile<BN, MODE, Tile10>(a, st);
+  else if (bm == 7) launch_fwd_tile<BN, MODE, Tile7>(a, st);
+  else if (bm == 8) launch_fwd_tile<BN, MODE, Tile8>(a, st);
   else return false;
   return true;
 }
@@ -404,11 +404,7 @@ static bool lab_wgrad_t(const ConvWgradArgs& a, dim3 grid, hipStream_t st) {
   }
   if constexpr (WC % 32 == 0 && WC >= 64) {
     if (a.variant == 2) {
-      constexpr int smem = 2 * (WN + WC) * 64 * kWgradKsub;
-      static const hipError_t attr2 = hipFuncSetAttribute((const void*)conv_wgrad_kernel<WN, WC, kWgradKsub, 2>,
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-      hip_check(attr2, "hipFuncSetAttribute(max dynamic LDS)");
-      hipLaunchKernelGGL((conv_wgrad_kernel<WN, WC, kWgradKsub, 2>), grid, dim3(256), smem, st, a);
+      launch_wgrad_cfg<WgradTap4Waves<WN, WC>>(a, grid, st);
       return true;
     }
   }
@@ -434,28 +430,16 @@ bool launch_conv_wgrad_lab(const ConvWgradArgs& a, int wn, int wc, dim3 grid, hi
 
 template <bool ILVW>
 static void launch_wgrad_pair(ConvWgradArgs a, hipStream_t st) {
-  constexpr int KS = 2;
-  constexpr int smem = 2 * (192 + 2 * 192) * 64 * KS;  // 144 KB
-  static const hipError_t attr = hipFuncSetAttribute(
-      (const void*)conv_wgrad_kernel<192, 192, KS, 4, 2, true, true, ILVW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-      smem);
-  hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
-  const int nks = (a.M + 32 * KS - 1) / (32 * KS);  // the op computed ksteps in 32-pixel units
+  using C = WgradPair<ILVW>;  // 144 KB of LDS
+  const int nks = (a.M + 32 * C::KSUB - 1) / (32 * C::KSUB);  // the op computed ksteps in 32-pixel units
   a.ksteps_per_split = (nks + a.nsplit - 1) / a.nsplit;
-  dim3 grid(a.nsplit, (a.T + 1) / 2, 1);
-  hipLaunchKernelGGL((conv_wgrad_kernel<192, 192, KS, 4, 2, true, true, ILVW>), grid, dim3(512), smem, st, a);
+  launch_wgrad_cfg<C>(a, dim3(a.nsplit, (a.T + 1) / 2, 1), st);
 }
 
 // per-tap kernel with line staging (variant 7): the production tile and grid, whole 128-byte
 // pixel lines per DMA piece
 static void launch_wgrad_line(const ConvWgradArgs& a, hipStream_t st) {
-  constexpr int KS = kWgradKsub;
-  constexpr int smem = 2 * (192 + 192) * 64 * KS;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)conv_wgrad_kernel<192, 192, KS, 4, 1, false, true>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
-  dim3 grid(a.nsplit, a.T, 1);
-  hipLaunchKernelGGL((conv_wgrad_kernel<192, 192, KS, 4, 1, false, true>), grid, dim3(512), smem, st, a);
+  launch_wgrad_cfg<WgradLine>(a, dim3(a.nsplit, a.T, 1), st);
 }
 
 // variants 6 (tap pairs), 7 (per tap, line staging), 8 (tap pairs, DMA spread); 192 x 192 3x3 only

@@ -282,6 +282,14 @@ struct ConvFp8Args {
 // Kernel choices are explicit launch arguments (ConvFwdArgs::tile,
 // ConvWgradArgs::variant, ConvFp8Args::variant): no process-global state.
 void launch_conv_fwd(const ConvFwdArgs& a, int mode, hipStream_t st);
+// What of a forward / dgrad launch the tile choice reads (M pixels, board side, kernel side, padded widths,
+// ConvFwdArgs::offi), and the choice itself (host only): the tile code launch_conv_fwd runs for a requested
+// code (0 = automatic), and that tile's {code, BM, waves, threads, LDS bytes, loop kind, chunk-outer, LDS slots}.
+struct FwdShape {
+  int M, S, K, Cin, Cout, offi;
+};
+int fwd_resolve_tile(const FwdShape& g, int mode, int tile);  // mode: with MODE_RES or without, the same tile
+void conv_fwd_tile_info(const FwdShape& g, int mode, int tile, int out[8]);
 // packed-tap first-layer forward (bias + ReLU, optional bitmask): cpt 8-channel chunks per tap
 void launch_conv_fwd_pk(const ConvFwdArgs& a, int cpt, hipStream_t st);
 void launch_conv_wgrad(const ConvWgradArgs& a, hipStream_t st);
@@ -315,8 +323,15 @@ int wgrad_tap_group(int Cout, int Cin, int K, int variant);  // taps per wgrad w
 int wgrad_row_code(int Cout, int Cin, int cin_real, int K);
 int wgrad_row_wgs_per_split(int code, int Cout, int Cin, int cin_real, int K);
 void wgrad_row_launch(int code, const ConvWgradArgs& a, hipStream_t st);
-// launch plan of the wgrad that launch_conv_wgrad runs for this variant:
-// {taps per workgroup, workgroups per split, resident workgroups per CU}
+// The tile launch_conv_wgrad runs for a layer and variant (host only; the launch and this are one walk over
+// the launchers): taps per workgroup, workgroups per split, the resident workgroups per CU its grid is sized
+// for, threads per workgroup, and the tile's n x c widths.  wgrad_plan: the first four, for the trainers.
+// Both raise for width pairs the launcher has no tile for (Cout 160 with a Cin that is neither 160 nor an odd
+// multiple of 64; Cin 160 with another Cout), as the launch does.
+struct WgradChoice {
+  int taps, wgs_per_split, per_cu, threads, wn, wc, lds_bytes;
+};
+WgradChoice wgrad_choose(int Cout, int Cin, int cin_real, int K, int variant);
 void wgrad_plan(int Cout, int Cin, int cin_real, int K, int variant, int out[4]);
 // a launch the runtime must reject (block of 2048 threads): tests the error path
 void launch_invalid_config_probe(hipStream_t st);

@@ -868,6 +868,23 @@ std::vector<int64_t> wgrad_plan(int64_t cout, int64_t cin, int64_t cin_real, int
   return {o[0], o[1], o[2], o[3]};
 }
 
+// host only: wgrad_plan's four values, then the tile's n and c widths and its dynamic LDS bytes
+std::vector<int64_t> wgrad_choice(int64_t cout, int64_t cin, int64_t cin_real, int64_t K, int64_t variant) {
+  const agk::WgradChoice c = agk::wgrad_choose((int)cout, (int)cin, (int)(cin_real > 0 && cin_real < cin ? cin_real : cin),
+                                               (int)K, (int)variant);
+  return {c.taps, c.wgs_per_split, c.per_cu, c.threads, c.wn, c.wc, c.lds_bytes};
+}
+
+// host only: {resolved tile code, BM, waves, threads, LDS bytes, loop kind, chunk-outer, LDS slots} of the tile
+// conv_fwd runs for M pixels of side-S boards (pin: the input's padding, -1 = the kernel's radius)
+std::vector<int64_t> conv_fwd_tile_info(int64_t M, int64_t S, int64_t K, int64_t cin, int64_t cout, int64_t mode,
+                                        bool res, int64_t tile, int64_t pin) {
+  int o[8];
+  const agk::FwdShape g{(int)M, (int)S, (int)K, (int)cin, (int)cout, pin < 0 ? 0 : (int)(pin - K / 2)};
+  agk::conv_fwd_tile_info(g, (int)(res ? mode | agk::MODE_RES : mode), (int)tile, o);
+  return std::vector<int64_t>(o, o + 8);
+}
+
 void comm_proxy(const Tensor& src, const Tensor& dst, int64_t channels, double wire_us) {
   check_dev("comm_proxy", src, dst);
   TORCH_CHECK(src.scalar_type() == at::kFloat && dst.scalar_type() == at::kFloat && src.is_contiguous() &&
@@ -1116,6 +1133,10 @@ TORCH_LIBRARY(alphago_amd, m) {
   m.def("quantize_fp8(Tensor x, Tensor(a!) y, float scale) -> ()");
   m.def("wgrad_tap_group(int cout, int cin, int K) -> int", &wgrad_tap_group);
   m.def("wgrad_plan(int cout, int cin, int cin_real, int K, int variant=0) -> int[]", &wgrad_plan);
+  m.def("wgrad_choice(int cout, int cin, int cin_real, int K, int variant=0) -> int[]", &wgrad_choice);
+  m.def("conv_fwd_tile_info(int M, int S, int K, int cin, int cout, int mode=0, bool res=False, int tile=0, "
+        "int pin=-1) -> int[]",
+        &conv_fwd_tile_info);
   m.def("conv_ws_supported(int cout, int cin, int K) -> bool", &conv_ws_supported);
   m.def("ws_pack(Tensor[] src, Tensor(a!)[] dst) -> ()");
   m.def("selftest_bad_launch() -> ()", &selftest_bad_launch);

@@ -128,16 +128,36 @@ def conv_fwd(x, w_packed, bias, y, K: int, S: int, Pin: int, Po: int = 1, mode: 
     ``res`` (modes 0 and 3, a bf16 tensor of ``y``'s shape that is not ``y``): the skip operand of a
     residual block, ``relu(conv + bias + res)`` / ``(dgrad + res)`` under the bitmask, read at interior
     pixels only.
-    ``tile``: 0 = automatic, or a production tiling: 36 / 37 (32 pixels), 40 (weight-stationary), 64 /
-    128 / 256, 384 (96 x 96 per wave), 385 (384 with the DMA issue spread through the MFMAs), 386 / 387
-    (385 / 384 with the chunk-outer K order), 388 (386 with the pixel rows staged once per 64-channel
-    chunk -- the compact halo; 3x3, 192-wide output tile, S <= 19, bias + ReLU and bitmask dgrad, else it
-    runs 386; the automatic choice for large batches, bit-identical to 386)."""
+    ``tile``: 0 = automatic, 40 = weight-stationary, or a tile code of docs/ARCHITECTURE.md's table;
+    ``conv_fwd_tile_info`` tells which tile a layer and code run."""
     if res is None:
         _ops().conv_fwd(x, w_packed, bias, mask, y, K, S, Pin, Po, mode, mbits, tile)
     else:
         _ops().conv_fwd(x, w_packed, bias, mask, y, K, S, Pin, Po, mode, mbits, tile, res)
     return y
+
+
+FWD_LOOPS = ("pipelined", "pipelined, late epilogue load", "plain", "dma-spread", "mfma32", "ring", "compact-halo")
+
+
+class FwdTileInfo(NamedTuple):
+    code: int
+    bm: int
+    waves: int
+    threads: int
+    lds_bytes: int
+    loop: str
+    chunk_outer: bool
+    slots: int
+
+
+def conv_fwd_tile_info(M: int, S: int, K: int, cin_p: int, cout_p: int, mode: int = MODE_BIAS_RELU,
+                       res: bool = False, tile: int = 0, Pin: int = -1) -> FwdTileInfo:
+    """The tile ``conv_fwd`` runs for ``M`` output pixels of side-``S`` boards and a requested ``tile`` code
+    (0 = automatic; not the weight-stationary code 40): the resolved code and its geometry, read on the
+    host from the description the launcher instantiates.  ``loop`` is one of ``FWD_LOOPS``."""
+    v = [int(t) for t in _ops().conv_fwd_tile_info(M, S, K, cin_p, cout_p, mode, res, tile, Pin)]
+    return FwdTileInfo(v[0], v[1], v[2], v[3], v[4], FWD_LOOPS[v[5]], bool(v[6]), v[7])
 
 
 # split-K forward / dgrad (tile 38) below this many output pixels (B <= 8 at 19 x 19); ALPHAGO_AMD_SPLITK=0
@@ -483,6 +503,12 @@ def packed_weight_like(w_oihw: torch.Tensor, cin_p: int, cout_p: int, transposed
 def wgrad_tap_group(cout_p: int, cin_p: int, K: int) -> int:
     """Kernel taps one wgrad workgroup covers (K for tap-merged 64-wide c tiles, else 1)."""
     return int(_ops().wgrad_tap_group(cout_p, cin_p, K))
+
+
+def wgrad_choice(cout_p: int, cin_p: int, K: int, cin_real: int = 0, variant: int = 0):
+    """The tile conv_wgrad launches: ``wgrad_plan``'s four values, then the tile's n and c widths and its dynamic
+    LDS bytes (host only; read from the launcher's own choice)."""
+    return tuple(int(v) for v in _ops().wgrad_choice(cout_p, cin_p, cin_real, K, variant))
 
 
 def wgrad_plan(cout_p: int, cin_p: int, K: int, cin_real: int = 0, variant: int = 0):

@@ -52,11 +52,24 @@ def demangle(names):
 
 
 def short_name(dem: str) -> str:
-    """conv_fwd_kernel<192, 0, 384, 6, false, ...> -> name<args> with bools as 0/1 and the mode spelled out."""
-    m = re.search(r"(conv_\w+)<([^>]*)>", dem)
+    """conv_fwd_kernel<192, 0, agk::Tile386, false> -> conv_fwd_kernel<192, bias+ReLU, Tile386, 0>: the template
+    arguments (a tile description may carry its own, WgradRow<192, 3>) without the namespace, bools as 0/1
+    and the mode spelled out."""
+    m = re.search(r"(conv_\w+)<", dem)
     if not m:
         return dem
-    args = [a.strip().replace("false", "0").replace("true", "1") for a in m.group(2).split(",")]
+    args, depth, cur = [], 1, ""
+    for ch in dem[m.end():]:
+        depth += (ch == "<") - (ch == ">")
+        if depth == 0:
+            break
+        if ch == "," and depth == 1:
+            args.append(cur)
+            cur = ""
+        else:
+            cur += ch
+    args.append(cur)
+    args = [re.sub(r"\bfalse\b", "0", re.sub(r"\btrue\b", "1", re.sub(r"\bagk(_lab)?::", "", a.strip()))) for a in args]
     args = [re.sub(r"^\(\w+\)", "", a) for a in args]
     if len(args) > 1 and args[1].isdigit():
         args[1] = MODES.get(int(args[1]), args[1])
@@ -138,7 +151,7 @@ def compress(toks):
 
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--flavor", default="prod", choices=("prod", "lab"))
+    ap.add_argument("--flavor", default="prod", choices=("prod", "debug", "lab"))
     ap.add_argument("--src", default="conv.hip", help="file under alphago_amd/csrc/kernels")
     ap.add_argument("--keep", default="", help="keep the assembly at this path")
     ap.add_argument("--asm", default="", help="read this assembly file instead of compiling")

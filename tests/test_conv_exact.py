@@ -604,10 +604,9 @@ def test_every_kernel_reached(ops, cuda_device):
         S, B, K = case[0], case[1], case[4]
         M = B * S * S
         assert M < 8192
-        halo = K == 3 and ops.conv_n_tile(wout) == 192 and wred % 64 == 0 and S <= 19
         for tile in PROD_TILES:
             if _tile_ok(wout, tile):
-                runs_as = 36 if tile == 0 else 386 if tile == 388 and not halo else tile
+                runs_as = ops.conv_fwd_tile_info(M, S, K, wred, wout, 0 if kind == "fwd" else 3, tile=tile).code
                 hit("tile %d" % runs_as, (kind, case))
         hit("N tile %d" % ops.conv_n_tile(wout), (kind, case))
         if wred % 64 == 32:

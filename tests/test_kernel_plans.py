@@ -99,6 +99,124 @@ def test_small_batch_wgrad_plan(B, small):
     assert ops.wgrad_config(B * S2, 160, 160, 3)[0] == 0
 
 
+# ----------------------------------------------------------------------------- forward / dgrad tile table
+# code: (pixels per workgroup, waves, threads, K loop, chunk-outer K order, LDS slots), as the launch sites
+# spelled them before the tile descriptions existed; LDS = slots x (BM + BN) x 128 bytes
+FWD_TILES = {
+    36: (32, 4, 256, "pipelined", False, 2), 37: (32, 2, 128, "pipelined", False, 2),
+    38: (32, 4, 256, "pipelined", False, 2), 64: (64, 4, 256, "pipelined", False, 2),
+    128: (128, 4, 256, "pipelined", False, 2), 256: (256, 8, 512, "pipelined", False, 2),
+    384: (384, 8, 512, "plain", False, 2), 385: (384, 8, 512, "dma-spread", False, 2),
+    386: (384, 8, 512, "dma-spread", True, 2), 387: (384, 8, 512, "plain", True, 2),
+}
+HALO388 = (388, 384, 8, 512, 2 * 432 * 128 + 2 * 192 * 128, "compact-halo", True, 2)  # 159744 B
+LAB_TILES = (7, 8, 9, 10, 65, 130, 2560, 2568)
+MODE_MASK, MODE_MASKBITS = 1, 3
+
+
+def _row(code, bn):
+    bm, waves, threads, loop, co, slots = FWD_TILES[code]
+    return (code, bm, waves, threads, slots * (bm + bn) * 128, loop, co, slots)
+
+
+@pytest.mark.parametrize("cout,bn", [(64, 64), (128, 128), (160, 160), (192, 192), (384, 192), (256, 128), (320, 64)])
+def test_conv_fwd_tile_table(cout, bn):
+    """Every production code on every width: the resolved code, BM, waves, threads, LDS bytes, loop, K order
+    and ring depth of the tile that runs.  160-wide has no 37; the kernel-lab codes raise here."""
+    for cin, K in ((cout if cout == 160 else 192, 3), (64, 5)):
+        for code in FWD_TILES:
+            if bn == 160 and code == 37:
+                with pytest.raises(ValueError, match="160-wide tiles support tile codes"):
+                    ops.conv_fwd_tile_info(S2, 19, K, cin, cout, tile=code)
+                continue
+            assert tuple(ops.conv_fwd_tile_info(S2, 19, K, cin, cout, tile=code)) == _row(code, bn), (code, cin, K)
+        for code in LAB_TILES + (1, 39, 389):
+            with pytest.raises(ValueError, match="160-wide tiles support" if bn == 160 else "unknown tile code %d" % code):
+                ops.conv_fwd_tile_info(S2, 19, K, cin, cout, tile=code)
+
+
+def test_conv_fwd_tile_388():
+    """388 is the compact-halo kernel where it covers the layer and 386 everywhere else."""
+    for mode in (0, MODE_MASKBITS):
+        for res in (False, True):
+            for S in (9, 13, 19):
+                for cin in (64, 128, 192, 256):
+                    assert tuple(ops.conv_fwd_tile_info(S2, S, 3, cin, 192, mode, res, 388)) == HALO388
+            assert tuple(ops.conv_fwd_tile_info(S2, 19, 3, 192, 384, mode, res, 388)) == HALO388
+    not_covered = [dict(S=19, K=3, cin_p=160, cout_p=160), dict(S=19, K=5, cin_p=64, cout_p=192),
+                   dict(S=21, K=3, cin_p=192, cout_p=192), dict(S=19, K=3, cin_p=192, cout_p=192, mode=MODE_MASK),
+                   dict(S=19, K=3, cin_p=192, cout_p=192, mode=2), dict(S=19, K=3, cin_p=128, cout_p=128),
+                   dict(S=19, K=3, cin_p=64, cout_p=64), dict(S=19, K=3, cin_p=192, cout_p=192, Pin=0)]
+    for kw in not_covered:
+        got = ops.conv_fwd_tile_info(S2, tile=388, **kw)
+        assert tuple(got) == _row(386, ops.conv_n_tile(kw["cout_p"])), kw
+
+
+@pytest.mark.parametrize("cout,K,cin,edges", [
+    # 192-wide, a layer the compact-halo kernel covers: 36 / 64 / 128 / 256 / 388
+    (192, 3, 192, [(64 * 256 - 1, 36), (64 * 256, 64), (128 * 256 - 1, 64), (128 * 256, 128), (256 * 512 - 1, 128),
+                   (256 * 512, 256), (384 * 512 - 1, 256), (384 * 512, 388), (2176 * S2, 388), (1, 36)]),
+    # ... and one it does not cover (5x5): 386 at the top
+    (192, 5, 64, [(64 * 256 - 1, 36), (64 * 256, 64), (128 * 256 - 1, 64), (128 * 256, 128), (256 * 512 - 1, 128),
+                  (256 * 512, 256), (384 * 512 - 1, 256), (384 * 512, 386), (2176 * S2, 386)]),
+    # 160-wide: the 32-pixel tile below 8192 pixels, then the same ladder; never the compact halo
+    (160, 3, 160, [(8191, 36), (8192, 64), (64 * 256, 64), (128 * 256 - 1, 64), (128 * 256, 128), (256 * 512 - 1, 128),
+                   (256 * 512, 256), (384 * 512 - 1, 256), (384 * 512, 386)]),
+    (160, 5, 64, [(8191, 36), (8192, 64), (384 * 512, 386)]),
+    (128, 3, 128, [(64 * 256 - 1, 36), (64 * 256, 64), (384 * 512 - 1, 256), (384 * 512, 386)]),
+])
+def test_conv_fwd_automatic_tile_edges(cout, K, cin, edges):
+    """tile 0 one below and at each threshold of the automatic rule, for the forward and the bitmask dgrad, with
+    and without a skip.  The build before fwd_resolve_tile had no host function to ask, so the expected codes are
+    written out from the five ifs its launcher held (M >= 384*512 -> 386, >= 256*512 -> 256, >= 128*256 -> 128,
+    else 64; 386 -> 388 where the compact halo covers; 36 below 64*256 pixels, below 8192 on 160-wide)."""
+    for M, want in edges:
+        for mode in (0, MODE_MASKBITS):
+            for res in (False, True):
+                assert ops.conv_fwd_tile_info(M, 19, K, cin, cout, mode, res).code == want, (M, mode, res)
+        # the plain-mask dgrad and the epilogue-free mode have no compact-halo kernel
+        for mode in (MODE_MASK, 2):
+            assert ops.conv_fwd_tile_info(M, 19, K, cin, cout, mode).code == (386 if want == 388 else want)
+
+
+# ----------------------------------------------------------------------------- wgrad plan = launch
+def test_wgrad_plan_grid():
+    """wgrad_plan and wgrad_tap_group over widths x real planes x kernel sizes x variants reproduce what the
+    hand-kept plan answered (tests/wgrad_plan_golden.py), now that they read the launcher's own choice."""
+    from wgrad_plan_golden import ROWS, VARIANTS
+
+    assert VARIANTS[1] == ops.WGRAD_SMALL and len(ROWS) == 99
+    widths = (64, 128, 160, 192)
+    legal = [(co, ci) for co in widths for ci in widths if (co == 160) == (ci == 160) or (co == 160 and ci == 64)]
+    assert sorted({k[:2] for k in ROWS}) == sorted(legal)
+    bad = {}
+    for (co, ci, cr, K), (group, plans) in ROWS.items():
+        if ops.wgrad_tap_group(co, ci, K) != group:
+            bad[(co, ci, cr, K, "tap group")] = ops.wgrad_tap_group(co, ci, K)
+        for v, want in zip(VARIANTS, plans):
+            got = tuple(ops.wgrad_plan(co, ci, K, cr, v))
+            if got != want:
+                bad[(co, ci, cr, K, v)] = (got, want)
+    assert bad == {}
+
+
+def test_wgrad_choice_tiles_and_lds():
+    """The tile behind a plan: n x c widths and dynamic LDS bytes, 2 buffers x (WN + WC x taps) x 64 bytes x 32
+    pixels as the launch sites computed them: the per-tap 192 x 192 tile, the value net's 160 x 160 on 4 waves, the
+    tap-merged rows, the thin first layer's 48-wide rows (96-wide halves at 5x5) and the small-batch plan."""
+    want = {(192, 192, 3, 0, 0): (1, 9, 2, 512, 192, 192, 49152), (160, 160, 3, 0, 0): (1, 9, 2, 256, 160, 160, 40960),
+            (192, 64, 3, 0, 0): (3, 3, 2, 512, 192, 64, 49152), (160, 64, 5, 49, 0): (5, 5, 1, 512, 160, 64, 61440),
+            (192, 64, 5, 48, 0): (5, 10, 2, 384, 96, 48, 43008), (192, 64, 3, 48, 0): (3, 3, 2, 384, 192, 48, 43008),
+            (128, 192, 1, 0, 0): (1, 1, 2, 512, 128, 192, 40960), (64, 128, 3, 0, 0): (1, 9, 2, 512, 64, 128, 24576),
+            (192, 192, 3, 0, ops.WGRAD_SMALL): (3, 27, 2, 512, 64, 64, 32768)}
+    for (co, ci, K, cr, v), row in want.items():
+        assert ops.wgrad_choice(co, ci, K, cr, v) == row, (co, ci, K, cr, v)
+        assert ops.wgrad_choice(co, ci, K, cr, v)[:4] == tuple(ops.wgrad_plan(co, ci, K, cr, v))
+    for co, ci in ((160, 128), (64, 160)):  # no tile for these width pairs: the plan raises as the launch does
+        with pytest.raises(ValueError, match="conv_wgrad: C(out|in) 160"):
+            ops.wgrad_plan(co, ci, 3)
+
+
 def test_automatic_overlap_range():
     from alphago_amd.train.engine import OVERLAP_AUTO_MAX_PIXELS, OVERLAP_AUTO_MIN_PIXELS
 
