@@ -92,9 +92,14 @@ def _init_model(argv):
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--residual", action="store_true",
                    help="pv only: a residual trunk (stem + two-layer blocks with a skip connection; --layers odd)")
+    p.add_argument("--ownership", action="store_true",
+                   help="pv only: a third 1x1 head predicting each point's owner at the end of the game "
+                        "(trained by train-pv on selfplay-mcts --ownership records)")
     a = p.parse_args(argv)
     if a.residual and a.kind != "pv":
         p.error("--residual needs the dual net (init-model pv): a Keras Sequential cannot express a skip connection")
+    if a.ownership and a.kind != "pv":
+        p.error("--ownership needs the dual net (init-model pv)")
     import torch
 
     torch.manual_seed(a.seed)
@@ -104,6 +109,8 @@ def _init_model(argv):
     elif a.kind == "pv":
         feats = a.features.split(",") if a.features else VALUE_FEATURES
         kw = {"residual": 1} if a.residual else {}
+        if a.ownership:
+            kw["ownership"] = 1
         try:
             m = CNNPolicyValue(feats, board=a.board, filters_per_layer=a.filters or 192, layers=a.layers,
                                device="cpu", **kw)

@@ -154,6 +154,12 @@ PYBIND11_MODULE(_engine, m) {
            },
            py::arg("include_eyes") = true)
       .def("get_winner", &GameState::get_winner)
+      .def("get_ownership",
+           [](const GameState& s) {
+             py::array_t<int8_t> a({s.n, s.n});
+             s.ownership(a.mutable_data());
+             return a;
+           })
       .def("get_group", [](const GameState& s, py::object a) { return stones_to_set(s, s.group_stones(to_idx(s, a))); })
       .def("get_groups_around",
            [](const GameState& s, py::object a) {

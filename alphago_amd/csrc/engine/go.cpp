@@ -184,6 +184,17 @@ int GameState::get_winner() const {
   return 0;
 }
 
+void GameState::ownership(int8_t* out) const {
+  // the map get_winner scores by, in its order of tests
+  for (int p = 0; p < np; ++p) {
+    if (board[p] == WHITE) out[p] = -1;
+    else if (board[p] == BLACK) out[p] = 1;
+    else if (is_eyeish(p, BLACK)) out[p] = 1;
+    else if (is_eyeish(p, WHITE)) out[p] = -1;
+    else out[p] = 0;
+  }
+}
+
 void GameState::place_stone(int p, int8_t color) {
   // go.py:104-136 (_update_neighbors) with bitset liberties
   board[p] = color;

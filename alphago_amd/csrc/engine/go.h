@@ -107,6 +107,8 @@ struct GameState {
   bool is_eye(int p, int owner) const;
   void legal_moves(std::vector<int>& out, bool include_eyes = true) const;
   int get_winner() const;
+  // the per-point map get_winner counts: +1 Black, -1 White, 0 neither (out: np entries, x * n + y)
+  void ownership(int8_t* out) const;
   // returns is_end_of_game; throws IllegalMove
   bool do_move(int p, int color = 0);
   // Same as do_move but returns false instead of throwing.

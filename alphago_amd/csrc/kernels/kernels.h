@@ -365,6 +365,61 @@ void launch_policy_value_head(const PolicyValueHeadArgs& a, hipStream_t st);
 // head_backward that adds into dz instead of overwriting it (PolicyHeadArgs: y, w, dz, dhead, B, S, C, C_real)
 void launch_head_backward_add(const PolicyHeadArgs& a, const float* dlogits, hipStream_t st);
 
+// The ownership head of the dual net (head_own.hip): a third 1x1 head, tanh per board point, trained
+// on the final territory map in the mover's frame.
+//
+// value_own_head: one read of the board gives the value head's logits zv (head_logits' quantity) and the
+// ownership row o = y . wo + bo, own = tanhf(o).  With a target t (int8 in {-1, 0, +1}, stored frame,
+// gathered through the board's symmetry as policy_head_soft gathers tdist) also, per board,
+//   oloss = (1 / SS) sum_p (own - t)^2,  oagree = #{p : t != 0 and sign(own) == t},
+//   dlo[p] = grad_scale * k * (2 / SS) * (own - t) * (1 - own^2),  k = valid[b] * weight[b] (null = 1);
+// a board with k == 0 writes zeros to dlo and still writes oloss and oagree.
+struct ValueOwnHeadArgs {
+  const __bf16* y;       // padded NHWC (HP = S+2, P = 1, C)
+  const float* wv;       // [C_real] value head
+  const float* bv;       // [1]
+  const float* wo;       // [C_real] ownership head
+  const float* bo;       // [1]
+  const int8_t* target;  // [B][S*S] or null (forward only)
+  const int* sym;        // [B] in 0..7 or null
+  const float* valid;    // [B] or null
+  const float* weight;   // [B] or null
+  float* zv;             // [B][S*S]
+  float* own;            // [B][S*S] or null
+  float* olog;           // [B][S*S] or null: the ownership row before tanh
+  float* oloss;          // [B]        (with a target)
+  float* oagree;         // [B]        (with a target)
+  float* dlo;            // [B][S*S]   (with a target)
+  int B, S, C, C_real;
+  float grad_scale;
+};
+void launch_value_own_head(const ValueOwnHeadArgs& a, hipStream_t st);
+
+// head_backward_add for two heads in one pass over y and dz.  Where y > 0:
+//   dz[p, c] = bf16_rne(fma(g2[p], w2[c], fma(g1[p], w1[c], float(dz[p, c]))))
+// and two partial blocks [B][C_real + 1], each in head_backward_add's order.
+struct HeadBackwardAdd2Args {
+  const __bf16* y;
+  const float* w1;  // [C_real]
+  const float* w2;  // [C_real]
+  const float* g1;  // [B][S*S]
+  const float* g2;  // [B][S*S]
+  __bf16* dz;
+  float* dhead1;    // [B][C_real + 1]
+  float* dhead2;    // [B][C_real + 1]
+  int B, S, C, C_real;
+};
+void launch_head_backward_add2(const HeadBackwardAdd2Args& a, hipStream_t st);
+
+// policy_value_head plus the ownership row: probs and zv with policy_value_head's bits, own = tanhf(y . wo + bo)
+struct PolicyValueOwnHeadArgs {
+  PolicyValueHeadArgs pv;
+  const float* wo;  // [C_real]
+  const float* bo;  // [1]
+  float* own;       // [B][S*S]
+};
+void launch_policy_value_own_head(const PolicyValueOwnHeadArgs& a, hipStream_t st);
+
 // fused move sampling (sample.hip): out[b] = a draw from probs[b]**beta, -1 where has[b] == 0
 struct SampleArgs {
   const float* probs;    // [B][NP]

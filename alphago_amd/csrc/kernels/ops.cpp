@@ -408,6 +408,146 @@ void policy_value_head(const Tensor& y, const Tensor& wp, const Tensor& bp, cons
   launch_check("policy_value_head");
 }
 
+// the geometry checks the ownership-head ops share: y (B, S+2, S+2, C) bf16, 1x1 head weights / biases f32
+void own_head_geometry(const char* op, const Tensor& y, int64_t S, std::initializer_list<const Tensor*> ws,
+                       std::initializer_list<const Tensor*> bs) {
+  CHECK_BF16(y); CHECK_CONTIG(y);
+  TORCH_CHECK(y.dim() == 4, op, ": head input must be (B, S+2, S+2, C)");
+  const int64_t C = y.size(3);
+  TORCH_CHECK(y.size(1) == S + 2 && y.size(2) == S + 2, op, ": head input must have pad 1");
+  TORCH_CHECK(C % 8 == 0 && C >= 8 && C <= 256, op, ": head channels must be a multiple of 8 and <= 256");
+  TORCH_CHECK(S >= 1 && S * S <= 361, op, ": board too large (the head holds at most 19 x 19)");
+  TORCH_CHECK(y.numel() < (1ll << 31), op, ": tensor too large");
+  const Tensor* w0 = *ws.begin();
+  for (const Tensor* w : ws) {
+    CHECK_F32(*w); CHECK_CONTIG(*w);
+    TORCH_CHECK(w->numel() >= 1 && w->numel() <= C && w->numel() == w0->numel(), op,
+                ": head weights must have the same (at most C) entries");
+  }
+  for (const Tensor* b : bs) {
+    CHECK_F32(*b);
+    TORCH_CHECK(b->numel() >= 1, op, ": head biases must hold one entry");
+  }
+}
+
+// Training / evaluation forward of the value and ownership heads from one read of the board (head_own.hip):
+// zv = y . wv + bv (head_logits' quantity), olog = y . wo + bo, own = tanhf(olog); with a target (int8
+// (B, S*S), stored frame, moved by sym inside the kernel) also oloss, oagree (B,) and dlo (B, S*S).
+void value_own_head(const Tensor& y, const Tensor& wv, const Tensor& bv, const Tensor& wo, const Tensor& bo,
+                    const Tensor& zv, const c10::optional<Tensor>& own, const c10::optional<Tensor>& olog,
+                    const c10::optional<Tensor>& target, const c10::optional<Tensor>& sym,
+                    const c10::optional<Tensor>& valid, const c10::optional<Tensor>& weight,
+                    const c10::optional<Tensor>& oloss, const c10::optional<Tensor>& oagree,
+                    const c10::optional<Tensor>& dlo, int64_t S, double grad_scale) {
+  check_dev("value_own_head", y, wv, bv, wo, bo, zv, own, olog, target, sym, valid, weight, oloss, oagree, dlo);
+  own_head_geometry("value_own_head", y, S, {&wv, &wo}, {&bv, &bo});
+  const int64_t B = y.size(0), C = y.size(3), SS = S * S;
+  CHECK_F32(zv); CHECK_CONTIG(zv);
+  TORCH_CHECK(zv.numel() == B * SS, "value_own_head: zv must be (B, S*S)");
+  agk::ValueOwnHeadArgs a{};
+  a.y = bfp(y);
+  a.wv = wv.data_ptr<float>(); a.bv = bv.data_ptr<float>();
+  a.wo = wo.data_ptr<float>(); a.bo = bo.data_ptr<float>();
+  a.zv = zv.data_ptr<float>();
+  a.B = (int)B; a.S = (int)S; a.C = (int)C; a.C_real = (int)wv.numel();
+  a.grad_scale = (float)grad_scale;
+  if (own.has_value()) {
+    CHECK_F32(*own); CHECK_CONTIG(*own);
+    TORCH_CHECK(own->numel() == B * SS, "value_own_head: own must be (B, S*S)");
+    a.own = own->data_ptr<float>();
+  }
+  if (olog.has_value()) {
+    CHECK_F32(*olog); CHECK_CONTIG(*olog);
+    TORCH_CHECK(olog->numel() == B * SS, "value_own_head: olog must be (B, S*S)");
+    a.olog = olog->data_ptr<float>();
+  }
+  if (target.has_value()) {
+    TORCH_CHECK(target->scalar_type() == at::kChar && target->dim() == 2 && target->size(0) == B &&
+                    target->size(1) == SS && target->is_contiguous(), "value_own_head: target must be int8 (B, S*S)");
+    TORCH_CHECK(oloss.has_value() && oagree.has_value() && dlo.has_value(),
+                "value_own_head: a target needs oloss, oagree and dlo");
+    CHECK_F32(*oloss); CHECK_F32(*oagree); CHECK_F32(*dlo);
+    CHECK_CONTIG(*oloss); CHECK_CONTIG(*oagree); CHECK_CONTIG(*dlo);
+    TORCH_CHECK(oloss->numel() == B && oagree->numel() == B && dlo->numel() == B * SS,
+                "value_own_head: oloss, oagree (B,), dlo (B, S*S)");
+    a.target = target->data_ptr<int8_t>();
+    a.oloss = oloss->data_ptr<float>(); a.oagree = oagree->data_ptr<float>(); a.dlo = dlo->data_ptr<float>();
+    if (sym.has_value()) {
+      TORCH_CHECK(sym->scalar_type() == at::kInt && sym->numel() == B && sym->is_contiguous(),
+                  "value_own_head: sym int32 (B,)");
+      a.sym = sym->data_ptr<int>();
+    }
+    if (valid.has_value()) {
+      CHECK_F32(*valid); CHECK_CONTIG(*valid);
+      TORCH_CHECK(valid->numel() == B, "value_own_head: valid must be (B,)");
+      a.valid = valid->data_ptr<float>();
+    }
+    if (weight.has_value()) {
+      CHECK_F32(*weight); CHECK_CONTIG(*weight);
+      TORCH_CHECK(weight->numel() == B, "value_own_head: weight must be (B,)");
+      a.weight = weight->data_ptr<float>();
+    }
+  } else {
+    TORCH_CHECK(!sym.has_value() && !valid.has_value() && !weight.has_value() && !oloss.has_value() &&
+                    !oagree.has_value() && !dlo.has_value(),
+                "value_own_head: sym, valid, weight, oloss, oagree and dlo go with a target");
+  }
+  if (B == 0) return;
+  agk::launch_value_own_head(a, cur_stream());
+  launch_check("value_own_head");
+}
+
+// head_backward_add for two heads in one pass: where y > 0, dz = bf16(fma(g2, w2, fma(g1, w1, dz))); dhead1 /
+// dhead2 (B, C_real + 1) as head_backward_add's dhead.  dz8 is refused like its sibling's.
+void head_backward_add2(const Tensor& y, const Tensor& w1, const Tensor& g1, const Tensor& w2, const Tensor& g2,
+                        const Tensor& dz, const Tensor& dhead1, const Tensor& dhead2, int64_t S,
+                        const c10::optional<Tensor>& dz8) {
+  check_dev("head_backward_add2", y, w1, g1, w2, g2, dz, dhead1, dhead2, dz8);
+  TORCH_CHECK(!dz8.has_value(), "head_backward_add2: accumulating into an e5m2 dz8 is not supported "
+              "(accumulate into the bf16 dz and quantise it with quantize_bf8)");
+  own_head_geometry("head_backward_add2", y, S, {&w1, &w2}, {});
+  const int64_t B = y.size(0), C = y.size(3), SS = S * S, N = w1.numel() + 1;
+  CHECK_F32(g1); CHECK_CONTIG(g1); CHECK_F32(g2); CHECK_CONTIG(g2);
+  CHECK_BF16(dz); CHECK_CONTIG(dz); CHECK_F32(dhead1); CHECK_CONTIG(dhead1); CHECK_F32(dhead2); CHECK_CONTIG(dhead2);
+  TORCH_CHECK(dz.sizes() == y.sizes() && g1.numel() == B * SS && g2.numel() == B * SS && dhead1.numel() >= B * N &&
+                  dhead2.numel() >= B * N, "head_backward_add2: dz as y, g1 / g2 (B, S*S), dhead1 / dhead2 (B, C_real + 1)");
+  agk::HeadBackwardAdd2Args a{};
+  a.y = bfp(y); a.w1 = w1.data_ptr<float>(); a.w2 = w2.data_ptr<float>();
+  a.g1 = g1.data_ptr<float>(); a.g2 = g2.data_ptr<float>();
+  a.dz = bfp_mut(dz); a.dhead1 = dhead1.data_ptr<float>(); a.dhead2 = dhead2.data_ptr<float>();
+  a.B = (int)B; a.S = (int)S; a.C = (int)C; a.C_real = (int)w1.numel();
+  if (B == 0) return;
+  agk::launch_head_backward_add2(a, cur_stream());
+  launch_check("head_backward_add2");
+}
+
+// policy_value_head plus own (B, S*S) = tanhf(y . wo + bo); probs and zv carry policy_value_head's bits
+void policy_value_own_head(const Tensor& y, const Tensor& wp, const Tensor& bp, const Tensor& wv, const Tensor& bv,
+                           const Tensor& wo, const Tensor& bo, const Tensor& probs, const Tensor& zv, const Tensor& own,
+                           int64_t S, const c10::optional<Tensor>& legal) {
+  check_dev("policy_value_own_head", y, wp, bp, wv, bv, wo, bo, probs, zv, own, legal);
+  own_head_geometry("policy_value_own_head", y, S, {&wp, &wv, &wo}, {&bp, &bv, &bo});
+  const int64_t B = y.size(0), C = y.size(3), SS = S * S;
+  CHECK_F32(probs); CHECK_CONTIG(probs); CHECK_F32(zv); CHECK_CONTIG(zv); CHECK_F32(own); CHECK_CONTIG(own);
+  TORCH_CHECK(probs.numel() == B * SS && zv.numel() == B * SS && own.numel() == B * SS,
+              "policy_value_own_head: probs, zv and own must be (B, S*S)");
+  agk::PolicyValueOwnHeadArgs a{};
+  a.pv.y = bfp(y);
+  a.pv.wp = wp.data_ptr<float>(); a.pv.bp = bp.data_ptr<float>();
+  a.pv.wv = wv.data_ptr<float>(); a.pv.bv = bv.data_ptr<float>();
+  a.wo = wo.data_ptr<float>(); a.bo = bo.data_ptr<float>();
+  a.pv.probs = probs.data_ptr<float>(); a.pv.zv = zv.data_ptr<float>(); a.own = own.data_ptr<float>();
+  a.pv.B = (int)B; a.pv.S = (int)S; a.pv.C = (int)C; a.pv.C_real = (int)wp.numel();
+  if (legal.has_value()) {
+    TORCH_CHECK(legal->scalar_type() == at::kByte && legal->numel() == B * SS && legal->is_contiguous(),
+                "policy_value_own_head: legal must be uint8 (B, S*S)");
+    a.pv.legal = legal->data_ptr<uint8_t>();
+  }
+  if (B == 0) return;
+  agk::launch_policy_value_own_head(a, cur_stream());
+  launch_check("policy_value_own_head");
+}
+
 void value_out(const Tensor& h, const Tensor& w2, const Tensor& b2, const c10::optional<Tensor>& target,
                const c10::optional<Tensor>& weight, const Tensor& v, const c10::optional<Tensor>& loss,
                const c10::optional<Tensor>& correct, const c10::optional<Tensor>& dh, const c10::optional<Tensor>& dout,
@@ -1091,6 +1231,13 @@ TORCH_LIBRARY(alphago_amd, m) {
         "Tensor(c!)? dz8=None) -> ()");
   m.def("policy_value_head(Tensor y, Tensor wp, Tensor bp, Tensor wv, Tensor bv, Tensor(a!) probs, Tensor(b!) zv, "
         "int S, Tensor? legal=None) -> ()");
+  m.def("value_own_head(Tensor y, Tensor wv, Tensor bv, Tensor wo, Tensor bo, Tensor(a!) zv, Tensor(b!)? own=None, "
+        "Tensor(c!)? olog=None, Tensor? target=None, Tensor? sym=None, Tensor? valid=None, Tensor? weight=None, "
+        "Tensor(d!)? oloss=None, Tensor(e!)? oagree=None, Tensor(f!)? dlo=None, int S=19, float grad_scale=1.0) -> ()");
+  m.def("head_backward_add2(Tensor y, Tensor w1, Tensor g1, Tensor w2, Tensor g2, Tensor(a!) dz, Tensor(b!) dhead1, "
+        "Tensor(c!) dhead2, int S, Tensor(d!)? dz8=None) -> ()");
+  m.def("policy_value_own_head(Tensor y, Tensor wp, Tensor bp, Tensor wv, Tensor bv, Tensor wo, Tensor bo, "
+        "Tensor(a!) probs, Tensor(b!) zv, Tensor(c!) own, int S, Tensor? legal=None) -> ()");
   m.def("head_grad_sums(Tensor dhead, Tensor loss, Tensor correct, Tensor(a!) grad, Tensor(b!) sums) -> ()");
   m.def(
       "value_out(Tensor h, Tensor w2, Tensor b2, Tensor? target, Tensor? weight, Tensor(a!) v, Tensor(b!)? loss, "
@@ -1173,6 +1320,9 @@ TORCH_LIBRARY_IMPL(alphago_amd, CUDA, m) {
   m.impl("head_backward", &head_backward);
   m.impl("head_backward_add", &head_backward_add);
   m.impl("policy_value_head", &policy_value_head);
+  m.impl("value_own_head", &value_own_head);
+  m.impl("head_backward_add2", &head_backward_add2);
+  m.impl("policy_value_own_head", &policy_value_own_head);
   m.impl("value_out", &value_out);
   m.impl("pack_weights", &pack_weights);
   m.impl("ws_pack", &ws_pack);

@@ -89,6 +89,7 @@ class GTPEngine(object):
             "time_settings": self._time_settings,
             "time_left": self._time_left,
             "printsgf": lambda a: gamestate_to_sgf(self.state),
+            "ownership": self._ownership,
         }
 
     # ------------------------------------------------------------- commands
@@ -212,6 +213,25 @@ class GTPEngine(object):
             row = "".join(".XO"[int(b[x, y])] + " " for x in range(self.size))
             rows.append("%2d %s" % (y + 1, row))
         rows.append("   " + " ".join(COLUMNS[:self.size]))
+        return "\n" + "\n".join(rows)
+
+    def _ownership_net(self):
+        """The player's dual net when it has the ownership head (the player itself, its ``policy`` or its
+        search's ``policy``), else None."""
+        p = self.player
+        for cand in (p, getattr(p, "policy", None), getattr(getattr(p, "search", None), "policy", None)):
+            if cand is not None and getattr(cand, "has_ownership", False):
+                return cand
+        return None
+
+    def _ownership(self, a):
+        """The net's territory estimate of the current position: S rows, top row first as showboard, of S
+        numbers with two decimals, + = Black."""
+        net = self._ownership_net()
+        if net is None:
+            raise ValueError("no ownership head")
+        own = net.eval_ownership(self.state)
+        rows = [" ".join("%+.2f" % float(own[x, y]) for x in range(self.size)) for y in reversed(range(self.size))]
         return "\n" + "\n".join(rows)
 
     def _final_score(self, a):

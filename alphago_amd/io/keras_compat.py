@@ -102,7 +102,8 @@ def model_from_keras_json(spec: str):
 
 def pv_spec(net: PolicyValueNet) -> Dict:
     """The dual net's architecture (it is no Keras Sequential: a spec key of its own, ``pv_model``);
-    ``residual: 1`` only for a residual trunk, so the spec of a plain net is what it always was."""
+    ``residual: 1`` only for a residual trunk and ``ownership: 1`` only with the ownership head, so the
+    spec of a plain net is what it always was."""
     return dict(net.arch)
 
 
@@ -122,6 +123,8 @@ def _weights_in_order(net) -> List[Tuple[str, List[torch.Tensor]]]:
         out.append(("value_convolution2d_1", [net.vhead_w, net.vhead_b]))
         out.append(("value_dense_1", [net.fc1_w, net.fc1_b]))
         out.append(("value_dense_2", [net.fc2_w, net.fc2_b]))
+        if getattr(net, "ownership", False):  # one more entry, only for a net with the ownership head
+            out.append(("ownership_convolution2d_1", [net.ohead_w, net.ohead_b]))
         return out
     names = _layer_names(net)
     out = []

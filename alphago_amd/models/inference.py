@@ -503,15 +503,24 @@ class HipPolicyValueInference(HipTrunkInference):
     The outputs of a bucket are one (B, S*S + 1) row per position, the move probabilities followed by
     the value, so that ``submit_encoded(to_host=True)`` / ``collect`` (the base class's, unchanged)
     bring both to the host in one copy behind one event; ``split_outputs`` takes such rows apart.
-    ``evaluate`` returns the pair (probs (n, S*S), values (n,)).  No symmetry ensembling yet."""
+    ``evaluate`` returns the pair (probs (n, S*S), values (n,)).  No symmetry ensembling yet.
+
+    ``ownership=True`` (a net with the ownership head only; off by default, so search does not pay for
+    it): ``policy_value_own_head`` takes the place of ``policy_value_head`` and also fills the bucket's
+    ``own`` (B, S*S), tanh of the third head in the mover's frame.  The output rows stay (B, S*S + 1);
+    ``ownership_view`` gives the device rows of a submission."""
 
     dual = True
 
-    def __init__(self, net: PolicyValueNet, device, **kw):
+    def __init__(self, net: PolicyValueNet, device, ownership: bool = False, **kw):
         if kw.get("symmetries", "none") != "none":
             raise ValueError("the dual (policy + value) engine does not ensemble over symmetries yet: "
                              "symmetries must be \"none\", not %r" % (kw["symmetries"],))
+        if ownership and not getattr(net, "ownership", False):
+            raise ValueError("ownership=True needs a PolicyValueNet with the ownership head (ownership=1)")
+        self.ownership = bool(ownership)
         self.vhead = None
+        self.ohead = None
         super().__init__(net, device, **kw)
 
     def _after_sync(self):
@@ -522,11 +531,19 @@ class HipPolicyValueInference(HipTrunkInference):
             self.vhead = [torch.empty(t.shape, dtype=torch.float32, device=self.device) for t in src]
         for dst, t in zip(self.vhead, src):
             dst.copy_(t)
+        if self.ownership:
+            osrc = [n.ohead_w.detach().view(-1), n.ohead_b.detach().view(-1)]
+            if self.ohead is None:
+                self.ohead = [torch.empty(t.shape, dtype=torch.float32, device=self.device) for t in osrc]
+            for dst, t in zip(self.ohead, osrc):
+                dst.copy_(t)
 
     def _alloc_outputs(self, bk):
         SS = self.S * self.S
         bk.probs = torch.zeros((bk.B, SS), device=self.device)
         bk.z = torch.zeros((bk.B, SS), device=self.device)
+        if self.ownership:
+            bk.own = torch.zeros((bk.B, SS), device=self.device)
         bk.h = torch.zeros((bk.B, self.vhead[2].shape[1]), device=self.device)
         bk.values = torch.zeros((bk.B,), device=self.device)
         bk.out = torch.zeros((bk.B, SS + 1), device=self.device)
@@ -534,7 +551,11 @@ class HipPolicyValueInference(HipTrunkInference):
     def _head(self, bk, y):
         vw, vb, w1, b1, w2, b2 = self.vhead
         SS = self.S * self.S
-        ops.policy_value_head(y, self.head_w, self.head_b, vw, vb, bk.probs, bk.z, self.S, legal=bk.legal)
+        if self.ownership:
+            ops.policy_value_own_head(y, self.head_w, self.head_b, vw, vb, self.ohead[0], self.ohead[1], bk.probs,
+                                      bk.z, bk.own, self.S, legal=bk.legal)
+        else:
+            ops.policy_value_head(y, self.head_w, self.head_b, vw, vb, bk.probs, bk.z, self.S, legal=bk.legal)
         ops.dense_f32(bk.z, w1, bk.h, bias=b1)
         ops.value_out(bk.h, w2.view(-1), b2, bk.values)
         bk.out[:, :SS].copy_(bk.probs)
@@ -547,6 +568,19 @@ class HipPolicyValueInference(HipTrunkInference):
         """(probs (n, S*S), values (n,)) views of output rows (device tensor or collect()'s numpy)."""
         SS = self.S * self.S
         return out[:, :SS], out[:, SS]
+
+    def ownership_view(self, handle=None):
+        """Device rows (n, S*S) of the ownership head for the last submission (or ``handle``'s bucket,
+        valid until it is submitted again), in the mover's frame."""
+        if not self.ownership:
+            raise RuntimeError("this engine was built without ownership=True")
+        if handle is not None:
+            bk, n = handle[0], handle[1]
+        elif self._last_sub is not None:
+            bk, n = self._last_sub
+        else:
+            raise RuntimeError("nothing submitted yet")
+        return bk.own[:n]
 
     @torch.no_grad()
     def evaluate(self, planes, legal=None, slot: int = 0):
@@ -668,19 +702,37 @@ class TorchPolicyValueInference:
     dual = True
     symmetries = "none"
 
-    def __init__(self, net: PolicyValueNet, device="cpu", symmetries: str = "none", symmetry_seed: int = 0):
+    def __init__(self, net: PolicyValueNet, device="cpu", symmetries: str = "none", symmetry_seed: int = 0,
+                 ownership: bool = False):
         if _check_symmetries(symmetries) != "none":
             raise ValueError("the dual (policy + value) engine does not ensemble over symmetries yet: "
                              "symmetries must be \"none\", not %r" % (symmetries,))
+        if ownership and not getattr(net, "ownership", False):
+            raise ValueError("ownership=True needs a PolicyValueNet with the ownership head (ownership=1)")
         self.net, self.device = net, torch.device(device)
+        self.ownership = bool(ownership)
+        self._own = None
 
     def sync_weights(self):
         pass
 
+    def ownership_view(self, handle=None):
+        """(n, S*S) ownership rows of the last evaluate, in the mover's frame."""
+        if not self.ownership:
+            raise RuntimeError("this engine was built without ownership=True")
+        if self._own is None:
+            raise RuntimeError("nothing submitted yet")
+        return self._own
+
     @torch.no_grad()
     def evaluate(self, planes, legal=None, slot: int = 0):
         x = torch.as_tensor(planes).to(self.device)
-        logits, values = self.net.logits_value_torch(x.float())
+        if self.ownership:
+            h = self.net.trunk.forward_torch(x.float())
+            logits, values = self.net.heads_torch(h)
+            self._own = self.net.ownership_torch(h)
+        else:
+            logits, values = self.net.logits_value_torch(x.float())
         if legal is not None:
             logits = logits.masked_fill(torch.as_tensor(legal).to(self.device) == 0, float("-inf"))
         return torch.nan_to_num(torch.softmax(logits, 1), nan=0.0), values
@@ -688,7 +740,7 @@ class TorchPolicyValueInference:
 
 def _torch_kw(kw):
     """The engine keywords the torch engines take too (feature_list etc. are unused: CPU featurizer path)."""
-    return {k: v for k, v in kw.items() if k in ("symmetries", "symmetry_seed")}
+    return {k: v for k, v in kw.items() if k in ("symmetries", "symmetry_seed", "ownership")}
 
 
 def make_policy_inference(net, device, **kw):

@@ -64,6 +64,10 @@ def he_uniform_(net: nn.Module, generator=None) -> nn.Module:
             if w is not None:
                 bound = (3.0 / w.shape[0]) ** 0.5
                 w.uniform_(-bound, bound, generator=generator)
+        oh = getattr(net, "ohead_w", None)  # the ownership head, like vhead_w; drawn last, so that the other
+        if oh is not None:                  # tensors get the values they get in a net without it
+            bound = (6.0 / (oh.shape[1] * oh.shape[2] * oh.shape[3])) ** 0.5
+            oh.uniform_(-bound, bound, generator=generator)
     return net
 
 
@@ -206,10 +210,12 @@ class PolicyValueNet(nn.Module):
     """Dual-head network: one ConvStack, the policy head of PolicyNet (1x1 conv, softmax over S*S)
     and the value head of ValueNet (1x1 conv, Dense(dense, linear), Dense(1, tanh)) on its output.
     Reads the value net's planes (49 with ``color``).  ``residual``: a residual trunk (ConvStack), kept in
-    ``arch`` only when set; ``layers`` must then be odd."""
+    ``arch`` only when set; ``layers`` must then be odd.  ``ownership``: a third 1x1 head (``ohead_w``,
+    ``ohead_b``) with a tanh per board point, the owner of the point at the end of the game in the
+    mover's frame (+1 = the player to move); kept in ``arch`` only when set."""
 
     def __init__(self, input_dim: int = 49, board: int = 19, filters_per_layer: int = 192, layers: int = 12,
-                 dense: int = 256, residual: int = 0, **kwargs):
+                 dense: int = 256, residual: int = 0, ownership: int = 0, **kwargs):
         super().__init__()
         widths = [int(kwargs.get("filter_width_%d" % i, 5 if i == 1 else 3)) for i in range(1, layers + 1)]
         self.arch = dict(input_dim=input_dim, board=board, filters_per_layer=filters_per_layer, layers=layers,
@@ -219,6 +225,9 @@ class PolicyValueNet(nn.Module):
                 self.arch["filter_width_%d" % i] = w
         if residual:
             self.arch["residual"] = 1
+        if ownership:
+            self.arch["ownership"] = 1
+        self.ownership = bool(ownership)
         self.board = board
         self.trunk = ConvStack(input_dim, filters_per_layer, layers, widths, residual=bool(residual))
         self.head_w = nn.Parameter(torch.empty(1, filters_per_layer, 1, 1))
@@ -231,6 +240,10 @@ class PolicyValueNet(nn.Module):
         self.fc2_b = nn.Parameter(torch.zeros(1))
         for p in (self.head_w, self.vhead_w, self.fc1_w, self.fc2_w):
             keras_uniform_(p)
+        if ownership:  # after the others: they draw what they draw without the head
+            self.ohead_w = nn.Parameter(torch.empty(1, filters_per_layer, 1, 1))
+            self.ohead_b = nn.Parameter(torch.zeros(1))
+            keras_uniform_(self.ohead_w)
 
     @property
     def input_dim(self):
@@ -244,7 +257,7 @@ class PolicyValueNet(nn.Module):
             tot += 2.0 * s2 * cin * self.trunk.filters * k * k
             cin = self.trunk.filters
         d = self.arch["dense"]
-        return tot + 2 * (2.0 * s2 * cin) + 2.0 * s2 * d + 2.0 * d
+        return tot + (3 if self.ownership else 2) * (2.0 * s2 * cin) + 2.0 * s2 * d + 2.0 * d
 
     def heads_torch(self, h: torch.Tensor):
         """(policy logits (B, S*S), value (B,)) from the trunk output: PolicyNet.logits_torch's and
@@ -253,6 +266,13 @@ class PolicyValueNet(nn.Module):
         zv = F.conv2d(h, self.vhead_w.to(h.dtype), self.vhead_b.to(h.dtype)).flatten(1).float()
         zv = zv @ self.fc1_w + self.fc1_b
         return z, torch.tanh(zv @ self.fc2_w + self.fc2_b).squeeze(1)
+
+    def ownership_torch(self, h: torch.Tensor) -> torch.Tensor:
+        """(B, S*S) ownership in the mover's frame from the trunk output: tanh of the third 1x1 conv."""
+        if not self.ownership:
+            raise ValueError("this PolicyValueNet has no ownership head (ownership=1)")
+        o = F.conv2d(h, self.ohead_w.to(h.dtype), self.ohead_b.to(h.dtype)).flatten(1)
+        return torch.tanh(o if o.dtype == torch.float64 else o.float())  # fp32 from a bf16 trunk; an fp64 oracle stays fp64
 
     def logits_value_torch(self, x: torch.Tensor):
         return self.heads_torch(self.trunk.forward_torch(x))

@@ -260,11 +260,45 @@ class CNNPolicyValue(_NetWrapper):
         self._check_states(states)
         return [float(v) for v in self.forward(self.preprocessor.states_to_uint8(states))[1]]
 
+    # ------------------------------------------------------------ ownership
+    @property
+    def has_ownership(self) -> bool:
+        return bool(getattr(self.model, "ownership", False))
+
+    def batch_eval_ownership(self, states) -> List[np.ndarray]:
+        """Per state an (S, S) float array of the ownership head, + = Black (the head's mover's-frame
+        output times ``current_player``), indexed [x][y] like the board.  Runs on a second engine built
+        on first use with ``ownership=True``; the search engine stays as it is."""
+        if not self.has_ownership:
+            raise ValueError("this net has no ownership head")
+        if not states:
+            return []
+        size = self._check_states(states)
+        if getattr(self, "_own_engine", None) is None:
+            self._own_engine = make_policy_value_inference(self.model, self.device, ownership=True,
+                                                           **self._engine_kw())
+        eng = self._own_engine
+        planes = self.preprocessor.states_to_uint8(states)
+        eng.evaluate(np.asarray(planes, dtype=np.uint8))
+        own = eng.ownership_view().float().cpu().numpy()
+        return [own[i].reshape(size, size) * float(st.current_player) for i, st in enumerate(states)]
+
+    def eval_ownership(self, state) -> np.ndarray:
+        return self.batch_eval_ownership([state])[0]
+
+    def refresh(self) -> None:
+        super().refresh()
+        if getattr(self, "_own_engine", None) is not None:
+            self._own_engine.sync_weights()
+
     # ---------------------------------------------------------------- split
     def split(self):
         """(CNNPolicy, CNNValue) carrying copies of the trunk and the respective head, both on this
         net's feature list: the pair computes what the two heads compute, each on its own trunk."""
         a, fl = self.model.arch, list(self.preprocessor.feature_list)
+        if getattr(self.model, "ownership", False):
+            raise ValueError("split(): a net with the ownership head has no (policy, value) form: the pair "
+                             "cannot carry the third head")
         if self.model.trunk.residual:
             raise ValueError("split(): a residual trunk has no single-head form (the Keras Sequential of "
                              "CNNPolicy / CNNValue cannot express a skip connection)")

@@ -601,6 +601,32 @@ def policy_value_head(y, wp, bp, wv, bv, probs, zv, S: int, legal=None):
     return probs, zv
 
 
+def value_own_head(y, wv, bv, wo, bo, zv, S: int, own=None, olog=None, target=None, sym=None, valid=None,
+                   weight=None, oloss=None, oagree=None, dlo=None, grad_scale: float = 1.0):
+    """The value and ownership heads of the dual net from one read of the trunk output: ``zv`` (B, S*S)
+    is ``head_logits(y, wv, bv)``, ``olog = y . wo + bo`` and ``own = tanh(olog)`` (both optional).
+    With ``target`` (int8 (B, S*S) in the stored frame; ``sym`` moves it with the board as
+    ``policy_head_soft`` moves its distribution) it also writes per board ``oloss`` = mean squared
+    error, ``oagree`` = points with target != 0 whose sign ``own`` matches, and ``dlo`` (B, S*S) =
+    grad_scale * valid[b] * weight[b] * (2 / S*S) * (own - t) * (1 - own**2)."""
+    _ops().value_own_head(y, wv, bv, wo, bo, zv, own, olog, target, sym, valid, weight, oloss, oagree, dlo, S,
+                          grad_scale)
+    return zv
+
+
+def head_backward_add2(y, w1, g1, w2, g2, dz, dhead1, dhead2, S: int, dz8=None):
+    """``head_backward_add`` for two heads in one pass over ``y`` and ``dz``: where y > 0,
+    dz = bf16(fma(g2, w2, fma(g1, w1, dz))); ``dhead1`` / ``dhead2`` as ``head_backward_add``'s
+    ``dhead``.  ``dz8`` is refused."""
+    _ops().head_backward_add2(y, w1, g1, w2, g2, dz, dhead1, dhead2, S, dz8)
+
+
+def policy_value_own_head(y, wp, bp, wv, bv, wo, bo, probs, zv, own, S: int, legal=None):
+    """``policy_value_head`` plus ``own`` (B, S*S) fp32 = tanh(y . wo + bo), the ownership head."""
+    _ops().policy_value_own_head(y, wp, bp, wv, bv, wo, bo, probs, zv, own, S, legal)
+    return probs, zv, own
+
+
 def value_out(h, w2, b2, v, target=None, weight=None, loss=None, correct=None, dh=None, dout=None,
               grad_scale: float = 1.0):
     """v = tanh(h w2 + b2); with target: MSE loss, sign agreement, dh and per-board [dw2 | db2]."""

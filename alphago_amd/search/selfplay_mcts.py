@@ -179,10 +179,17 @@ def play_selfplay(policy, value, n_games: int, concurrent: int, cfg: MCTSConfig,
 class SelfPlayWriter(object):
     """Finished games -> SGF files and the (states, pi, outcomes, moves, game) HDF5 dataset.
     ``positions_per_game`` > 0 keeps that many positions per game, drawn uniformly (the value-net
-    recipe of one position per game avoids correlated samples); 0 keeps every searched position."""
+    recipe of one position per game avoids correlated samples); 0 keeps every searched position.
+
+    ``ownership=True`` adds two datasets for the dual net's ownership head.  ``ownership`` (N, S*S) int8:
+    the final map of the row's game (``GameState.get_ownership``, the map ``get_winner`` scores by)
+    times the row's player to move, so +1 means "mine".  ``ownership_valid`` (N,) uint8: 1 for rows of
+    games that ended by two passes; a resigned or capped game is not settled, its rows are all zero and
+    marked 0.  Off (the default): the file holds exactly the five datasets above."""
 
     def __init__(self, h5_path: str, sgf_dir: Optional[str], features: Sequence[str] = VALUE_FEATURES,
-                 size: int = 19, positions_per_game: int = 0, seed: int = 0, threads: int = 16):
+                 size: int = 19, positions_per_game: int = 0, seed: int = 0, threads: int = 16,
+                 ownership: bool = False):
         self.pre = Preprocess(list(features))
         self.size = size
         self.sgf_dir = sgf_dir
@@ -200,6 +207,10 @@ class SelfPlayWriter(object):
         self.z: List[np.ndarray] = []
         self.mv: List[np.ndarray] = []
         self.gid: List[np.ndarray] = []
+        self.ownership = bool(ownership)
+        self.own: List[np.ndarray] = []
+        self.own_valid: List[np.ndarray] = []
+        self.own_positions = 0  # rows with a valid ownership map
         self.games = self.positions = 0
         self.winners = {go.BLACK: 0, go.WHITE: 0, 0: 0}
         self.lengths: List[int] = []
@@ -210,10 +221,12 @@ class SelfPlayWriter(object):
 
     def add(self, r: GameRecord) -> None:
         n = len(r.pi)
+        scored = False
         if r.resigned:
             self.endings["resignation"] += 1
         elif len(r.moves) >= 2 and r.moves[-1] == -1 and r.moves[-2] == -1:
             self.endings["two_passes"] += 1
+            scored = True
         else:
             self.endings["move_cap"] += 1
         keep = np.arange(n)
@@ -239,6 +252,14 @@ class SelfPlayWriter(object):
         self.z.append(np.array([r.winner * r.players[k] for k in keep], np.int8))
         self.mv.append(np.array([r.moves[k] for k in keep], np.int16))
         self.gid.append(np.full(len(keep), r.game_id, np.int32))
+        if self.ownership:
+            rows = np.zeros((len(keep), r.size * r.size), np.int8)
+            if scored:  # the position after the replayed moves is the game's last
+                final = np.asarray(st.get_ownership(), np.int8).reshape(-1)
+                rows = final[None, :] * np.array([r.players[k] for k in keep], np.int8)[:, None]
+                self.own_positions += len(keep)
+            self.own.append(rows.astype(np.int8))
+            self.own_valid.append(np.full(len(keep), 1 if scored else 0, np.uint8))
         self.games += 1
         self.positions += len(keep)
         self.winners[r.winner] = self.winners.get(r.winner, 0) + 1
@@ -255,13 +276,31 @@ class SelfPlayWriter(object):
         self.w.create_dataset("outcomes", data=np.concatenate(self.z) if self.z else np.zeros(0, np.int8))
         self.w.create_dataset("moves", data=np.concatenate(self.mv) if self.mv else np.zeros(0, np.int16))
         self.w.create_dataset("game", data=np.concatenate(self.gid) if self.gid else np.zeros(0, np.int32))
+        if self.ownership:
+            own = self.w.stream_dataset("ownership", (self.size * self.size,), np.int8, chunk_rows=STATE_CHUNK_ROWS,
+                                        compression="lzf")
+            for rows in self.own:
+                own.append(rows)
+            own.finish()
+            self.w.create_dataset("ownership_valid",
+                                  data=np.concatenate(self.own_valid) if self.own_valid else np.zeros(0, np.uint8))
         self.w.close()
         os.replace(self.tmp, self.path)
         return self.positions
 
 
 def merge_selfplay_files(paths: List[str], outfile: str, block_rows: int = 4096) -> int:
-    """Concatenate per-rank self-play files; game ids are offset so they stay unique."""
+    """Concatenate per-rank self-play files; game ids are offset so they stay unique.  The ownership
+    datasets are carried when every input has them; inputs of which only some do are refused."""
+    has_own = []
+    for pth in paths:
+        with H5File(pth) as f:
+            has_own.append("ownership" in f and "ownership_valid" in f)
+    if any(has_own) and not all(has_own):
+        raise ValueError("only some of the files hold ownership datasets (%s do not): merge files written with "
+                         "the same --ownership setting"
+                         % ", ".join(p for p, h in zip(paths, has_own) if not h))
+    carry_own = bool(has_own) and all(has_own)
     tmp = outfile + ".tmp"
     total = 0
     with H5Writer(tmp) as w:
@@ -272,6 +311,9 @@ def merge_selfplay_files(paths: List[str], outfile: str, block_rows: int = 4096)
                     w.attrs[k] = first.attrs[k]
         st = w.stream_dataset("states", shape, np.uint8, chunk_rows=STATE_CHUNK_ROWS, compression="lzf")
         cols: Dict[str, List[np.ndarray]] = {"pi": [], "outcomes": [], "moves": [], "game": []}
+        own_rows: List[np.ndarray] = []
+        if carry_own:
+            cols["ownership_valid"] = []
         goff = 0
         for pth in paths:
             with H5File(pth) as f:
@@ -282,13 +324,23 @@ def merge_selfplay_files(paths: List[str], outfile: str, block_rows: int = 4096)
                     st.append(ds.read_rows(r0, r0 + block_rows))
                 for k in cols:
                     cols[k].append(np.asarray(f[k].read()))
+                if carry_own:
+                    own_rows.append(np.asarray(f["ownership"].read(), np.int8))
                 g = cols["game"][-1]
                 cols["game"][-1] = g + goff
                 goff += int(g.max()) + 1 if len(g) else 0
                 total += ds.shape[0]
         st.finish()
         for k, v in cols.items():
-            w.create_dataset(k, data=np.concatenate(v))
+            if k != "ownership_valid":
+                w.create_dataset(k, data=np.concatenate(v))
+        if carry_own:
+            own = w.stream_dataset("ownership", own_rows[0].shape[1:], np.int8, chunk_rows=STATE_CHUNK_ROWS,
+                                   compression="lzf")
+            for rows in own_rows:
+                own.append(rows)
+            own.finish()
+            w.create_dataset("ownership_valid", data=np.concatenate(cols["ownership_valid"]))
     os.replace(tmp, outfile)
     return total
 
@@ -413,6 +465,9 @@ def selfplay_cli(argv=None):
     p.add_argument("--max-moves", type=int, default=0)
     p.add_argument("--komi", type=float, default=7.5)
     p.add_argument("--positions-per-game", type=int, default=0)
+    p.add_argument("--ownership", action="store_true",
+                   help="also write ownership / ownership_valid: the final territory map of each scored game in the "
+                        "mover's frame, the target of the dual net's ownership head (init-model pv --ownership)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--no-sgf", action="store_true")
     p.add_argument("--progress-every", type=int, default=0, help="print a progress line every N search rounds")
@@ -438,7 +493,7 @@ def selfplay_cli(argv=None):
     sgf = None if a.no_sgf else os.path.join(a.out_directory, "sgf", "rank%d" % env.rank)
     wkw = {"features": list(policy.preprocessor.feature_list)} if dual else {}  # the dual net's own planes
     writer = SelfPlayWriter(h5, sgf, size=S, positions_per_game=a.positions_per_game,
-                            seed=a.seed * 1009 + env.rank, **wkw)
+                            seed=a.seed * 1009 + env.rank, ownership=a.ownership, **wkw)
     stats: List[RoundStats] = []
     t0 = time.perf_counter()
     play_selfplay(policy, value, a.games, a.concurrent, cfg, size=S, komi=a.komi, max_moves=a.max_moves or None,
@@ -452,6 +507,8 @@ def selfplay_cli(argv=None):
                                                "draw": writer.winners.get(0, 0)},
              "mean_length": round(float(np.mean(writer.lengths)), 1) if writer.lengths else 0.0,
              "endings": dict(writer.endings)}
+    if a.ownership:
+        local["ownership_positions"] = writer.own_positions
     every = agdist.all_gather_object(local)
     if env.world_size > 1:
         agdist.barrier()
@@ -466,6 +523,8 @@ def selfplay_cli(argv=None):
                "leaf_evals": sum(e["leaf_evals"] for e in every), "seconds": max(e["seconds"] for e in every),
                "ranks": every, "phases_rank0": phase_table(stats),
                "endings": {k: sum(e["endings"][k] for e in every) for k in every[0]["endings"]}}
+    if a.ownership:  # positions whose game was scored: the rows with a valid ownership map
+        summary["ownership_positions"] = sum(e["ownership_positions"] for e in every)
     summary["leaf_evals_per_s"] = round(summary["leaf_evals"] / max(summary["seconds"], 1e-9), 1)
     if env.is_main:
         with open(os.path.join(a.out_directory, "selfplay_summary.json"), "w") as f:

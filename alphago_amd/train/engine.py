@@ -1199,10 +1199,29 @@ _PV_REFUSED = ("the dual (policy + value) trainer trains the plain cross-entropy
                "policy_loss at 'ce' and ent_coef, kl_coef and collect_* off")
 
 
-def _pv_targets(targets):
+def _pv_targets(targets, ownership: bool = False):
+    """(pi_or_moves, z, own) of a dual-trainer target: a pair (own = None) or, for a net with the
+    ownership head, a triple whose last entry is (own_t (B, S*S) int8 in the mover's frame, own_valid
+    (B,))."""
+    if isinstance(targets, (tuple, list)) and len(targets) == 3:
+        if not ownership:
+            raise ValueError("a target triple (pi, z, (own_t, own_valid)) needs a net with the ownership head")
+        own = targets[2]
+        if not isinstance(own, (tuple, list)) or len(own) != 2:
+            raise ValueError("the ownership target is a pair (own_t (B, S*S), own_valid (B,))")
+        return targets[0], targets[1], (own[0], own[1])
     if not isinstance(targets, (tuple, list)) or len(targets) != 2:
-        raise ValueError("the dual trainer's targets are a pair (moves or pi, outcomes z)")
-    return targets[0], targets[1]
+        raise ValueError("the dual trainer's targets are a pair (moves or pi, outcomes z)" +
+                         (" or a triple with (own_t, own_valid)" if ownership else ""))
+    return targets[0], targets[1], None
+
+
+def own_agreement_share(own, own_t):
+    """Per board, the share of the points with a non-zero target whose sign ``own`` matches (0 for a
+    board without such points): the trainers' sixth metric before the sum over valid boards."""
+    t = own_t.to(own.dtype)
+    nz = t != 0
+    return ((torch.sign(own) == t) & nz).to(own.dtype).sum(1) / nz.sum(1).clamp_min(1).to(own.dtype)
 
 
 class HipPolicyValueTrainer(HipPolicyTrainer):
@@ -1221,19 +1240,39 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
 
     ``step`` returns (policy loss sum, top-1 sum, value squared-error sum, sign-agreement sum).
 
+    A net with the ownership head (``PolicyValueNet(ownership=1)``) takes targets
+    ``(pi_or_moves, z, (own_t, own_valid))``: ``own_t`` (B, S*S) int8 is the final territory map in the
+    mover's frame of the stored planes (the head kernel moves it with ``sym``), ``own_valid`` (B,) marks
+    the boards whose game was scored.  The loss gains ``own_coef`` * (1 / B_global) sum_b valid_b w_b
+    MSE_b(own, own_t); ``own_coef`` defaults to 1.0, a conventional starting point that is not tuned.
+    In the step ``value_own_head`` takes ``head_logits``' place (one read of Y[L-1] for both heads) and
+    ``head_backward_add2`` ``head_backward_add``'s (one read-modify-write of dZ[L-1] for both), with one
+    more ``head_grad_sums`` call for ``ohead_w`` / ``ohead_b``, which follow ``fc2_b`` in the flat
+    parameters.  ``step`` and ``evaluate`` then return six sums: the four above, the sum over valid
+    boards of the per-board mean squared error, and the sum over valid boards of the share of decided
+    points (target != 0) whose sign the head matches.  A pair ``(pi, z)`` is still accepted: it runs
+    the step of a net without the head, leaves ``ohead_*`` without gradient and reports 0 for both.
+    A net without the head launches exactly the kernels above and returns four sums.
+
     fp8: the head writes the bf16 dZ only (``_top_e5m2_fusable`` is False: a sum of two heads cannot
     be accumulated in e5m2), so an fp8 backward works through the unfused ``quantize_bf8`` pass over
     the summed dZ[L-1], the policy trainer's path.  Graph mode and the regularised head options
     (``ent_coef``, ``kl_coef``, ``collect_*``, ``policy_loss='bce'``) are refused."""
 
-    def __init__(self, net, batch: int, lr: float = 0.003, decay: float = 0.0, value_coef: float = 1.0, **kw):
+    def __init__(self, net, batch: int, lr: float = 0.003, decay: float = 0.0, value_coef: float = 1.0,
+                 own_coef: float = 1.0, **kw):
         self.value_coef = float(value_coef)
+        self.own_coef = float(own_coef)
+        self.has_own = bool(getattr(net, "ownership", False))
         super().__init__(net, batch, lr, decay, **kw)
 
     def _head_named_params(self):
         n = self.net
-        return [("head_w", n.head_w), ("head_b", n.head_b), ("vhead_w", n.vhead_w), ("vhead_b", n.vhead_b),
-                ("fc1_w", n.fc1_w), ("fc1_b", n.fc1_b), ("fc2_w", n.fc2_w), ("fc2_b", n.fc2_b)]
+        named = [("head_w", n.head_w), ("head_b", n.head_b), ("vhead_w", n.vhead_w), ("vhead_b", n.vhead_b),
+                 ("fc1_w", n.fc1_w), ("fc1_b", n.fc1_b), ("fc2_w", n.fc2_w), ("fc2_b", n.fc2_b)]
+        if self.has_own:  # appended: the existing segments keep their offsets
+            named += [("ohead_w", n.ohead_w), ("ohead_b", n.ohead_b)]
+        return named
 
     def _init_head(self):
         super()._init_head()
@@ -1249,6 +1288,14 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
         self.tval = torch.zeros(B, device=dev)
         self.vloss = torch.zeros(B, device=dev)
         self.vcorrect = torch.zeros(B, device=dev)
+        if self.has_own:
+            self.own = torch.zeros(B, NP, device=dev)
+            self.dlo = torch.zeros(B, NP, device=dev)
+            self.odhead = torch.zeros(B, self.F + 1, device=dev)
+            self.oloss = torch.zeros(B, device=dev)
+            self.oagree = torch.zeros(B, device=dev)
+            self.own_t = torch.zeros(B, NP, dtype=torch.int8, device=dev)
+            self.own_valid = torch.zeros(B, device=dev)
 
     def enable_graphs(self, on: bool = True) -> None:
         if on:
@@ -1266,10 +1313,34 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
         self._check_plain()
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError(_PV_NO_GRAPH)
-        pi, z = _pv_targets(targets)
+        pi, z, own = _pv_targets(targets, self.has_own)
         if z.numel() != self.batch:
             raise ValueError("outcomes must hold %d entries, got %d" % (self.batch, z.numel()))
+        if own is not None:
+            self._check_own(own)
         super()._forward_for_head(planes, pi, sym)
+
+    def _check_own(self, own) -> None:
+        NP = self.S * self.S
+        if tuple(own[0].shape) != (self.batch, NP) or own[1].numel() != self.batch:
+            raise ValueError("the ownership target is (own_t (%d, %d), own_valid (%d,)), got %s and %s"
+                             % (self.batch, NP, self.batch, tuple(own[0].shape), tuple(own[1].shape)))
+
+    def _own_forward(self, own, sym, weight, gscale):
+        """value_own_head in head_logits' place: z, own, the per-board ownership loss / agreement and dlo."""
+        v = self.fp.views
+        self.own_t.copy_(own[0])
+        self.own_valid.copy_(own[1])
+        ops.value_own_head(self.Y[-1], v["vhead_w"].view(-1), v["vhead_b"], v["ohead_w"].view(-1), v["ohead_b"],
+                           self.z, self.S, own=self.own, target=self.own_t, sym=sym, valid=self.own_valid,
+                           weight=weight, oloss=self.oloss, oagree=self.oagree, dlo=self.dlo, grad_scale=gscale)
+        ops.dense_f32(self.z, v["fc1_w"], self.h, bias=v["fc1_b"])  # h = z W1 + b1
+
+    def _own_metric_vectors(self):
+        """(valid_b * MSE_b, valid_b * share_b): the kernel's per-board loss and agreement count times the
+        caller's validity column, the count over the board's decided points."""
+        nz = (self.own_t != 0).sum(1).clamp_min(1).float()
+        return self.oloss * self.own_valid, self.oagree * self.own_valid / nz
 
     def _value_forward(self):
         v = self.fp.views
@@ -1277,23 +1348,31 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
         ops.dense_f32(self.z, v["fc1_w"], self.h, bias=v["fc1_b"])  # h = z W1 + b1
 
     def _head_train(self, targets, gscale, weight, sym=None):
-        pi, z = _pv_targets(targets)
+        pi, z, own = _pv_targets(targets, self.has_own)
         v, gv = self.fp.views, self.fp.grad_views
         # 1. the policy head, unchanged: dZ[L-1] and its [dW_head | db_head] partials
         if is_soft_target(pi):
             self._head_soft(pi, gscale, weight, sym)
         else:
             self._head_hard(gscale, weight)
-        # 2. the value head's forward, output layer and dense backward (HipValueTrainer._head_train)
-        self._value_forward()
+        # 2. the value head's forward, output layer and dense backward (HipValueTrainer._head_train); with
+        #    an ownership target the same read of Y[L-1] gives the ownership head's forward and dlo
+        if own is not None:
+            self._own_forward(own, sym, weight, gscale * self.own_coef)
+        else:
+            self._value_forward()
         self.tval.copy_(z)
         ops.value_out(self.h, v["fc2_w"].view(-1), v["fc2_b"], self.val, target=self.tval, weight=weight,
                       loss=self.vloss, correct=self.vcorrect, dh=self.dh, dout=self.dout,
                       grad_scale=gscale * self.value_coef)
         ops.dense_f32(self.z, self.dh, gv["fc1_w"], trans_a=True)  # dW1 = z^T dh
         ops.dense_f32(self.dh, v["fc1_w"], self.dzl, trans_b=True)  # dz = dh W1^T
-        # 3. the value head's dY added into the policy head's dZ[L-1]
-        ops.head_backward_add(self.Y[-1], v["vhead_w"].view(-1), self.dzl, self.DZ[-1], self.vdhead, self.S)
+        # 3. the value head's dY (and the ownership head's, in the same pass) added into the policy head's dZ[L-1]
+        if own is not None:
+            ops.head_backward_add2(self.Y[-1], v["vhead_w"].view(-1), self.dzl, v["ohead_w"].view(-1), self.dlo,
+                                   self.DZ[-1], self.vdhead, self.odhead, self.S)
+        else:
+            ops.head_backward_add(self.Y[-1], v["vhead_w"].view(-1), self.dzl, self.DZ[-1], self.vdhead, self.S)
         # 4. column sums of every per-board partial, and the four metric sums (fresh vectors per step)
         self._metric_sums = torch.empty(2, device=self.device)
         self._vmetric_sums = torch.empty(2, device=self.device)
@@ -1304,6 +1383,15 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
         ops.head_grad_sums(self.dout, self.vloss, self.vcorrect, self.fp.grad[o2:o2 + n2 + 1], self._vmetric_sums)
         vo, vn = self.fp.segments["vhead_w"]
         ops.head_grad_sums(self.vdhead, self.vloss, self.vcorrect, self.fp.grad[vo:vo + vn + 1], self._vmetric_sums)
+        if self.has_own:
+            oo, on = self.fp.segments["ohead_w"]
+            if own is not None:
+                self._ometric_sums = torch.empty(2, device=self.device)
+                ol, oa = self._own_metric_vectors()
+                ops.head_grad_sums(self.odhead, ol, oa, self.fp.grad[oo:oo + on + 1], self._ometric_sums)
+            else:  # a pair: no ownership term
+                self._ometric_sums = torch.zeros(2, device=self.device)
+                self.fp.grad[oo:oo + on + 1].zero_()
 
     def step(self, planes, targets, sym: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None,
              rows: Optional[torch.Tensor] = None):
@@ -1314,7 +1402,10 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
         return self._step_metrics()
 
     def _step_metrics(self):
-        return self._metric_sums[0], self._metric_sums[1], self._vmetric_sums[0], self._vmetric_sums[1]
+        m = (self._metric_sums[0], self._metric_sums[1], self._vmetric_sums[0], self._vmetric_sums[1])
+        if self.has_own:
+            m += (self._ometric_sums[0], self._ometric_sums[1])
+        return m
 
     @torch.no_grad()
     def predict(self, planes: torch.Tensor) -> torch.Tensor:
@@ -1327,15 +1418,27 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
 
     @torch.no_grad()
     def evaluate(self, planes: torch.Tensor, targets):
-        """The four metric sums without an update (validation)."""
+        """The four metric sums (six for a net with the ownership head) without an update (validation)."""
         self._check_plain()
-        pi, z = _pv_targets(targets)
+        pi, z, own = _pv_targets(targets, self.has_own)
+        if own is not None:
+            self._check_own(own)
         pl, pc = super().evaluate(planes, pi)  # leaves the trunk output in Y[-1]
-        self._value_forward()
+        if own is not None:
+            self._own_forward(own, None, None, 0.0)
+        else:
+            self._value_forward()
         v = self.fp.views
         ops.value_out(self.h, v["fc2_w"].view(-1), v["fc2_b"], self.val)
         zt = z.float()
-        return pl, pc, ((self.val - zt) ** 2).sum(), (torch.sign(self.val) == torch.sign(zt)).float().sum()
+        m = (pl, pc, ((self.val - zt) ** 2).sum(), (torch.sign(self.val) == torch.sign(zt)).float().sum())
+        if self.has_own:
+            if own is not None:
+                ol, oa = self._own_metric_vectors()
+                m += (ol.sum(), oa.sum())
+            else:
+                m += (torch.zeros((), device=self.device), torch.zeros((), device=self.device))
+        return m
 
     def policy_stats(self, planes, ref_probs=None):
         raise ValueError(_PV_REFUSED)
@@ -1514,7 +1617,9 @@ class TorchValueTrainer(_TorchTrainerBase):
 
 class TorchPolicyValueTrainer(_TorchTrainerBase):
     """Autograd twin of HipPolicyValueTrainer: mean over the global batch of the policy CE (hard or soft
-    targets, TorchPolicyTrainer's expressions) + ``value_coef`` * (v - z)^2 on one trunk output."""
+    targets, TorchPolicyTrainer's expressions) + ``value_coef`` * (v - z)^2 on one trunk output; for a net
+    with the ownership head and a target triple also ``own_coef`` * valid_b * mean_p (own - own_t)^2 (the
+    target moved with the board by ``sym``).  ``own_coef`` defaults to 1.0, untuned."""
 
     policy_loss = "ce"
     ent_coef = 0.0
@@ -1524,24 +1629,32 @@ class TorchPolicyValueTrainer(_TorchTrainerBase):
 
     def __init__(self, net, batch: int, lr: float = 0.003, decay: float = 0.0, device=None, dtype=torch.float32,
                  iterations: int = 0, optimizer: str = "sgd", momentum: float = 0.0, nesterov: bool = False,
-                 value_coef: float = 1.0):
+                 value_coef: float = 1.0, own_coef: float = 1.0):
         self.value_coef = float(value_coef)
+        self.own_coef = float(own_coef)
+        self.has_own = bool(getattr(net, "ownership", False))
         named = _trunk_named(net.trunk) + [(n, getattr(net, n)) for n in (
-            "head_w", "head_b", "vhead_w", "vhead_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
+            "head_w", "head_b", "vhead_w", "vhead_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b") +
+            (("ohead_w", "ohead_b") if self.has_own else ())]
         self._setup(net, batch, lr, decay, device, dtype, iterations, named, optimizer, momentum, nesterov)
 
     def _loss(self, planes, targets, sym, weight):
         if self.policy_loss != "ce" or self.ent_coef or self.kl_coef or self.collect_stats or self.collect_probs:
             raise ValueError(_PV_REFUSED)
-        pi, z = _pv_targets(targets)
+        pi, z, own = _pv_targets(targets, self.has_own)
         soft = is_soft_target(pi)
+        if own is not None:
+            own_t, own_valid = own[0].to(self.dtype), own[1].to(self.dtype)
+            if sym is not None:
+                own_t = apply_symmetry_dist(own_t, sym, self.table)
         if sym is not None:
             if soft:
                 planes, _ = apply_symmetry(planes, None, sym, self.table)
                 pi = apply_symmetry_dist(pi, sym, self.table)
             else:
                 planes, pi = apply_symmetry(planes, pi, sym, self.table)
-        logits, v = self.net.logits_value_torch(planes.to(self.dtype))
+        h = self.net.trunk.forward_torch(planes.to(self.dtype))
+        logits, v = self.net.heads_torch(h)
         norm = planes.shape[0] * self.env.world_size
         if soft:
             per, correct, has = soft_target_loss(logits, pi)
@@ -1559,16 +1672,29 @@ class TorchPolicyValueTrainer(_TorchTrainerBase):
         err = (v - zt) ** 2
         vobj = (err if weight is None else err * weight).sum() / norm
         self._vlast = (err.detach(), (torch.sign(v) == torch.sign(zt)).float().detach())
-        return pobj + self.value_coef * vobj, per, correct
+        obj = pobj + self.value_coef * vobj
+        if own is not None:
+            o = self.net.ownership_torch(h)
+            oerr = ((o - own_t) ** 2).mean(1)
+            ow = own_valid if weight is None else own_valid * weight
+            obj = obj + self.own_coef * (oerr * ow).sum() / norm
+            self._olast = ((oerr * own_valid).detach(), (own_agreement_share(o.detach(), own_t) * own_valid))
+        elif self.has_own:
+            self._olast = (torch.zeros_like(err.detach()), torch.zeros_like(err.detach()))
+        return obj, per, correct
+
+    def _metrics(self, pl, pc):
+        m = (pl, pc, self._vlast[0].sum(), self._vlast[1].sum())
+        if self.has_own:
+            m += (self._olast[0].sum(), self._olast[1].sum())
+        return m
 
     def step(self, planes, targets, sym=None, weight=None, rows=None):
-        pl, pc = super().step(planes, targets, sym, weight, rows)
-        return pl, pc, self._vlast[0].sum(), self._vlast[1].sum()
+        return self._metrics(*super().step(planes, targets, sym, weight, rows))
 
     @torch.no_grad()
     def evaluate(self, planes, targets):
-        pl, pc = super().evaluate(planes, targets)
-        return pl, pc, self._vlast[0].sum(), self._vlast[1].sum()
+        return self._metrics(*super().evaluate(planes, targets))
 
     @torch.no_grad()
     def predict(self, planes) -> torch.Tensor:
@@ -1598,15 +1724,16 @@ def make_policy_trainer(net: PolicyNet, batch: int, lr: float, decay: float = 0.
 def make_policy_value_trainer(net, batch: int, lr: float, decay: float = 0.0, backend: str = "auto", device=None,
                               **kw):
     """The dual net's trainer: HipPolicyValueTrainer on a GPU, TorchPolicyValueTrainer otherwise
-    (``value_coef`` goes to both)."""
+    (``value_coef`` and ``own_coef`` go to both)."""
     dev = torch.device(device) if device is not None else agdist.env().device
     if backend == "auto":
         backend = "hip" if dev.type == "cuda" else "torch"
     if backend == "hip":
         return HipPolicyValueTrainer(net, batch, lr, decay, device=dev, **kw)
     tkw = _torch_kw(kw)
-    if "value_coef" in kw:
-        tkw["value_coef"] = kw["value_coef"]
+    for k in ("value_coef", "own_coef"):
+        if k in kw:
+            tkw[k] = kw[k]
     return TorchPolicyValueTrainer(net, batch, lr, decay, device=dev, **tkw)
 
 

@@ -9,10 +9,16 @@ the soft-target head, rows at their full S*S + 1 width) or against the played mo
 game outcome for the player to move.  A position whose visit mass is all on the pass has no policy
 loss and still trains the value head.
 
+A model with the ownership head (``init-model pv --ownership``) also reads ``ownership`` and
+``ownership_valid`` (``selfplay-mcts --ownership``) and adds ``--ownership-coef`` times the mean squared
+error of the ownership head against the final territory map, over the positions of scored games.
+
 D4 augmentation goes through the input pack's ``sym``: the soft head moves the distribution with the
-board, and the outcome is invariant.  The output directory holds ``metadata.json`` (per-epoch
-``loss``, ``acc``, ``value_loss``, ``value_acc`` and their ``val_`` forms), ``shuffle.npz`` and
-``weights.{epoch:05d}.hdf5`` per epoch, as ``train-sl`` writes them.
+board, the ownership head moves its target the same way, and the outcome is invariant.  The output
+directory holds ``metadata.json`` (per-epoch ``loss``, ``acc``, ``value_loss``, ``value_acc`` and their
+``val_`` forms; with the ownership head also ``own_loss`` and ``own_acc``, means over the positions with
+a valid ownership row), ``shuffle.npz`` and ``weights.{epoch:05d}.hdf5`` per epoch, as ``train-sl``
+writes them.
 
 Out of scope here: checkpoint / exact resume (``--weights`` restarts from a weights file with a fresh
 schedule), the watchdog, streaming datasets (the file is held in host memory) and graph mode.
@@ -36,6 +42,7 @@ from .engine import make_policy_value_trainer
 from .sl import MetadataWriter
 
 _KEYS = ("loss", "acc", "value_loss", "value_acc")
+_OWN_KEYS = ("own_loss", "own_acc")
 
 
 def _parser():
@@ -52,6 +59,9 @@ def _parser():
     p.add_argument("--learning-rate", "-r", type=float, default=.03)
     p.add_argument("--decay", "-d", type=float, default=.0001)
     p.add_argument("--value-coef", type=float, default=1.0, help="weight of the value MSE next to the policy CE")
+    p.add_argument("--ownership-coef", type=float, default=1.0,
+                   help="weight of the ownership MSE (models with the ownership head); 1.0 is a conventional "
+                        "starting point, not a tuned value")
     p.add_argument("--targets", default="pi", choices=["pi", "played"],
                    help="pi: the search's visit distribution (soft-target head, default); played: the move played")
     p.add_argument("--no-symmetries", action="store_true", help="disable random D4 augmentation")
@@ -85,12 +95,23 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
         pi = np.asarray(f["pi"].read(), dtype=np.float32)
         z = np.asarray(f["outcomes"].read()).astype(np.float32)
         moves = np.asarray(f["moves"].read()).astype(np.int32) if args.targets == "played" else None
+        own = own_valid = None
+        if getattr(net, "ownership", False):
+            if "ownership" not in f or "ownership_valid" not in f:
+                raise ValueError("%s has no 'ownership' / 'ownership_valid' datasets, which a model with the "
+                                 "ownership head trains on: write the records with selfplay-mcts --ownership"
+                                 % args.train_data)
+            own = np.asarray(f["ownership"].read()).astype(np.int8)
+            own_valid = np.asarray(f["ownership_valid"].read()).astype(np.float32)
     n_total = states.shape[0]
     if states.shape[1] != model.preprocessor.output_dim or states.shape[2] != S:
         raise ValueError("dataset rows are %s, the model expects (%d, %d, %d)"
                          % (states.shape[1:], model.preprocessor.output_dim, S, S))
     if pi.shape != (n_total, S * S + 1) or z.shape != (n_total,):
         raise ValueError("pi / outcomes do not match states: %s, %s for %d positions" % (pi.shape, z.shape, n_total))
+    if own is not None and (own.shape != (n_total, S * S) or own_valid.shape != (n_total,)):
+        raise ValueError("ownership / ownership_valid do not match states: %s, %s for %d positions"
+                         % (own.shape, own_valid.shape, n_total))
     perm = np.random.default_rng(args.seed).permutation(n_total)
     n_train = int(args.train_val_test[0] * n_total)
     n_val = int(args.train_val_test[1] * n_total)
@@ -106,9 +127,13 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
     meta = MetadataWriter(os.path.join(args.out_directory, "metadata.json"))
     meta.metadata.update(training_data=args.train_data, model_file=args.model, targets=args.targets,
                          value_coef=args.value_coef)
+    if own is not None:
+        meta.metadata.update(ownership_coef=args.ownership_coef)
 
     B = args.minibatch
     kw = {"value_coef": args.value_coef}
+    if own is not None:
+        kw["own_coef"] = args.ownership_coef
     if args.precision != "bf16":
         kw["precision"] = args.precision
     trainer = make_policy_value_trainer(net, B, args.learning_rate, args.decay, backend=args.backend, device=dev, **kw)
@@ -127,13 +152,18 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
             tgt = _pad(torch.from_numpy(pi[idx]).to(dev), B, 0.0)
         else:
             tgt = _pad(torch.from_numpy(moves[idx]).to(dev), B, -1)
+        if own is not None:  # padding rows are invalid: no ownership term
+            ot = _pad(torch.from_numpy(own[idx]).to(dev), B, 0)
+            ov = _pad(torch.from_numpy(own_valid[idx]).to(dev), B, 0.0)
+            return planes, (tgt, zt, (ot, ov))
         return planes, (tgt, zt)
 
     steps = max(1, len(my_train) // B)
     for epoch in range(args.epochs):
         t0 = time.perf_counter()
         order = order_rng.permutation(my_train)
-        sums = torch.zeros(4, device=dev, dtype=torch.float64)
+        nm = 6 if own is not None else 4
+        sums = torch.zeros(nm + 1, device=dev, dtype=torch.float64)  # the metric sums, then the valid ownership rows
         for s in range(steps):
             idx = order[s * B:(s + 1) * B]
             if len(idx) < B:  # fewer positions than one minibatch: wrap around
@@ -141,12 +171,17 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
             planes, tgt = batch(idx)
             sym = None if args.no_symmetries else torch.randint(0, 8, (B,), device=dev, dtype=torch.int32,
                                                                  generator=gen)
-            sums += torch.stack([m.double() for m in trainer.step(planes, tgt, sym)])
+            sums[:nm] += torch.stack([m.double() for m in trainer.step(planes, tgt, sym)])
+            if own is not None:
+                sums[nm] += tgt[2][1].double().sum()
         agdist.all_reduce_sum_(sums)
         seen = steps * B * world
         logs = {k: float(v) / seen for k, v in zip(_KEYS, sums)}
+        if own is not None:
+            logs.update({k: float(v) / max(1.0, float(sums[nm])) for k, v in zip(_OWN_KEYS, sums[4:6])})
         if n_val > 0:
             vs = torch.zeros(5, device=dev, dtype=torch.float64)
+            vo = torch.zeros(3, device=dev, dtype=torch.float64)
             for i in range(0, len(my_val), B):
                 idx = my_val[i:i + B]
                 planes, tgt = batch(idx)
@@ -156,11 +191,17 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
                     pv = trainer.predict(planes)[len(idx):].double()
                     m[2] -= (pv ** 2).sum()
                     m[3] -= (torch.sign(pv) == 0).double().sum()
-                vs[:4] += m
+                vs[:4] += m[:4]
                 vs[4] += len(idx)
+                if own is not None:
+                    vo[:2] += m[4:6]
+                    vo[2] += tgt[2][1].double().sum()
             agdist.all_reduce_sum_(vs)
             n = max(1.0, float(vs[4]))
             logs.update({"val_" + k: float(v) / n for k, v in zip(_KEYS, vs[:4])})
+            if own is not None:
+                agdist.all_reduce_sum_(vo)
+                logs.update({"val_" + k: float(v) / max(1.0, float(vo[2])) for k, v in zip(_OWN_KEYS, vo[:2])})
         dt = time.perf_counter() - t0
         if env.is_main:
             ep = meta.on_epoch_end(logs)

@@ -8,6 +8,11 @@
          positions, pair against dual
   train  training step time at B = 2176: HipPolicyValueTrainer (49 planes) against HipPolicyTrainer
          (48 planes), both 12 x 192
+  own    (not in the default set) the ownership head at B = 2176, 12 x 192: (a) the head alone, the fused
+         pair value_own_head + head_backward_add2 against the composition of the older kernels that
+         computes the same (head_logits twice, tanh / MSE elementwise in torch, head_backward_add
+         twice); (b) the whole training step of the dual net with the head against the same net
+         without it.  Prints the byte counts of one pass over the trunk output next to the times.
 
 Every timed window is warmed up first and ends in a device synchronise (or the batch's own event);
 the two sides alternate inside one process and every figure is the median of ``--repeats`` windows,
@@ -137,6 +142,93 @@ def bench_train(dev, B, steps, repeats, only=None):
     return {"B": B} | {k + "_step_ms": spread(v) for k, v in res.items()}
 
 
+def _alternate(sides, warm, iters, repeats):
+    res = {k: [] for k in sides}
+    for fn in sides.values():
+        for _ in range(warm):
+            fn()
+    torch.cuda.synchronize()
+    for _ in range(repeats):
+        for name, fn in sides.items():
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(iters):
+                fn()
+            torch.cuda.synchronize()
+            res[name].append((time.perf_counter() - t) / iters * 1e3)
+    return res
+
+
+def bench_own(dev, B, steps, repeats, only=None):
+    from alphago_amd import ops
+    from alphago_amd.models.nets import PolicyValueNet
+    from alphago_amd.train.engine import HipPolicyValueTrainer
+
+    ops.load()
+    S, C, SS = 19, 192, 361
+    g = torch.Generator().manual_seed(0)
+    out = {"B": B, "bytes": {"pass_over_trunk_output": B * SS * C * 2}}
+    pas = out["bytes"]["pass_over_trunk_output"]
+    # reads of y, reads + writes of dz (the (B, S*S) rows and the weights are three orders smaller)
+    out["bytes"].update(value_own_head=pas, head_backward_add2=3 * pas, fused_pair=4 * pas,
+                        head_logits_x2=2 * pas, head_backward_add_x2=6 * pas, unfused_composition=8 * pas)
+    if only in (None, "fused", "unfused"):
+        y = torch.zeros(B, S + 2, S + 2, C, dtype=torch.bfloat16, device=dev)
+        y[:, 1:-1, 1:-1] = torch.randn(B, S, S, C, generator=g).to(torch.bfloat16).clamp_min(0).to(dev)
+        dz0 = torch.zeros_like(y)
+        dz0[:, 1:-1, 1:-1] = (torch.randn(B, S, S, C, generator=g) * 1e-3).to(torch.bfloat16).to(dev)
+        dz = dz0.clone()
+        wv, wo = [(torch.randn(C, generator=g) * 0.05).to(dev) for _ in range(2)]
+        bv, bo = [torch.randn(1, generator=g).to(dev) for _ in range(2)]
+        t8 = torch.randint(-1, 2, (B, SS), generator=g).to(torch.int8).to(dev)
+        tf = t8.float()
+        sym = torch.zeros(B, dtype=torch.int32, device=dev)
+        valid = torch.ones(B, device=dev)
+        dzl = (torch.randn(B, SS, generator=g) / B).to(dev)  # the value head's dlogits, as the dense backward leaves them
+        zv, own, olog, dlo = [torch.zeros(B, SS, device=dev) for _ in range(4)]
+        oloss, oagree = torch.zeros(B, device=dev), torch.zeros(B, device=dev)
+        dh1, dh2 = torch.zeros(B, C + 1, device=dev), torch.zeros(B, C + 1, device=dev)
+        gs = 1.0 / B
+
+        def fused():
+            ops.value_own_head(y, wv, bv, wo, bo, zv, S, own=own, target=t8, sym=sym, valid=valid, oloss=oloss,
+                               oagree=oagree, dlo=dlo, grad_scale=gs)
+            ops.head_backward_add2(y, wv, dzl, wo, dlo, dz, dh1, dh2, S)
+
+        def unfused():
+            ops.head_logits(y, wv, bv, zv, S)
+            ops.head_logits(y, wo, bo, olog, S)
+            torch.tanh(olog, out=own)
+            e = own - tf
+            oloss.copy_((e * e).mean(1))
+            oagree.copy_(((torch.sign(own) == tf) & (tf != 0)).float().sum(1))
+            dlo.copy_((valid * (gs * 2.0 / SS)).unsqueeze(1) * e * (1 - own * own))
+            ops.head_backward_add(y, wv, dzl, dz, dh1, S)
+            ops.head_backward_add(y, wo, dlo, dz, dh2, S)
+
+        arms = {k: v for k, v in (("fused", fused), ("unfused", unfused)) if only in (None, k)}
+        res = _alternate(arms, 3, 20 * steps, repeats)  # a call is a fraction of a millisecond: 20 x the step count per window
+        out["head"] = {k + "_ms": spread(v) for k, v in res.items()}
+        if len(res) == 2:
+            f, u = res["fused"], res["unfused"]
+            out["head"]["fused_faster_by_ms"] = round(float(np.median(u) - np.median(f)), 4)
+            out["head"]["min_max_spread_ms"] = round(float(max(max(f) - min(f), max(u) - min(u))), 4)
+        del y, dz, dz0
+    if only in (None, "step"):
+        moves = torch.randint(0, 361, (B,), dtype=torch.int32, generator=g).to(dev)
+        z = (torch.randint(0, 2, (B,), generator=g) * 2 - 1).float().to(dev)
+        sym = torch.randint(0, 8, (B,), dtype=torch.int32, generator=g).to(dev)
+        x49 = torch.randint(0, 2, (B, 49, 19, 19), dtype=torch.uint8, generator=g).to(dev)
+        ot = torch.randint(-1, 2, (B, SS), generator=g).to(torch.int8).to(dev)
+        ov = torch.ones(B, device=dev)
+        th = HipPolicyValueTrainer(PolicyValueNet(ownership=1), B, lr=0.003, device=dev)
+        tn = HipPolicyValueTrainer(PolicyValueNet(), B, lr=0.003, device=dev)
+        res = _alternate({"with_head": lambda: th.step(x49, (moves, z, (ot, ov)), sym),
+                          "without_head": lambda: tn.step(x49, (moves, z), sym)}, 3, steps, repeats)
+        out["step"] = {k + "_step_ms": spread(v) for k, v in res.items()}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="*", default=["leaf", "genmove", "train"])
@@ -145,6 +237,8 @@ def main():
     ap.add_argument("--train-batch", type=int, default=2176)
     ap.add_argument("--train-steps", type=int, default=10)
     ap.add_argument("--train-only", choices=["policy", "dual"], default=None, help="one trainer only (kernel traces)")
+    ap.add_argument("--own-only", choices=["fused", "unfused", "step"], default=None,
+                    help="own: one arm only (kernel traces)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("pv_benchmark measures on a GPU")
@@ -163,6 +257,8 @@ def main():
             out["genmove"] = bench_genmove(pol, val, pv, a.positions, 1600, 32)
     if "train" in a.what:
         out["train"] = bench_train(dev, a.train_batch, a.train_steps, a.repeats, a.train_only)
+    if "own" in a.what:
+        out["own"] = bench_own(dev, a.train_batch, a.train_steps, a.repeats, a.own_only)
     print(json.dumps(out))
 
 
