@@ -4,7 +4,10 @@
 // per-board partials of the head weight/bias gradients).  One workgroup per
 // board: the board's 361 x F activations are read from HBM once into registers
 // (BoardRows / BoardRegs), and nothing of the head round-trips through HBM as a
-// separate tensor.
+// separate tensor.  The kernel template and the blocks it is made of are in
+// policy_head.h; this file instantiates the plain kernels and holds the streaming
+// kernels of the value net's head (head_logits, head_backward: head_dots,
+// head_input_backward) with value_out and head_grad_sums.
 //
 // Reference ops replaced: policy.py:145-154 (Conv 1x1 / Flatten / Softmax),
 // Keras categorical_crossentropy with output clipping (supervised_policy_trainer
@@ -67,74 +70,47 @@ __device__ __forceinline__ void head_dots(const __bf16* base, const float* w_s, 
 template <int NT>
 __device__ __forceinline__ void head_input_backward(const PolicyHeadArgs& a, int b, const __bf16* base,
                                                     const float* w_s, const float* g_s) {
-  // One pass over the board's activations: thread (r, c8) walks positions
-  // p = r, r + R, ... for its 8-channel group, writing the ReLU'-masked dY and
-  // accumulating sum_p g[p] * y[p, c] in registers; the R partials per
-  // channel are then reduced through LDS.  Consecutive threads cover
-  // consecutive 16-B channel groups of one position (coalesced rows).
+  // One pass over the board's activations (head_walk_positions, eight positions in flight): the
+  // ReLU'-masked dY is written and sum_p g[p] * y[p, c] accumulated in registers; the R partials per
+  // channel are then reduced through LDS.
   __shared__ float part[NT * 8];
   const int tid = threadIdx.x;
-  const int SS = a.S * a.S;
   const int HP = a.S + 2;
   const int C8 = a.C >> 3;
-  const int R = blockDim.x / C8;  // positions processed concurrently
-  const int r = tid / C8, cg = tid - r * C8;
+  const int c8 = (tid % C8) << 3;
   __bf16* dzb = a.dz + (size_t)b * HP * HP * a.C;
   uint8_t* dz8b = a.dz8 ? a.dz8 + (size_t)b * HP * HP * a.C : nullptr;
   const float sc8 = a.dz8 ? *a.dz8_scale : 0.f;
   float m8 = 0.f;  // max |bf16 dY| (e5m2 output)
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (r < R) {
-    const int c8 = cg << 3;
-    // BU positions' loads issued before their stores (latency-bound loop)
-    constexpr int BU = 8;
-    for (int p0 = r; p0 < SS; p0 += BU * R) {
-      bf16x8 v[BU];
-      size_t off[BU];
+  head_walk_positions<NT, 8, false>(base, nullptr, a.S, a.C, [&](int p, size_t off, const bf16x8& v, const bf16x8&) {
+    const float g = g_s[p];
+    bf16x8 o;
 #pragma unroll
-      for (int u = 0; u < BU; ++u) {
-        const int p = p0 + u * R;
-        const int pc = p < SS ? p : SS - 1;
-        const int i = pc / a.S, j = pc - (pc / a.S) * a.S;
-        off[u] = (size_t)((i + 1) * HP + j + 1) * a.C + c8;
-        v[u] = *(const bf16x8*)(base + off[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < BU; ++u) {
-        const int p = p0 + u * R;
-        if (p < SS) {
-          const float g = g_s[p];
-          bf16x8 o;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float y = (float)v[u][e];
-            o[e] = (__bf16)(y > 0.f ? g * w_s[c8 + e] : 0.f);
-            acc[e] += g * y;
-          }
-          if (dz8b) {
-            // quantize_bf8_dev_kernel's conversion of the bf16 value: the same bytes and max, and the
-            // bf16 dz is never written or re-read
-            float f[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              f[e] = (float)o[e];
-              m8 = fmaxf(m8, fabsf(f[e]));
-              f[e] = fminf(fmaxf(f[e] * sc8, -57344.f), 57344.f);
-            }
-            int lo = __builtin_amdgcn_cvt_pk_bf8_f32(f[0], f[1], 0, false);
-            lo = __builtin_amdgcn_cvt_pk_bf8_f32(f[2], f[3], lo, true);
-            int hi = __builtin_amdgcn_cvt_pk_bf8_f32(f[4], f[5], 0, false);
-            hi = __builtin_amdgcn_cvt_pk_bf8_f32(f[6], f[7], hi, true);
-            *(int2*)(dz8b + off[u]) = make_int2(lo, hi);
-          } else {
-            *(bf16x8*)(dzb + off[u]) = o;
-          }
-        }
-      }
+    for (int e = 0; e < 8; ++e) {
+      const float y = (float)v[e];
+      o[e] = (__bf16)(y > 0.f ? g * w_s[c8 + e] : 0.f);
+      acc[e] += g * y;
     }
-  }
+    if (dz8b) {
+      // quantize_bf8_dev_kernel's conversion of the bf16 value: the same bytes and max, and the
+      // bf16 dz is never written or re-read
+      float f[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) part[tid * 8 + e] = acc[e];
+      for (int e = 0; e < 8; ++e) {
+        f[e] = (float)o[e];
+        m8 = fmaxf(m8, fabsf(f[e]));
+        f[e] = fminf(fmaxf(f[e] * sc8, -57344.f), 57344.f);
+      }
+      int lo = __builtin_amdgcn_cvt_pk_bf8_f32(f[0], f[1], 0, false);
+      lo = __builtin_amdgcn_cvt_pk_bf8_f32(f[2], f[3], lo, true);
+      int hi = __builtin_amdgcn_cvt_pk_bf8_f32(f[4], f[5], 0, false);
+      hi = __builtin_amdgcn_cvt_pk_bf8_f32(f[6], f[7], hi, true);
+      *(int2*)(dz8b + off) = make_int2(lo, hi);
+    } else {
+      *(bf16x8*)(dzb + off) = o;
+    }
+  });
   if (dz8b) {  // one atomic per board into the spread amax slots
     __shared__ float red8[NT / 64];
     m8 = wave_max(m8);
@@ -145,14 +121,7 @@ __device__ __forceinline__ void head_input_backward(const PolicyHeadArgs& a, int
       if (m8 > 0.f) atomicMax(a.dz8_amax + (b & (kFp8AmaxSlots - 1)), __float_as_uint(m8));
     }
   }
-  __syncthreads();
-  float* dh = a.dhead + (size_t)b * (a.C_real + 1);
-  for (int c = tid; c < a.C_real; c += blockDim.x) {
-    const int g8 = c >> 3, e = c & 7;
-    float s = 0.f;
-    for (int rr = 0; rr < R; ++rr) s += part[(rr * C8 + g8) * 8 + e];
-    dh[c] = s;
-  }
+  head_channel_sums<NT>(part, acc, a.dhead + (size_t)b * (a.C_real + 1), a.C_real, C8, NT / C8);
 }
 
 // Head logits only: z[b][p] = y[b,p,:] . w + bias (value-net head input,
@@ -164,7 +133,7 @@ __global__ __launch_bounds__(NT) void head_logits_kernel(PolicyHeadArgs a) {
   const int tid = threadIdx.x;
   const int SS = a.S * a.S;
   const int HP = a.S + 2;
-  for (int c = tid; c < a.C; c += NT) w_s[c] = c < a.C_real ? a.w[c] : 0.f;
+  head_stage_weights<NT>({w_s}, {a.w}, a.C, a.C_real);
   __syncthreads();
   __shared__ float z_s[368];
   const __bf16* base = a.y + (size_t)b * HP * HP * a.C;
@@ -183,7 +152,7 @@ __global__ __launch_bounds__(NT) void head_backward_kernel(PolicyHeadArgs a, con
   const int tid = threadIdx.x;
   const int SS = a.S * a.S;
   const int HP = a.S + 2;
-  for (int c = tid; c < a.C; c += NT) w_s[c] = c < a.C_real ? a.w[c] : 0.f;
+  head_stage_weights<NT>({w_s}, {a.w}, a.C, a.C_real);
   float gs = 0.f;
   for (int p = tid; p < SS; p += NT) {
     const float g = dlogits[(size_t)b * SS + p];
@@ -192,8 +161,7 @@ __global__ __launch_bounds__(NT) void head_backward_kernel(PolicyHeadArgs a, con
   }
   __syncthreads();
   head_input_backward<NT>(a, b, a.y + (size_t)b * HP * HP * a.C, w_s, g_s);
-  gs = block_reduce_sum(gs, red);
-  if (tid == 0) a.dhead[(size_t)b * (a.C_real + 1) + a.C_real] = gs;
+  head_bias_grad(gs, red, a.dhead + (size_t)b * (a.C_real + 1) + a.C_real);
 }
 
 // Value output layer: v = tanh(h . w2 + b2) (value.py:28-29) and, with
@@ -250,11 +218,11 @@ void launch_head_grad_sums(const float* dhead, int B, int N, const float* loss, 
 }
 
 void launch_head_logits(const PolicyHeadArgs& a, hipStream_t st) {
-  if (a.B < kHeadWideBelow) hipLaunchKernelGGL(head_logits_kernel<1024>, dim3(a.B), dim3(1024), 0, st, a);
+  if (head_wide_block(a.B)) hipLaunchKernelGGL(head_logits_kernel<1024>, dim3(a.B), dim3(1024), 0, st, a);
   else hipLaunchKernelGGL(head_logits_kernel<256>, dim3(a.B), dim3(256), 0, st, a);
 }
 void launch_head_backward(const PolicyHeadArgs& a, const float* dlogits, hipStream_t st) {
-  if (a.B < kHeadWideBelow) hipLaunchKernelGGL(head_backward_kernel<1024>, dim3(a.B), dim3(1024), 0, st, a, dlogits);
+  if (head_wide_block(a.B)) hipLaunchKernelGGL(head_backward_kernel<1024>, dim3(a.B), dim3(1024), 0, st, a, dlogits);
   else hipLaunchKernelGGL(head_backward_kernel<256>, dim3(a.B), dim3(256), 0, st, a, dlogits);
 }
 void launch_value_out(const ValueOutArgs& a, hipStream_t st) {

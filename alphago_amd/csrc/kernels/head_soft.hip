@@ -15,10 +15,10 @@
 // clip of p to [1e-7, 1 - 1e-7]: the loss is the exact cross-entropy of its gradient.
 //
 // A __global__ and an argument struct of its own: PolicyHeadArgs, and with it the kernarg layout and
-// code objects of the plain and REG kernels, stay exactly as they are.  The logit / argmax / softmax
-// prologue below repeats policy_head_kernel's for that reason (an accepted duplication); the board
-// holders, block reductions and the backward are shared (policy_head.h).  No legal mask, no
-// temperature, no binary-CE loss, no entropy / KL terms or stats, no e5m2 dz.
+// code objects of the plain and REG kernels, stay exactly as they are.  From policy_head.h it uses
+// head_stage_weights, the board holders with their backward, board_launder, block_argmax (for the
+// logits and for q), the block reductions and head_bias_grad.  No legal mask, no temperature, no
+// binary-CE loss, no entropy / KL terms or stats, no e5m2 dz.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(NT) void policy_head_soft_kernel(PolicyHeadSoftArgs
     sym_inv(s, a.S, i, j, x, y);
     qv = fmaxf(a.tdist[(size_t)b * a.T + x * a.S + y], 0.f);
   }
-  for (int c = tid; c < a.C; c += NT) w_s[c] = c < a.C_real ? a.w[c] : 0.f;
+  head_stage_weights<NT>({w_s}, {a.w}, a.C, a.C_real);
   Board board;
   board.load(a.y + (size_t)b * HP * HP * a.C, a.S, a.C);
   __syncthreads();
@@ -60,11 +60,7 @@ __global__ __launch_bounds__(NT) void policy_head_soft_kernel(PolicyHeadSoftArgs
   float lmax = -INFINITY;
   int lidx = 0x7fffffff;
   board.dots(w_s, z_s, a.S, a.C);
-  // the board's registers made opaque here: otherwise the compiler keeps the fp32 conversions of the
-  // dot products alive for the backward, twice the registers of the packed bf16 (BoardRegs<1024> spilt
-  // 180 bytes per lane to scratch)
-#pragma unroll
-  for (int u = 0; u < Board::P; ++u) asm volatile("" : "+v"(board.v[u]));
+  board_launder(board);  // or the backward keeps the dots' fp32 copies: BoardRegs<1024> spilt 180 bytes per lane
   for (int p = tid; p < SS; p += NT) {
     const float z = z_s[p] + bias;
     z_s[p] = z;
@@ -74,54 +70,10 @@ __global__ __launch_bounds__(NT) void policy_head_soft_kernel(PolicyHeadSoftArgs
     }
   }
   // block argmax / max of the logits and of q (ties -> smallest index)
-  float qmax = tid < SS ? qv : -INFINITY;
-  int qidx = tid < SS ? tid : 0x7fffffff;
-  {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(lmax, o, 64);
-      const int oi = __shfl_xor(lidx, o, 64);
-      if (ov > lmax || (ov == lmax && oi < lidx)) {
-        lmax = ov;
-        lidx = oi;
-      }
-    }
-    if ((tid & 63) == 0) {
-      red[tid >> 6] = lmax;
-      redi[tid >> 6] = lidx;
-    }
-    __syncthreads();
-    lmax = red[0];
-    lidx = redi[0];
-    for (int w = 1; w < NT / 64; ++w)
-      if (red[w] > lmax || (red[w] == lmax && redi[w] < lidx)) {
-        lmax = red[w];
-        lidx = redi[w];
-      }
-    __syncthreads();  // red / redi are reused for q
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(qmax, o, 64);
-      const int oi = __shfl_xor(qidx, o, 64);
-      if (ov > qmax || (ov == qmax && oi < qidx)) {
-        qmax = ov;
-        qidx = oi;
-      }
-    }
-    if ((tid & 63) == 0) {
-      red[tid >> 6] = qmax;
-      redi[tid >> 6] = qidx;
-    }
-    __syncthreads();
-    qmax = red[0];
-    qidx = redi[0];
-    for (int w = 1; w < NT / 64; ++w)
-      if (red[w] > qmax || (red[w] == qmax && redi[w] < qidx)) {
-        qmax = red[w];
-        qidx = redi[w];
-      }
-  }
-  const float zmax = lmax;
+  const ArgMax zm = block_argmax<NT>(lmax, lidx, red, redi);
+  __syncthreads();  // red / redi are reused for q
+  const ArgMax qm = block_argmax<NT>(tid < SS ? qv : -INFINITY, tid < SS ? tid : 0x7fffffff, red, redi);
+  const float zmax = zm.v;
   float ls = 0.f;
   for (int p = tid; p < SS; p += NT) ls += __expf(z_s[p] - zmax);
   const float sum = block_reduce_sum(ls, red);
@@ -140,7 +92,7 @@ __global__ __launch_bounds__(NT) void policy_head_soft_kernel(PolicyHeadSoftArgs
   ce = block_reduce_sum(ce, red);
   if (tid == 0) {
     a.loss[b] = has ? 0.f - ce : 0.f;
-    a.correct[b] = (has && lidx == qidx) ? 1.f : 0.f;
+    a.correct[b] = (has && zm.idx == qm.idx) ? 1.f : 0.f;
   }
   const float sc = has ? a.grad_scale * (a.weight ? a.weight[b] : 1.f) : 0.f;
   for (int p = tid; p < SS; p += NT) z_s[p] = has ? (__expf(z_s[p] - zmax) * inv - q_s[p]) * sc : 0.f;
@@ -153,15 +105,11 @@ __global__ __launch_bounds__(NT) void policy_head_soft_kernel(PolicyHeadSoftArgs
   pa.C = a.C;
   pa.C_real = a.C_real;
   board.backward(pa, b, w_s, z_s);
-  float gs = 0.f;
-  for (int p = tid; p < SS; p += NT) gs += z_s[p];
-  gs = block_reduce_sum(gs, red);
-  if (tid == 0) a.dhead[(size_t)b * (a.C_real + 1) + a.C_real] = gs;
+  head_bias_grad<NT>(z_s, SS, red, a.dhead + (size_t)b * (a.C_real + 1) + a.C_real);
 }
 
-// policy_head_go's rule
 void launch_policy_head_soft(const PolicyHeadSoftArgs& a, hipStream_t st) {
-  if (a.B >= kHeadWideBelow && a.S * (a.C >> 3) <= 512)
+  if (head_rows_mapping(a.B, a.S, a.C))
     hipLaunchKernelGGL((policy_head_soft_kernel<512, BoardRows<512>>), dim3(a.B), dim3(512), 0, st, a);
   else
     hipLaunchKernelGGL((policy_head_soft_kernel<1024, BoardRegs<1024>>), dim3(a.B), dim3(1024), 0, st, a);

@@ -173,6 +173,48 @@ void conv_wgrad_reduce_multi(const std::vector<Tensor>& slabs, const std::vector
   launch_check("conv_wgrad_reduce_multi");
 }
 
+// What every 1x1 head op checks before a launch: y (B, S+2, S+2, C) bf16 contiguous with
+// 8 <= C <= 256 a multiple of 8 and 1 <= S, S * S <= 361 (the kernels hold a board in 368 LDS slots and
+// up to 19 rows of registers); the heads' weights f32 with one count C_real <= C; biases of one entry.
+void head_geometry(const char* op, const Tensor& y, int64_t S, std::initializer_list<const Tensor*> ws,
+                   std::initializer_list<const Tensor*> bs) {
+  CHECK_BF16(y); CHECK_CONTIG(y);
+  TORCH_CHECK(y.dim() == 4, op, ": head input must be (B, S+2, S+2, C)");
+  const int64_t C = y.size(3);
+  TORCH_CHECK(y.size(1) == S + 2 && y.size(2) == S + 2, op, ": head input must have pad 1");
+  TORCH_CHECK(C % 8 == 0 && C >= 8 && C <= 256, op, ": head channels must be a multiple of 8 and <= 256");
+  TORCH_CHECK(S >= 1 && S * S <= 361, op, ": board too large (the head holds at most 19 x 19)");
+  const Tensor* w0 = *ws.begin();
+  for (const Tensor* w : ws) {
+    CHECK_F32(*w); CHECK_CONTIG(*w);
+    TORCH_CHECK(w->numel() >= 1 && w->numel() <= C && w->numel() == w0->numel(), op,
+                ": head weights must have the same (at most C) entries");
+  }
+  for (const Tensor* b : bs) {
+    CHECK_F32(*b);
+    TORCH_CHECK(b->numel() >= 1, op, ": head biases must hold one entry");
+  }
+}
+
+// the optional per-board inputs of the head ops; nullptr when absent
+const float* head_board_weight(const char* op, const char* name, const c10::optional<Tensor>& t, int64_t B) {
+  if (!t.has_value()) return nullptr;
+  CHECK_F32(*t); CHECK_CONTIG(*t);
+  TORCH_CHECK(t->numel() == B, op, ": ", name, " must be (B,)");
+  return t->data_ptr<float>();
+}
+const uint8_t* head_legal(const char* op, const c10::optional<Tensor>& t, int64_t B, int64_t S) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->scalar_type() == at::kByte && t->numel() == B * S * S && t->is_contiguous(), op,
+              ": legal must be contiguous uint8 (B, S*S)");
+  return t->data_ptr<uint8_t>();
+}
+const int* head_sym(const char* op, const c10::optional<Tensor>& t, int64_t B) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->scalar_type() == at::kInt && t->numel() == B && t->is_contiguous(), op, ": sym int32 (B,)");
+  return t->data_ptr<int>();
+}
+
 void policy_head(const Tensor& y, const Tensor& w, const Tensor& b, const c10::optional<Tensor>& target,
                  const c10::optional<Tensor>& legal, const c10::optional<Tensor>& weight, const c10::optional<Tensor>& dz, const c10::optional<Tensor>& loss,
                  const c10::optional<Tensor>& correct, const c10::optional<Tensor>& dhead,
@@ -180,12 +222,8 @@ void policy_head(const Tensor& y, const Tensor& w, const Tensor& b, const c10::o
                  const c10::optional<Tensor>& ref_probs, const c10::optional<Tensor>& stats, double ent_coef,
                  double kl_coef) {
   check_dev("policy_head", y, w, b, target, legal, weight, dz, loss, correct, dhead, probs, ref_probs, stats);
-  CHECK_BF16(y); CHECK_CONTIG(y); CHECK_F32(w); CHECK_F32(b);
+  head_geometry("policy_head", y, S, {&w}, {&b});
   const int64_t B = y.size(0), C = y.size(3);
-  TORCH_CHECK(y.size(1) == S + 2, "head input must have pad 1");
-  TORCH_CHECK(C % 8 == 0 && C <= 256, "head channels must be a multiple of 8 and <= 256");
-  TORCH_CHECK(w.numel() <= C, "head weight must have at most as many entries as the head has channels");
-  TORCH_CHECK(S * S <= 361, "board too large (the head holds at most 19 x 19)");
   agk::PolicyHeadArgs a{};
   a.y = bfp(y);
   a.w = w.data_ptr<float>();
@@ -207,15 +245,8 @@ void policy_head(const Tensor& y, const Tensor& w, const Tensor& b, const c10::o
     a.correct = correct->data_ptr<float>();
     a.dhead = dhead->data_ptr<float>();
   }
-  if (weight.has_value()) {
-    CHECK_F32(*weight);
-    TORCH_CHECK(weight->numel() == B, "weight must be (B,)");
-    a.weight = weight->data_ptr<float>();
-  }
-  if (legal.has_value()) {
-    TORCH_CHECK(legal->scalar_type() == at::kByte && legal->numel() == B * S * S, "legal must be uint8 (B, S*S)");
-    a.legal = legal->data_ptr<uint8_t>();
-  }
+  a.weight = head_board_weight("policy_head", "weight", weight, B);
+  a.legal = head_legal("policy_head", legal, B, S);
   if (probs.has_value()) {
     CHECK_F32(*probs);
     TORCH_CHECK(probs->numel() == B * S * S, "probs must be (B, S*S)");
@@ -255,13 +286,8 @@ void policy_head_soft(const Tensor& y, const Tensor& w, const Tensor& b, const T
                       const c10::optional<Tensor>& sym, const c10::optional<Tensor>& weight, const Tensor& dz,
                       const Tensor& loss, const Tensor& correct, const Tensor& dhead, int64_t S, double grad_scale) {
   check_dev("policy_head_soft", y, w, b, tdist, sym, weight, dz, loss, correct, dhead);
-  CHECK_BF16(y); CHECK_CONTIG(y); CHECK_F32(w); CHECK_F32(b);
-  TORCH_CHECK(y.dim() == 4, "head input must be (B, S+2, S+2, C)");
+  head_geometry("policy_head_soft", y, S, {&w}, {&b});
   const int64_t B = y.size(0), C = y.size(3);
-  TORCH_CHECK(y.size(1) == S + 2 && y.size(2) == S + 2, "head input must have pad 1");
-  TORCH_CHECK(C % 8 == 0 && C <= 256, "head channels must be a multiple of 8 and <= 256");
-  TORCH_CHECK(w.numel() <= C, "head weight must have at most as many entries as the head has channels");
-  TORCH_CHECK(S >= 1 && S * S <= 361, "board too large (the head holds at most 19 x 19)");
   CHECK_F32(tdist); CHECK_CONTIG(tdist);
   TORCH_CHECK(tdist.dim() == 2 && tdist.size(0) == B && (tdist.size(1) == S * S || tdist.size(1) == S * S + 1),
               "tdist must be (B, S*S) or (B, S*S + 1)");
@@ -281,15 +307,8 @@ void policy_head_soft(const Tensor& y, const Tensor& w, const Tensor& b, const T
   a.dhead = dhead.data_ptr<float>();
   a.B = (int)B; a.S = (int)S; a.C = (int)C; a.C_real = (int)w.numel(); a.T = (int)tdist.size(1);
   a.grad_scale = (float)grad_scale;
-  if (sym.has_value()) {
-    TORCH_CHECK(sym->scalar_type() == at::kInt && sym->numel() == B && sym->is_contiguous(), "sym: int32 (B,)");
-    a.sym = sym->data_ptr<int>();
-  }
-  if (weight.has_value()) {
-    CHECK_F32(*weight); CHECK_CONTIG(*weight);
-    TORCH_CHECK(weight->numel() == B, "weight must be (B,)");
-    a.weight = weight->data_ptr<float>();
-  }
+  a.sym = head_sym("policy_head_soft", sym, B);
+  a.weight = head_board_weight("policy_head_soft", "weight", weight, B);
   if (B == 0) return;
   agk::launch_policy_head_soft(a, cur_stream());
   launch_check("policy_head_soft");
@@ -298,9 +317,9 @@ void policy_head_soft(const Tensor& y, const Tensor& w, const Tensor& b, const T
 // z: (B, S*S) f32 <- y (B, S+2, S+2, C) bf16 . w + b
 void head_logits(const Tensor& y, const Tensor& w, const Tensor& b, const Tensor& z, int64_t S) {
   check_dev("head_logits", y, w, b, z);
-  CHECK_BF16(y); CHECK_CONTIG(y); CHECK_F32(w); CHECK_F32(b); CHECK_F32(z); CHECK_CONTIG(z);
+  head_geometry("head_logits", y, S, {&w}, {&b});
+  CHECK_F32(z); CHECK_CONTIG(z);
   const int64_t B = y.size(0), C = y.size(3);
-  TORCH_CHECK(y.size(1) == S + 2 && C % 8 == 0 && C <= 256 && w.numel() <= C && S * S <= 368, "head geometry");
   TORCH_CHECK(z.numel() == B * S * S, "z must be (B, S*S)");
   agk::PolicyHeadArgs a{};
   a.y = bfp(y); a.w = w.data_ptr<float>(); a.b = b.data_ptr<float>(); a.probs = z.data_ptr<float>();
@@ -330,10 +349,9 @@ void head_backward(const Tensor& y, const Tensor& w, const Tensor& dlogits, cons
                    int64_t S, const c10::optional<Tensor>& dz8, const c10::optional<Tensor>& dz8_scale,
                    const c10::optional<Tensor>& dz8_amax) {
   check_dev("head_backward", y, w, dlogits, dz, dhead, dz8, dz8_scale, dz8_amax);
-  CHECK_BF16(y); CHECK_CONTIG(y); CHECK_F32(w); CHECK_F32(dlogits); CHECK_CONTIG(dlogits);
-  CHECK_BF16(dz); CHECK_CONTIG(dz); CHECK_F32(dhead);
+  head_geometry("head_backward", y, S, {&w}, {});
+  CHECK_F32(dlogits); CHECK_CONTIG(dlogits); CHECK_BF16(dz); CHECK_CONTIG(dz); CHECK_F32(dhead);
   const int64_t B = y.size(0), C = y.size(3);
-  TORCH_CHECK(y.size(1) == S + 2 && C % 8 == 0 && C <= 256 && w.numel() <= C && S * S <= 368, "head geometry");
   TORCH_CHECK(dz.sizes() == y.sizes() && dlogits.numel() == B * S * S && dhead.numel() >= B * (w.numel() + 1), "shapes");
   agk::PolicyHeadArgs a{};
   a.y = bfp(y); a.w = w.data_ptr<float>(); a.dz = bfp_mut(dz); a.dhead = dhead.data_ptr<float>();
@@ -361,12 +379,9 @@ void head_backward_add(const Tensor& y, const Tensor& w, const Tensor& dlogits, 
   check_dev("head_backward_add", y, w, dlogits, dz, dhead, dz8);
   TORCH_CHECK(!dz8.has_value(), "head_backward_add: accumulating into an e5m2 dz8 is not supported "
               "(accumulate into the bf16 dz and quantise it with quantize_bf8)");
-  CHECK_BF16(y); CHECK_CONTIG(y); CHECK_F32(w); CHECK_CONTIG(w); CHECK_F32(dlogits); CHECK_CONTIG(dlogits);
-  CHECK_BF16(dz); CHECK_CONTIG(dz); CHECK_F32(dhead); CHECK_CONTIG(dhead);
-  TORCH_CHECK(y.dim() == 4, "head input must be (B, S+2, S+2, C)");
+  head_geometry("head_backward_add", y, S, {&w}, {});
+  CHECK_F32(dlogits); CHECK_CONTIG(dlogits); CHECK_BF16(dz); CHECK_CONTIG(dz); CHECK_F32(dhead); CHECK_CONTIG(dhead);
   const int64_t B = y.size(0), C = y.size(3);
-  TORCH_CHECK(y.size(1) == S + 2 && y.size(2) == S + 2 && C % 8 == 0 && C >= 8 && C <= 256 && w.numel() <= C &&
-                  S >= 1 && S * S <= 361, "head geometry");
   TORCH_CHECK(dz.sizes() == y.sizes() && dlogits.numel() == B * S * S && dhead.numel() >= B * (w.numel() + 1), "shapes");
   agk::PolicyHeadArgs a{};
   a.y = bfp(y); a.w = w.data_ptr<float>(); a.dz = bfp_mut(dz); a.dhead = dhead.data_ptr<float>();
@@ -381,16 +396,9 @@ void head_backward_add(const Tensor& y, const Tensor& w, const Tensor& dlogits, 
 void policy_value_head(const Tensor& y, const Tensor& wp, const Tensor& bp, const Tensor& wv, const Tensor& bv,
                        const Tensor& probs, const Tensor& zv, int64_t S, const c10::optional<Tensor>& legal) {
   check_dev("policy_value_head", y, wp, bp, wv, bv, probs, zv, legal);
-  CHECK_BF16(y); CHECK_CONTIG(y); CHECK_F32(wp); CHECK_F32(bp); CHECK_F32(wv); CHECK_F32(bv);
-  CHECK_CONTIG(wp); CHECK_CONTIG(wv);
+  head_geometry("policy_value_head", y, S, {&wp, &wv}, {&bp, &bv});
   CHECK_F32(probs); CHECK_CONTIG(probs); CHECK_F32(zv); CHECK_CONTIG(zv);
-  TORCH_CHECK(y.dim() == 4, "head input must be (B, S+2, S+2, C)");
   const int64_t B = y.size(0), C = y.size(3);
-  TORCH_CHECK(y.size(1) == S + 2 && y.size(2) == S + 2, "head input must have pad 1");
-  TORCH_CHECK(C % 8 == 0 && C >= 8 && C <= 256, "head channels must be a multiple of 8 and <= 256");
-  TORCH_CHECK(wp.numel() <= C && wv.numel() == wp.numel(), "both head weights must have the same (at most C) entries");
-  TORCH_CHECK(bp.numel() >= 1 && bv.numel() >= 1, "head biases must hold one entry");
-  TORCH_CHECK(S >= 1 && S * S <= 361, "board too large (the head holds at most 19 x 19)");
   TORCH_CHECK(probs.numel() == B * S * S && zv.numel() == B * S * S, "probs and zv must be (B, S*S)");
   agk::PolicyValueHeadArgs a{};
   a.y = bfp(y);
@@ -398,36 +406,10 @@ void policy_value_head(const Tensor& y, const Tensor& wp, const Tensor& bp, cons
   a.wv = wv.data_ptr<float>(); a.bv = bv.data_ptr<float>();
   a.probs = probs.data_ptr<float>(); a.zv = zv.data_ptr<float>();
   a.B = (int)B; a.S = (int)S; a.C = (int)C; a.C_real = (int)wp.numel();
-  if (legal.has_value()) {
-    TORCH_CHECK(legal->scalar_type() == at::kByte && legal->numel() == B * S * S && legal->is_contiguous(),
-                "legal must be uint8 (B, S*S)");
-    a.legal = legal->data_ptr<uint8_t>();
-  }
+  a.legal = head_legal("policy_value_head", legal, B, S);
   if (B == 0) return;
   agk::launch_policy_value_head(a, cur_stream());
   launch_check("policy_value_head");
-}
-
-// the geometry checks the ownership-head ops share: y (B, S+2, S+2, C) bf16, 1x1 head weights / biases f32
-void own_head_geometry(const char* op, const Tensor& y, int64_t S, std::initializer_list<const Tensor*> ws,
-                       std::initializer_list<const Tensor*> bs) {
-  CHECK_BF16(y); CHECK_CONTIG(y);
-  TORCH_CHECK(y.dim() == 4, op, ": head input must be (B, S+2, S+2, C)");
-  const int64_t C = y.size(3);
-  TORCH_CHECK(y.size(1) == S + 2 && y.size(2) == S + 2, op, ": head input must have pad 1");
-  TORCH_CHECK(C % 8 == 0 && C >= 8 && C <= 256, op, ": head channels must be a multiple of 8 and <= 256");
-  TORCH_CHECK(S >= 1 && S * S <= 361, op, ": board too large (the head holds at most 19 x 19)");
-  TORCH_CHECK(y.numel() < (1ll << 31), op, ": tensor too large");
-  const Tensor* w0 = *ws.begin();
-  for (const Tensor* w : ws) {
-    CHECK_F32(*w); CHECK_CONTIG(*w);
-    TORCH_CHECK(w->numel() >= 1 && w->numel() <= C && w->numel() == w0->numel(), op,
-                ": head weights must have the same (at most C) entries");
-  }
-  for (const Tensor* b : bs) {
-    CHECK_F32(*b);
-    TORCH_CHECK(b->numel() >= 1, op, ": head biases must hold one entry");
-  }
 }
 
 // Training / evaluation forward of the value and ownership heads from one read of the board (head_own.hip):
@@ -440,7 +422,8 @@ void value_own_head(const Tensor& y, const Tensor& wv, const Tensor& bv, const T
                     const c10::optional<Tensor>& oloss, const c10::optional<Tensor>& oagree,
                     const c10::optional<Tensor>& dlo, int64_t S, double grad_scale) {
   check_dev("value_own_head", y, wv, bv, wo, bo, zv, own, olog, target, sym, valid, weight, oloss, oagree, dlo);
-  own_head_geometry("value_own_head", y, S, {&wv, &wo}, {&bv, &bo});
+  head_geometry("value_own_head", y, S, {&wv, &wo}, {&bv, &bo});
+  TORCH_CHECK(y.numel() < (1ll << 31), "value_own_head: tensor too large");
   const int64_t B = y.size(0), C = y.size(3), SS = S * S;
   CHECK_F32(zv); CHECK_CONTIG(zv);
   TORCH_CHECK(zv.numel() == B * SS, "value_own_head: zv must be (B, S*S)");
@@ -472,21 +455,9 @@ void value_own_head(const Tensor& y, const Tensor& wv, const Tensor& bv, const T
                 "value_own_head: oloss, oagree (B,), dlo (B, S*S)");
     a.target = target->data_ptr<int8_t>();
     a.oloss = oloss->data_ptr<float>(); a.oagree = oagree->data_ptr<float>(); a.dlo = dlo->data_ptr<float>();
-    if (sym.has_value()) {
-      TORCH_CHECK(sym->scalar_type() == at::kInt && sym->numel() == B && sym->is_contiguous(),
-                  "value_own_head: sym int32 (B,)");
-      a.sym = sym->data_ptr<int>();
-    }
-    if (valid.has_value()) {
-      CHECK_F32(*valid); CHECK_CONTIG(*valid);
-      TORCH_CHECK(valid->numel() == B, "value_own_head: valid must be (B,)");
-      a.valid = valid->data_ptr<float>();
-    }
-    if (weight.has_value()) {
-      CHECK_F32(*weight); CHECK_CONTIG(*weight);
-      TORCH_CHECK(weight->numel() == B, "value_own_head: weight must be (B,)");
-      a.weight = weight->data_ptr<float>();
-    }
+    a.sym = head_sym("value_own_head", sym, B);
+    a.valid = head_board_weight("value_own_head", "valid", valid, B);
+    a.weight = head_board_weight("value_own_head", "weight", weight, B);
   } else {
     TORCH_CHECK(!sym.has_value() && !valid.has_value() && !weight.has_value() && !oloss.has_value() &&
                     !oagree.has_value() && !dlo.has_value(),
@@ -505,7 +476,8 @@ void head_backward_add2(const Tensor& y, const Tensor& w1, const Tensor& g1, con
   check_dev("head_backward_add2", y, w1, g1, w2, g2, dz, dhead1, dhead2, dz8);
   TORCH_CHECK(!dz8.has_value(), "head_backward_add2: accumulating into an e5m2 dz8 is not supported "
               "(accumulate into the bf16 dz and quantise it with quantize_bf8)");
-  own_head_geometry("head_backward_add2", y, S, {&w1, &w2}, {});
+  head_geometry("head_backward_add2", y, S, {&w1, &w2}, {});
+  TORCH_CHECK(y.numel() < (1ll << 31), "head_backward_add2: tensor too large");
   const int64_t B = y.size(0), C = y.size(3), SS = S * S, N = w1.numel() + 1;
   CHECK_F32(g1); CHECK_CONTIG(g1); CHECK_F32(g2); CHECK_CONTIG(g2);
   CHECK_BF16(dz); CHECK_CONTIG(dz); CHECK_F32(dhead1); CHECK_CONTIG(dhead1); CHECK_F32(dhead2); CHECK_CONTIG(dhead2);
@@ -526,7 +498,8 @@ void policy_value_own_head(const Tensor& y, const Tensor& wp, const Tensor& bp, 
                            const Tensor& wo, const Tensor& bo, const Tensor& probs, const Tensor& zv, const Tensor& own,
                            int64_t S, const c10::optional<Tensor>& legal) {
   check_dev("policy_value_own_head", y, wp, bp, wv, bv, wo, bo, probs, zv, own, legal);
-  own_head_geometry("policy_value_own_head", y, S, {&wp, &wv, &wo}, {&bp, &bv, &bo});
+  head_geometry("policy_value_own_head", y, S, {&wp, &wv, &wo}, {&bp, &bv, &bo});
+  TORCH_CHECK(y.numel() < (1ll << 31), "policy_value_own_head: tensor too large");
   const int64_t B = y.size(0), C = y.size(3), SS = S * S;
   CHECK_F32(probs); CHECK_CONTIG(probs); CHECK_F32(zv); CHECK_CONTIG(zv); CHECK_F32(own); CHECK_CONTIG(own);
   TORCH_CHECK(probs.numel() == B * SS && zv.numel() == B * SS && own.numel() == B * SS,
@@ -538,11 +511,7 @@ void policy_value_own_head(const Tensor& y, const Tensor& wp, const Tensor& bp, 
   a.wo = wo.data_ptr<float>(); a.bo = bo.data_ptr<float>();
   a.pv.probs = probs.data_ptr<float>(); a.pv.zv = zv.data_ptr<float>(); a.own = own.data_ptr<float>();
   a.pv.B = (int)B; a.pv.S = (int)S; a.pv.C = (int)C; a.pv.C_real = (int)wp.numel();
-  if (legal.has_value()) {
-    TORCH_CHECK(legal->scalar_type() == at::kByte && legal->numel() == B * SS && legal->is_contiguous(),
-                "policy_value_own_head: legal must be uint8 (B, S*S)");
-    a.pv.legal = legal->data_ptr<uint8_t>();
-  }
+  a.pv.legal = head_legal("policy_value_own_head", legal, B, S);
   if (B == 0) return;
   agk::launch_policy_value_own_head(a, cur_stream());
   launch_check("policy_value_own_head");
@@ -638,16 +607,11 @@ void policy_head_d4(const Tensor& y, const Tensor& w, const Tensor& b, const Ten
                     const Tensor& sym, int64_t G, const c10::optional<Tensor>& legal, double temperature,
                     const c10::optional<Tensor>& scratch) {
   check_dev("policy_head_d4", y, w, b, probs, sym, legal, scratch);
-  CHECK_BF16(y); CHECK_CONTIG(y); CHECK_F32(w); CHECK_CONTIG(w); CHECK_F32(b); CHECK_F32(probs); CHECK_CONTIG(probs);
-  CHECK_CONTIG(sym);
-  TORCH_CHECK(y.dim() == 4 && probs.dim() == 2, "policy_head_d4: y (G*B, S+2, S+2, C), probs (B, S*S)");
+  head_geometry("policy_head_d4", y, S, {&w}, {&b});
+  CHECK_F32(probs); CHECK_CONTIG(probs); CHECK_CONTIG(sym);
+  TORCH_CHECK(probs.dim() == 2, "policy_head_d4: y (G*B, S+2, S+2, C), probs (B, S*S)");
   const int64_t B = probs.size(0), C = y.size(3);
   TORCH_CHECK(G >= 1 && G <= 64 && y.size(0) == G * B, "policy_head_d4: y must hold G * B boards (1 <= G <= 64)");
-  TORCH_CHECK(S >= 1 && y.size(1) == S + 2 && y.size(2) == S + 2, "head input must have pad 1");
-  TORCH_CHECK(C % 8 == 0 && C <= 256, "head channels must be a multiple of 8 and <= 256");
-  TORCH_CHECK(w.numel() <= C, "head weight must have at most as many entries as the head has channels");
-  TORCH_CHECK(b.numel() >= 1, "head bias must have one entry");
-  TORCH_CHECK(S * S <= 361, "board too large (the head holds at most 19 x 19)");
   TORCH_CHECK(probs.size(1) == S * S, "probs must be (B, S*S)");
   TORCH_CHECK(sym.scalar_type() == at::kInt && sym.numel() == G * B, "sym: int32 (G*B,)");
   TORCH_CHECK(temperature > 0.0, "temperature must be > 0");
@@ -656,11 +620,7 @@ void policy_head_d4(const Tensor& y, const Tensor& w, const Tensor& b, const Ten
   a.sym = sym.data_ptr<int>();
   a.B = (int)B; a.G = (int)G; a.S = (int)S; a.C = (int)C; a.C_real = (int)w.numel();
   a.inv_temp = (float)(1.0 / temperature);
-  if (legal.has_value()) {
-    TORCH_CHECK(legal->scalar_type() == at::kByte && legal->numel() == B * S * S && legal->is_contiguous(),
-                "legal must be contiguous uint8 (B, S*S)");
-    a.legal = legal->data_ptr<uint8_t>();
-  }
+  a.legal = head_legal("policy_head_d4", legal, B, S);
   if (scratch.has_value()) {  // (G*B, S*S) f32: few positions run one workgroup per orientation through it
     CHECK_F32(*scratch); CHECK_CONTIG(*scratch);
     TORCH_CHECK(scratch->numel() >= G * B * S * S, "scratch must hold (G*B, S*S) floats");

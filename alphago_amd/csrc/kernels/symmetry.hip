@@ -6,8 +6,8 @@
 //  * policy_head_d4: the policy head (1x1 conv, legal-masked softmax) of the G orientations of a
 //    board, each mapped back to the original frame, averaged in fixed g order.
 //  * group_mean: the same average for the value net's scalar outputs.
-// Symmetry convention: symmetry.h (pack_input's).  Its own translation unit like head_reg.hip
-// (policy_head.h): the plain head kernels' code objects do not depend on these.
+// Symmetry convention: symmetry.h (pack_input's).  From policy_head.h the head uses head_stage_weights,
+// the board holders, the block reductions and head_rows_mapping.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(NT) void policy_head_d4_kernel(PolicyHeadD4Args a) 
   const int tid = threadIdx.x;
   const int SS = a.S * a.S;
   const int HP = a.S + 2;
-  for (int c = tid; c < a.C; c += NT) w_s[c] = c < a.C_real ? a.w[c] : 0.f;
+  head_stage_weights<NT>({w_s}, {a.w}, a.C, a.C_real);
   const float bias = a.b[0];
   const bool own = tid < SS;
   const bool ok = own && (!a.legal || a.legal[(size_t)(b % a.LB) * SS + tid]);
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(NT) void policy_head_d4_kernel(PolicyHeadD4Args a) 
   if (own) a.probs[(size_t)b * SS + tid] = acc * a.inv_g;
 }
 
-// The thread mapping follows the plain head's rule at the trunk batch G * B (policy_head_go), so the
+// The thread mapping follows head_rows_mapping at the trunk batch G * B, so the
 // logits of an orientation carry the bits policy_head_probs gives the same board in a G * B batch.
 //
 // Few positions (B < kD4SplitBelow, G > 1, scratch given): B workgroups walking G boards one after
@@ -102,7 +102,7 @@ void launch_policy_head_d4(const PolicyHeadD4Args& a0, hipStream_t st) {
   PolicyHeadD4Args a = a0;
   a.inv_g = (float)(1.0 / a.G);
   a.LB = a.B;
-  const bool wide = (int64_t)a.G * a.B >= kHeadWideBelow && a.S * (a.C >> 3) <= 512;
+  const bool rows = head_rows_mapping((int64_t)a.G * a.B, a.S, a.C);
   const bool split = a.G > 1 && a.scratch && a.B < kD4SplitBelow;
   if (split) {
     a.probs = a.scratch;
@@ -110,7 +110,7 @@ void launch_policy_head_d4(const PolicyHeadD4Args& a0, hipStream_t st) {
     a.G = 1;
     a.inv_g = 1.f;
   }
-  if (wide) hipLaunchKernelGGL((policy_head_d4_kernel<512, BoardRows<512>>), dim3(a.B), dim3(512), 0, st, a);
+  if (rows) hipLaunchKernelGGL((policy_head_d4_kernel<512, BoardRows<512>>), dim3(a.B), dim3(512), 0, st, a);
   else hipLaunchKernelGGL((policy_head_d4_kernel<1024, BoardRegs<1024>>), dim3(a.B), dim3(1024), 0, st, a);
   if (split) launch_group_mean(a0.scratch, a0.probs, a0.B * a0.S * a0.S, a0.G, st);
 }

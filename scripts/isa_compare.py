@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""Kernel-by-kernel comparison of the conv kernels' gfx950 assembly between two source trees.
+"""Kernel-by-kernel comparison of the kernels' gfx950 assembly between two source trees.
 
-A refactor of the conv templates must leave the machine code alone.  This compiles the conv sources of
+A refactor of kernel templates must leave the machine code alone.  This compiles the same sources of
 two trees (device code only, the flags of alphago_amd/_build.py; nothing is linked or run), or reads two
 assembly files, and pairs their kernels by position within each kernel family (the template name).
 Per kernel it prints the demangled name, a digest of the body and the register / LDS metadata.
@@ -16,12 +16,15 @@ Every pair is classified:
      instructions were reordered);
   FAIL  anything else.  Different kernel counts in a family are an error.
 
-    python scripts/isa_compare.py OLD NEW [--flavor prod|debug|lab] [--out listing.txt] [--keep DIR] [--brief]
+    python scripts/isa_compare.py OLD NEW [--flavor prod|debug|lab] [--sources a.hip,b.hip] [--out listing.txt]
+                                  [--keep DIR] [--brief]
 
 OLD / NEW: a source tree (the directory that holds alphago_amd/), an assembly file, or several assembly
 files joined with commas (one per source file, the same order on both sides).  The lab flavour
 compiles conv.hip, conv_lab.hip, conv_fwd_variants.hip and conv_wgrad_row.hip; the others conv.hip.
-About a minute per tree and file.  Exit status 1 when a pair fails.
+--sources names other files under csrc/kernels instead (the head family has no MFMA, so its pairs are
+class A or FAIL; a failed pair lists both sides' metadata and the difference of the mnemonic multisets,
+to be judged by hand).  About a minute per tree and file.  Exit status 1 when a pair fails.
 """
 from __future__ import annotations
 
@@ -138,12 +141,16 @@ def compare(old, new, out, brief=False):
             print("  %3d %-4s %s %s  %s | old %s | new %s" % (n, c, x[2], y[2], ms, x[1], y[1]), file=out)
             if c != "A":
                 print("           old metadata %s" % " ".join("%s=%d" % (k, x[3].get(k, -1)) for k in META), file=out)
+                ca, cb = collections.Counter(x[4]), collections.Counter(y[4])
+                print("           mnemonics %d -> %d: %s" % (len(x[4]), len(y[4]), " ".join(
+                    "%s%+d" % (k, cb[k] - ca[k]) for k in sorted(set(ca) | set(cb)) if ca[k] != cb[k]) or "same multiset"),
+                      file=out)
     print("class A %d, class B %d, failed %d; %s" % (counts["A"], counts["B"], counts["FAIL"],
                                                       "OK" if ok else "NOT EQUIVALENT"), file=out)
     return ok
 
 
-def asm_of(path, flavor, keep, tag):
+def asm_of(path, flavor, keep, tag, sources):
     """assembly texts of a tree (compiled) or of one assembly file"""
     files = path.split(",")
     if all(os.path.isfile(f) for f in files):
@@ -151,9 +158,9 @@ def asm_of(path, flavor, keep, tag):
     kdir = os.path.join(path, "alphago_amd", "csrc", "kernels")
     with tempfile.TemporaryDirectory() as td:
         d = keep or td
-        outs = [os.path.join(d, "%s_%s_%s.s" % (tag, flavor, s[:-4])) for s in SOURCES[flavor]]
+        outs = [os.path.join(d, "%s_%s_%s.s" % (tag, flavor, s[:-4])) for s in sources]
         with ThreadPoolExecutor(len(outs)) as ex:
-            list(ex.map(lambda so: compile_asm(os.path.join(kdir, so[0]), flavor, so[1]), zip(SOURCES[flavor], outs)))
+            list(ex.map(lambda so: compile_asm(os.path.join(kdir, so[0]), flavor, so[1]), zip(sources, outs)))
         return [open(o).read() for o in outs]
 
 
@@ -162,14 +169,17 @@ def main() -> int:
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--flavor", default="prod", choices=tuple(SOURCES))
+    ap.add_argument("--sources", default="", help="files under alphago_amd/csrc/kernels, joined with commas, "
+                    "instead of the flavour's conv sources")
     ap.add_argument("--out", default="", help="write the listing here instead of standard output")
     ap.add_argument("--keep", default="", help="keep the assembly files in this directory")
     ap.add_argument("--brief", action="store_true", help="one line per family; kernels are listed only outside class A")
     args = ap.parse_args()
     if args.keep:
         os.makedirs(args.keep, exist_ok=True)
-    old = [r for t in asm_of(args.old, args.flavor, args.keep, "old") for r in load(t)]
-    new = [r for t in asm_of(args.new, args.flavor, args.keep, "new") for r in load(t)]
+    sources = args.sources.split(",") if args.sources else SOURCES[args.flavor]
+    old = [r for t in asm_of(args.old, args.flavor, args.keep, "old", sources) for r in load(t)]
+    new = [r for t in asm_of(args.new, args.flavor, args.keep, "new", sources) for r in load(t)]
     out = open(args.out, "w") if args.out else sys.stdout
     print("isa_compare %s build: %d / %d kernels" % (args.flavor, len(old), len(new)), file=out)
     ok = compare(old, new, out, args.brief)
