@@ -18,6 +18,8 @@
 //     (atomicMax, delayed scaling) and writes bf16 and/or e4m3 outputs.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -271,9 +273,18 @@ constexpr int fp8_ga_red_off(int BN, int MB, bool stg, int NW) {
              : 2 * fp8_ga_wrows(BN, 64 * NW) * 128;
 }
 
+// RES: the skip operand of a residual block (ConvFp8ResArgs::res), a compile-time flag as MODE_RES is for the
+// bf16 kernels -- the instantiations without it are the ones that existed before.  The accumulators are in
+// real units after the E8M0 scales, so the bf16 skip adds as the bias does:
+//   forward:  v = max(acc + bias + res, 0), and the bf16 / e4m3 stores, the ReLU' bits and the amax follow;
+//   DGBITS:   v = bit ? acc + res : 0 (the skip gradient joins before ReLU'), then bf16 / e5m2 and max |dx|.
+// Only the 192-wide production tile is instantiated with it (launch_conv_fwd_fp8).  The RES kernels take
+// ConvFp8ResArgs, the others ConvFp8Args as before (kernels.h: the hidden arguments follow the explicit ones).
+template <bool RES>
+using Fp8KernArgs = std::conditional_t<RES, ConvFp8ResArgs, ConvFp8Args>;
 template <int BN, int MB, int NPART, bool OUT_BF16, bool OUT_FP8, bool DG = false, bool DGB = false,
-          bool DGBITS = false, int CW = 64, int NW = 8, bool STGE = false, int PROBE = 0>
-__global__ __launch_bounds__(64 * NW, 8 / NW) void conv_fwd_fp8_ga_kernel(ConvFp8Args a) {
+          bool DGBITS = false, int CW = 64, int NW = 8, bool STGE = false, int PROBE = 0, bool RES = false>
+__global__ __launch_bounds__(64 * NW, 8 / NW) void conv_fwd_fp8_ga_kernel(Fp8KernArgs<RES> a) {
   // PROBE (kernel-lab timing probes, wrong values): bit 1 no MFMA, 2 no pixel loads, 4 no weight
   // staging (load + ds_write), 8 no LDS fragment reads, 16 no epilogue stores;
   // NW: waves per workgroup -- 8 (one workgroup per CU) or 4 (two per CU: one workgroup's
@@ -534,10 +545,21 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv_fwd_fp8_ga_kernel(ConvFp
 #pragma unroll
       for (int i = 0; i < NB; ++i) mk[i] = *(const bf16x4*)(a.mask + ooff + nbase + i * 16);
     }
+    // RES: the block's skip quads, issued together as the mask quads are and unconditionally: pixo is
+    // clamped to pixel M - 1 for lanes past the end, so no load leaves the tensor's interior
+    bf16x4 rs[RES ? NB : 1];
+    if constexpr (RES) {
+#pragma unroll
+      for (int i = 0; i < NB; ++i) rs[i] = *(const bf16x4*)(a.res + ooff + nbase + i * 16);
+    }
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
       const int n = nbase + i * 16;
       f32x4 v = acc[i][j];
+      if constexpr (RES && MASKBITS) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] += (float)rs[i][r];
+      }
       if constexpr (MASKBITS) {
         const uint32_t w = mw[i / (NB / 2)];
 #pragma unroll
@@ -547,10 +569,15 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv_fwd_fp8_ga_kernel(ConvFp
         for (int r = 0; r < 4; ++r) v[r] = (float)mk[i][r] > 0.f ? v[r] : 0.f;
       } else {
         const f32x4 bb = bias4[i];
-        v[0] = fmaxf(v[0] + bb[0], 0.f);
-        v[1] = fmaxf(v[1] + bb[1], 0.f);
-        v[2] = fmaxf(v[2] + bb[2], 0.f);
-        v[3] = fmaxf(v[3] + bb[3], 0.f);
+        if constexpr (RES) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r] + bb[r] + (float)rs[i][r], 0.f);
+        } else {
+          v[0] = fmaxf(v[0] + bb[0], 0.f);
+          v[1] = fmaxf(v[1] + bb[1], 0.f);
+          v[2] = fmaxf(v[2] + bb[2], 0.f);
+          v[3] = fmaxf(v[3] + bb[3], 0.f);
+        }
       }
       if (!ok) continue;
       if constexpr ((PROBE & 16) != 0) {
@@ -642,16 +669,16 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void conv_fwd_fp8_ga_kernel(ConvFp
 // tilings, 5 = LDS-staged conv_fwd_fp8_kernel
 
 template <int BN, int MB, int NPART, bool OB, bool OF, bool DG, bool DGB, bool DGBITS, int CW, int NW, bool STGE,
-          int PROBE = 0>
-static void launch_fp8_ga_cw(const ConvFp8Args& a, hipStream_t st) {
+          int PROBE = 0, bool RES = false>
+static void launch_fp8_ga_cw(const Fp8KernArgs<RES>& a, hipStream_t st) {
   constexpr int smem = fp8_ga_red_off(BN, MB, STGE && OF, NW) + 64;  // as in the kernel
   static const hipError_t attr = hipFuncSetAttribute(
-      (const void*)conv_fwd_fp8_ga_kernel<BN, MB, NPART, OB, OF, DG, DGB, DGBITS, CW, NW, STGE, PROBE>,
+      (const void*)conv_fwd_fp8_ga_kernel<BN, MB, NPART, OB, OF, DG, DGB, DGBITS, CW, NW, STGE, PROBE, RES>,
       hipFuncAttributeMaxDynamicSharedMemorySize, smem);  // once per instantiation (thread-safe static)
   hip_check(attr, "hipFuncSetAttribute(max dynamic LDS)");
   constexpr int BM = NW * 16 * MB;
   dim3 grid((a.M + BM - 1) / BM, a.Cout / BN);
-  hipLaunchKernelGGL((conv_fwd_fp8_ga_kernel<BN, MB, NPART, OB, OF, DG, DGB, DGBITS, CW, NW, STGE, PROBE>), grid, dim3(64 * NW), smem, st,
+  hipLaunchKernelGGL((conv_fwd_fp8_ga_kernel<BN, MB, NPART, OB, OF, DG, DGB, DGBITS, CW, NW, STGE, PROBE, RES>), grid, dim3(64 * NW), smem, st,
                      a);
 }
 
@@ -782,7 +809,18 @@ static void launch_fp8_bn(const ConvFp8Args& a, hipStream_t st) {
   else launch_fp8_t<BN, false, true>(a, st);
 }
 
-void launch_conv_fwd_fp8(const ConvFp8Args& a_in, hipStream_t st) {
+#ifndef AGK_KERNEL_LAB
+// The skip operand of a residual block (ConvFp8ResArgs::res): the RES instantiations of the 192-wide production
+// tile (48 px per wave, weights in 4 parts, 8 waves, staged byte outputs), forward or bitmask dgrad, with
+// the bf16 output (the residual stream) and optionally the byte output next to it
+template <bool DGBITS>
+static void launch_fp8_res(const ConvFp8ResArgs& a, hipStream_t st) {
+  if (a.y_fp8) launch_fp8_ga_cw<192, 3, 4, true, true, DGBITS, false, DGBITS, 64, 8, true, 0, true>(a, st);
+  else launch_fp8_ga_cw<192, 3, 4, true, false, DGBITS, false, DGBITS, 64, 8, true, 0, true>(a, st);
+}
+#endif
+
+void launch_conv_fwd_fp8(const ConvFp8Args& a_in, hipStream_t st, const __bf16* res) {
   ConvFp8Args a = a_in;
   a.divSS = make_fastdiv((uint32_t)(a.S * a.S));
   a.divS = make_fastdiv((uint32_t)a.S);
@@ -790,6 +828,29 @@ void launch_conv_fwd_fp8(const ConvFp8Args& a_in, hipStream_t st) {
   a.cw = cw;
   a.divCC = make_fastdiv((uint32_t)((a.Cin + cw - 1) / cw));  // chunks per tap
   a.divK = make_fastdiv((uint32_t)a.K);
+  if (res) {
+    // residual block: the skip operand selects the RES instantiations (a compile-time flag -- the kernels
+    // without it are untouched)
+#ifdef AGK_KERNEL_LAB
+    throw std::invalid_argument("conv_fwd_fp8: the kernel-lab library has no skip operand (res)");
+#else
+    const char* op = a.dgrad || a.dgrad_bf16 ? "conv_dgrad_fp8" : "conv_fwd_fp8";
+    if (a.Cout != 192 || cw != 64)
+      throw std::invalid_argument(std::string(op) + ": a skip operand (res) goes with the 192-wide tile only (got " +
+                                  std::to_string(a.Cout) + ")");
+    if (a.dgrad_bf16) throw std::invalid_argument("conv_dgrad_fp8 (bf16 operand): no skip operand (res)");
+    if (a.dgrad && !a.mbits_in) throw std::invalid_argument("conv_dgrad_fp8 (mask tensor): no skip operand (res)");
+    if (a.variant != 0) throw std::invalid_argument(std::string(op) + ": a skip operand (res): production kernel only");
+    if (!a.y_bf16)
+      throw std::invalid_argument(std::string(op) + ": a skip operand (res) needs the bf16 output (the residual stream)");
+    ConvFp8ResArgs r;
+    static_cast<ConvFp8Args&>(r) = a;
+    r.res = res;
+    if (a.dgrad) launch_fp8_res<true>(r, st);
+    else launch_fp8_res<false>(r, st);
+    return;
+#endif
+  }
   if (a.dgrad_bf16) {
     if (a.Cout == 160) launch_fp8_dgrad_bf16<160>(a, st);
     else if (a.Cout % 192 == 0) launch_fp8_dgrad_bf16<192>(a, st);

@@ -278,6 +278,15 @@ struct ConvFp8Args {
   // from (pixel, channel, *sr_seed); the trainer advances the device seed every step
   const int* sr_seed;
 };
+// ConvFp8Args plus the skip operand of a residual block: the kernel argument of the RES instantiations
+// (conv_fwd_fp8_ga_kernel).  res is a bf16 tensor of the bf16 output's shape and padding in real (unscaled)
+// units, never an output of the same launch, read at interior pixels only and added in fp32 before the
+// ReLU (forward) or the ReLU' bitmask (mbits_in dgrad); the 192-wide production tile only.  It is a struct
+// of its own because the hidden kernel arguments (gridDim) follow the explicit ones: a field added to
+// ConvFp8Args would move them, and with them one load offset in every kernel that has no skip.
+struct ConvFp8ResArgs : ConvFp8Args {
+  const __bf16* res;
+};
 
 // Kernel choices are explicit launch arguments (ConvFwdArgs::tile,
 // ConvWgradArgs::variant, ConvFp8Args::variant): no process-global state.
@@ -465,7 +474,8 @@ void launch_policy_head_d4(const PolicyHeadD4Args& a, hipStream_t st);
 void launch_group_mean(const float* v, float* out, int B, int G, hipStream_t st);
 void launch_pack_weights(const PackWeightsArgs& a, hipStream_t st);
 void launch_featurize(const FeaturizeArgs& a, hipStream_t st);
-void launch_conv_fwd_fp8(const ConvFp8Args& a, hipStream_t st);
+// res: the skip operand (ConvFp8ResArgs::res) or null
+void launch_conv_fwd_fp8(const ConvFp8Args& a, hipStream_t st, const __bf16* res = nullptr);
 void launch_pack_weights_fp8(const float* w, uint8_t* out, int Cout_real, int Cin_real, int K, int Cout_p, int Cin_p,
                              int nch, float scale, const float* scale_dev, int transposed, int cw, hipStream_t st);
 struct Fp8WeightScalesArgs {

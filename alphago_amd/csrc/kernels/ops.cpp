@@ -744,14 +744,16 @@ void featurize(const Tensor& board, const Tensor& ages, const Tensor& meta, cons
   launch_check("featurize");
 }
 
-// x: (B, HPi, HPi, Cin) uint8 (e4m3); w: (nch, Cout, 64) uint8; scales int32[2]; out_scale f32[1]
+// x: (B, HPi, HPi, Cin) uint8 (e4m3); w: (nch, Cout, 64) uint8; scales int32[2]; out_scale f32[1];
+// res (optional, Cout 192, with y_bf16): the skip operand of a residual block, y = relu(acc + bias + res)
 void conv_fwd_fp8(const Tensor& x, const Tensor& w, const Tensor& bias, const Tensor& scales, const Tensor& out_scale,
                   const c10::optional<Tensor>& amax, const c10::optional<Tensor>& y_bf16,
                   const c10::optional<Tensor>& y_fp8, int64_t K, int64_t S, int64_t Pin, int64_t Po,
-                  const c10::optional<Tensor>& mbits, const c10::optional<Tensor>& sr_seed) {
-  check_dev("conv_fwd_fp8", x, w, bias, scales, out_scale, amax, y_bf16, y_fp8, mbits, sr_seed);
+                  const c10::optional<Tensor>& mbits, const c10::optional<Tensor>& sr_seed,
+                  const c10::optional<Tensor>& res) {
+  check_dev("conv_fwd_fp8", x, w, bias, scales, out_scale, amax, y_bf16, y_fp8, mbits, sr_seed, res);
   conv_fwd_fp8_impl(x, w, bias, scales, out_scale, amax, y_bf16, y_fp8, K, S, Pin, Po, 0, c10::nullopt, mbits,
-                    sr_seed);
+                    sr_seed, res);
 }
 
 // fp8 dgrad: dx = conv(dz (e5m2, scales[0]), flipped/transposed e4m3 weights (scales[1])) masked
@@ -765,8 +767,8 @@ void conv_dgrad_fp8(const Tensor& dz8, const Tensor& w, const Tensor& mask, cons
 
 void conv_dgrad_fp8_bits(const Tensor& dz8, const Tensor& w8t, const Tensor& mbits, const Tensor& scales,
                          const Tensor& out_scale, const c10::optional<Tensor>& amax, const c10::optional<Tensor>& y_bf16,
-                         const c10::optional<Tensor>& y_fp8, int64_t K, int64_t S) {
-  conv_dgrad_fp8_bits_impl(dz8, w8t, mbits, scales, out_scale, amax, y_bf16, y_fp8, K, S);
+                         const c10::optional<Tensor>& y_fp8, int64_t K, int64_t S, const c10::optional<Tensor>& res) {
+  conv_dgrad_fp8_bits_impl(dz8, w8t, mbits, scales, out_scale, amax, y_bf16, y_fp8, K, S, res);
 }
 
 void conv_dgrad_fp8_bf16(const Tensor& dz, const Tensor& w8t, const Tensor& mbits, const Tensor& scales,
@@ -1222,14 +1224,14 @@ TORCH_LIBRARY(alphago_amd, m) {
   m.def(
       "conv_fwd_fp8(Tensor x, Tensor w, Tensor bias, Tensor scales, Tensor out_scale, Tensor(a!)? amax, "
       "Tensor(b!)? y_bf16, Tensor(c!)? y_fp8, int K, int S, int Pin, int Po, Tensor(d!)? mbits=None, "
-      "Tensor? sr_seed=None) -> ()");
+      "Tensor? sr_seed=None, Tensor? res=None) -> ()");
   m.def("pack_weights_fp8(Tensor w, Tensor(a!) out, float scale, Tensor? scale_dev, bool transposed=False) -> ()");
   m.def("pack_weights_fp8_multi(Tensor[] ws, Tensor(a!)[] outs, Tensor scales, int[] layer, int[] transposed) -> ()");
   m.def("absmax_bf16(Tensor x, Tensor(a!) amax, Tensor scale_any) -> ()");
   m.def("conv_dgrad_fp8_bf16(Tensor dz, Tensor w8t, Tensor mbits, Tensor scales, Tensor in_scale, Tensor(a!)? amax, "
         "Tensor(b!) dx, int K, int S) -> ()");
   m.def("conv_dgrad_fp8_bits(Tensor dz8, Tensor w8t, Tensor mbits, Tensor scales, Tensor out_scale, Tensor(a!)? amax, "
-        "Tensor(b!)? y_bf16, Tensor(c!)? y_fp8, int K, int S) -> ()");
+        "Tensor(b!)? y_bf16, Tensor(c!)? y_fp8, int K, int S, Tensor? res=None) -> ()");
   m.def("conv_dgrad_fp8(Tensor dz8, Tensor w, Tensor mask, Tensor scales, Tensor out_scale, Tensor(a!)? amax, "
         "Tensor(b!) y_bf16, Tensor(c!)? y_fp8, int K, int S) -> ()");
   m.def("fp8_grad_scales(Tensor(a!) amax, Tensor(b!) gscales8, Tensor(c!) gosc, int margin) -> ()");

@@ -267,14 +267,34 @@ inline int fp8_check_chunks(const Tensor& w, int64_t K, int64_t C, const char* w
   return (int)cw;
 }
 
+// The skip operand of a residual block for the fp8 forward and bitmask dgrad: bf16, contiguous, the bf16
+// output's shape (the residual stream stays in bf16, so that output must be there), no output of the launch,
+// and the 192-wide tile
+inline const __bf16* fp8_check_res(const char* op, const Tensor& res, const c10::optional<Tensor>& y_bf16,
+                                   const c10::optional<Tensor>& y_fp8, int64_t Cout) {
+  CHECK_DEV(res);
+  TORCH_CHECK(res.scalar_type() == at::kBFloat16 && res.is_contiguous(), op, ": res must be a contiguous bf16 tensor");
+  TORCH_CHECK(y_bf16.has_value(), op, ": res needs the bf16 output (the residual stream is kept in bf16)");
+  TORCH_CHECK(Cout == 192, op, ": res goes with the 192-wide tile only (got ", Cout, " channels)");
+  TORCH_CHECK(res.sizes() == y_bf16->sizes(), op, ": res must have y_bf16's shape (padded NHWC, output pad)");
+  TORCH_CHECK(res.data_ptr() != y_bf16->data_ptr() && (!y_fp8.has_value() || res.data_ptr() != y_fp8->data_ptr()),
+              op, ": res must not alias an output");
+  const char* r0 = static_cast<const char*>(res.data_ptr());
+  const char* y0 = static_cast<const char*>(y_bf16->data_ptr());
+  const int64_t nbytes = res.numel() * 2;
+  TORCH_CHECK(r0 + nbytes <= y0 || y0 + nbytes <= r0, op, ": res must not alias an output");
+  return bfp(res);
+}
+
 inline void conv_fwd_fp8_impl(const Tensor& x, const Tensor& w, const Tensor& bias, const Tensor& scales,
                               const Tensor& out_scale, const c10::optional<Tensor>& amax,
                               const c10::optional<Tensor>& y_bf16, const c10::optional<Tensor>& y_fp8, int64_t K,
                               int64_t S, int64_t Pin, int64_t Po, int variant,
                               const c10::optional<Tensor>& dgrad_mask = c10::nullopt,
                               const c10::optional<Tensor>& mbits = c10::nullopt,
-                              const c10::optional<Tensor>& sr_seed = c10::nullopt) {
-  check_dev("conv_fwd_fp8_impl", x, w, bias, scales, out_scale, amax, y_bf16, y_fp8, dgrad_mask, mbits, sr_seed);
+                              const c10::optional<Tensor>& sr_seed = c10::nullopt,
+                              const c10::optional<Tensor>& res = c10::nullopt) {
+  check_dev("conv_fwd_fp8_impl", x, w, bias, scales, out_scale, amax, y_bf16, y_fp8, dgrad_mask, mbits, sr_seed, res);
   // dgrad_mask given: fp8 dgrad (x = e5m2 gradients, w = transposed e4m3 weights, output masked
   // by dgrad_mask > 0, no bias, e5m2 y_fp8)
   CHECK_DEV(x); CHECK_DEV(w); CHECK_CONTIG(x); CHECK_CONTIG(w);
@@ -331,21 +351,28 @@ inline void conv_fwd_fp8_impl(const Tensor& x, const Tensor& w, const Tensor& bi
     TORCH_CHECK(mbits->numel() >= B * HPo * HPo * words, "mbits too small: need B*HPo*HPo*words");
     a.mbits_out = reinterpret_cast<uint32_t*>(mbits->data_ptr<int>());
   }
+  const __bf16* skip = nullptr;
+  if (res.has_value()) {  // residual block: the skip operand, added before the ReLU
+    TORCH_CHECK(!dgrad_mask.has_value(), "conv_dgrad_fp8: no skip operand (res) in the mask-tensor dgrad");
+    TORCH_CHECK(variant == 0, "conv_fwd_fp8: res: not in the kernel-lab variants");
+    skip = fp8_check_res("conv_fwd_fp8", *res, y_bf16, y_fp8, Cout);
+  }
   TORCH_CHECK(B * HPi * HPi * Cin < (1ll << 31), "tensor too large for int32 offsets");
   if (a.M == 0) return;
-  agk::launch_conv_fwd_fp8(a, cur_stream());
+  agk::launch_conv_fwd_fp8(a, cur_stream(), skip);
   launch_check("conv_fwd_fp8");
 }
 
 // fp8 dgrad of the all-fp8 backward (160-wide value and 192-wide policy trunks): dz8 e5m2
 // (B, HP, HP, C), C = 160 or 192 (MFMA scale scales[0]), w8t the transposed flipped e4m3 weights
 // (scales[1]), ReLU' from the forward's bitmask; outputs y_fp8 (e5m2 of dx * out_scale[0]) and/or
-// y_bf16; amax (optional) accumulates max |dx|
+// y_bf16; amax (optional) accumulates max |dx|; res (optional, 192 wide, with y_bf16): the skip gradient of a
+// residual block, dx = bit ? acc + res : 0
 inline void conv_dgrad_fp8_bits_impl(const Tensor& dz8, const Tensor& w8t, const Tensor& mbits, const Tensor& scales,
                                      const Tensor& out_scale, const c10::optional<Tensor>& amax,
                                      const c10::optional<Tensor>& y_bf16, const c10::optional<Tensor>& y_fp8,
-                                     int64_t K, int64_t S) {
-  check_dev("conv_dgrad_fp8_bits", dz8, w8t, mbits, scales, out_scale, amax, y_bf16, y_fp8);
+                                     int64_t K, int64_t S, const c10::optional<Tensor>& res = c10::nullopt) {
+  check_dev("conv_dgrad_fp8_bits", dz8, w8t, mbits, scales, out_scale, amax, y_bf16, y_fp8, res);
   CHECK_DEV(dz8); CHECK_DEV(w8t); CHECK_DEV(mbits); CHECK_CONTIG(dz8); CHECK_CONTIG(w8t); CHECK_CONTIG(mbits);
   TORCH_CHECK(dz8.scalar_type() == at::kByte && w8t.scalar_type() == at::kByte, "fp8 tensors are stored as uint8");
   TORCH_CHECK(dz8.dim() == 4 && w8t.dim() == 3, "dz8 (B, HP, HP, C), w8t (nch, C, cw)");
@@ -382,9 +409,11 @@ inline void conv_dgrad_fp8_bits_impl(const Tensor& dz8, const Tensor& w8t, const
   a.HPi = (int)HP; a.offi = (int)(1 - K / 2); a.HPo = (int)HP; a.Po = 1; a.nch = (int)nch; a.cw = cw;
   a.dgrad = 1;
   a.mbits_in = reinterpret_cast<const uint32_t*>(mbits.data_ptr<int>());
+  // residual block: the skip gradient, added before the ReLU' mask
+  const __bf16* skip = res.has_value() ? fp8_check_res("conv_dgrad_fp8_bits", *res, y_bf16, y_fp8, C) : nullptr;
   TORCH_CHECK(B * HP * HP * C < (1ll << 31), "tensor too large for int32 offsets");
   if (a.M == 0) return;
-  agk::launch_conv_fwd_fp8(a, cur_stream());
+  agk::launch_conv_fwd_fp8(a, cur_stream(), skip);
   launch_check("conv_dgrad_fp8_bits");
 }
 

@@ -31,7 +31,7 @@ call; MCTS policy/value callables (mcts.py:107-118).
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -54,6 +54,31 @@ class _Bucket:
     pass
 
 
+class Fp8LayerPlan(NamedTuple):
+    """What one layer of the fp8 trunk writes and adds (fp8_trunk_plan): indices into a bucket's buffers."""
+    y_bf16: Optional[int]  # bf16 output buffer (bk.Y) or None
+    y_fp8: Optional[int]   # e4m3 output buffer (bk.Y8) or None; layer l + 1 reads it
+    res: Optional[int]     # bf16 buffer (bk.Y) holding the skip operand of a block end, or None
+
+
+def fp8_trunk_plan(layers: int, residual: bool) -> List[Fp8LayerPlan]:
+    """Per-layer outputs and skip operand of the fp8 inference trunk (HipTrunkInference._trunk_fp8).
+
+    Every layer but the top writes e4m3 into Y8[l % 2] for the next one; the top writes bf16 only, for the
+    heads.  A plain trunk writes no other bf16.  A residual trunk keeps its stream in bf16: the even layers
+    (the stem and every block end) also write bf16, into Y[(l // 2) % 2], and a block end (even l >= 2) adds
+    the stream written two layers earlier, Y[((l - 2) // 2) % 2] -- the other buffer of the pair, so the
+    skip is never an output of its own launch, the top layer included."""
+    plan = []
+    for l in range(layers):
+        last = l == layers - 1
+        stream = residual and l % 2 == 0
+        yb = (l // 2) % 2 if stream else (0 if last else None)
+        res = ((l - 2) // 2) % 2 if stream and l >= 2 else None
+        plan.append(Fp8LayerPlan(yb, None if last else l % 2, res))
+    return plan
+
+
 class HipTrunkInference:
     """Forward-only runner of a ConvStack (+ head) on the HIP kernels."""
 
@@ -72,12 +97,14 @@ class HipTrunkInference:
             raise ValueError("precision must be bf16 or fp8")
         self.device = torch.device(device)
         tr = net.trunk
-        # residual trunk: the skip-add rides in the bf16 conv epilogue (conv_planned res=); three Y
-        # buffers in rotation instead of two, so the block input outlives the block's first layer
+        # residual trunk: the skip-add rides in the conv epilogue (conv_planned / conv_fwd_fp8 res=); three Y
+        # buffers in rotation instead of two, so the block input outlives the block's first layer.  The fp8
+        # kernels take the skip on the 192-wide tile only (fp8_trunk_plan: the stream stays bf16)
         self.residual = bool(getattr(tr, "residual", False))
-        if self.residual and self.precision == "fp8":
-            raise ValueError("a residual trunk runs in bf16 only: the fp8 conv kernels have no skip operand "
-                             "(precision=\"fp8\" argument or ALPHAGO_AMD_PRECISION=fp8)")
+        if self.residual and self.precision == "fp8" and ops.pad_filters(tr.filters) != 192:
+            raise ValueError("a residual trunk of %d filters runs in bf16 only: the fp8 conv kernels have their "
+                             "skip operand on the 192-wide tile alone (precision=\"fp8\" argument or "
+                             "ALPHAGO_AMD_PRECISION=fp8)" % tr.filters)
         self._ny = 3 if self.residual else 2
         self.S, self.L, self.K = net.board, tr.layers, list(tr.widths)
         self.C0, self.F = tr.in_planes, tr.filters
@@ -262,16 +289,19 @@ class HipTrunkInference:
     # ------------------------------------------------------------------ fp8
     def _trunk_fp8(self, bk) -> torch.Tensor:
         """e4m3 trunk on the block-scaled MFMA: every layer reads and (but the
-        last) writes e4m3 activations; the last writes bf16 for the head."""
+        last) writes e4m3 activations; the last writes bf16 for the head.  A residual trunk also keeps
+        its stream in bf16 and adds it in the block ends' epilogues (fp8_trunk_plan)."""
         ops.quantize_fp8(bk.X0, bk.X08, 0)  # 0/1 planes are exact in e4m3
         x8, pin = bk.X08, self.P0
-        for l in range(self.L):
-            last = l == self.L - 1
+        yb = None
+        for l, p in enumerate(fp8_trunk_plan(self.L, self.residual)):
+            yb = None if p.y_bf16 is None else bk.Y[p.y_bf16]
+            y8 = None if p.y_fp8 is None else bk.Y8[p.y_fp8]
             ops.conv_fwd_fp8(x8, self.w8[l], self.bias_p[l], self.scales8[l], self.osc8[l:l + 1], self.K[l], self.S,
-                             pin, 1, y_bf16=bk.Y[0] if last else None, y_fp8=None if last else bk.Y8[l % 2],
-                             amax=self.amax8[l])
-            x8, pin = bk.Y8[l % 2], 1
-        return bk.Y[0]
+                             pin, 1, y_bf16=yb, y_fp8=y8, amax=self.amax8[l],
+                             res=None if p.res is None else bk.Y[p.res])
+            x8, pin = y8, 1
+        return yb
 
     @torch.no_grad()
     def calibrate(self, bk, encoded: bool = False, margin: int = 1) -> None:

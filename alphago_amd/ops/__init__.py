@@ -765,12 +765,15 @@ def conv_dgrad_fp8(dz8, w8t, mask, scales, out_scale, K: int, S: int, y_bf16, y_
     _ops().conv_dgrad_fp8(dz8, w8t, mask, scales, out_scale, amax, y_bf16, y_fp8, K, S)
 
 
-def conv_dgrad_fp8_bits(dz8, w8t, mbits, scales, out_scale, K: int, S: int, y_bf16=None, y_fp8=None, amax=None):
+def conv_dgrad_fp8_bits(dz8, w8t, mbits, scales, out_scale, K: int, S: int, y_bf16=None, y_fp8=None, amax=None,
+                        res=None):
     """fp8 dgrad of the all-fp8 backward (160 channels: value trunk; 192: policy trunk): dz8 e5m2 (the
     copy the previous dgrad wrote for the fp8 wgrad; MFMA scale scales[0]) x the transposed flipped
     e4m3 weights (scales[1]), ReLU' from the forward's bitmask ``mbits``; writes y_fp8 =
-    e5m2(dx * out_scale[0]) and/or bf16 y_bf16; ``amax`` accumulates max |dx|.  Other widths raise."""
-    _ops().conv_dgrad_fp8_bits(dz8, w8t, mbits, scales, out_scale, amax, y_bf16, y_fp8, K, S)
+    e5m2(dx * out_scale[0]) and/or bf16 y_bf16; ``amax`` accumulates max |dx|.  Other widths raise.
+    ``res`` (192 wide, with y_bf16; bf16 of y_bf16's shape, not an output): the skip gradient of a residual
+    block in real units, dx = bit ? acc + res : 0."""
+    _ops().conv_dgrad_fp8_bits(dz8, w8t, mbits, scales, out_scale, amax, y_bf16, y_fp8, K, S, res)
 
 
 def conv_dgrad_fp8_bf16(dz, w8t, mbits, scales, in_scale, K: int, S: int, dx, amax=None):
@@ -827,11 +830,13 @@ def quantize_fp8(x_bf16: torch.Tensor, out: torch.Tensor, exponent: int):
 
 
 def conv_fwd_fp8(x8, w8, bias, scales, out_scale, K: int, S: int, Pin: int, Po: int = 1, y_bf16=None, y_fp8=None,
-                 amax=None, mbits=None, sr_seed=None):
+                 amax=None, mbits=None, sr_seed=None, res=None):
     """fp8 conv + bias + ReLU.  scales: int32 device tensor {127 - e_x, 127 - e_w} (MFMA E8M0);
     out_scale: f32 device tensor [2^e_y] for the e4m3 output; amax: int32[64] running max slots (float bits);
-    sr_seed: int32 device scalar -> the e4m3 output is stochastically rounded (training forward)."""
-    _ops().conv_fwd_fp8(x8, w8, bias, scales, out_scale, amax, y_bf16, y_fp8, K, S, Pin, Po, mbits, sr_seed)
+    sr_seed: int32 device scalar -> the e4m3 output is stochastically rounded (training forward);
+    res (Cout 192, with y_bf16; bf16 of y_bf16's shape, not an output): the skip operand of a residual block
+    in real units, y = relu(acc + bias + res), and every output follows the sum."""
+    _ops().conv_fwd_fp8(x8, w8, bias, scales, out_scale, amax, y_bf16, y_fp8, K, S, Pin, Po, mbits, sr_seed, res)
 
 
 def fp8_to_float(t_u8: torch.Tensor, exponent: int = 0) -> torch.Tensor:

@@ -282,12 +282,13 @@ class HipConvTrainer:
         if precision not in ("bf16", "fp8"):
             raise ValueError("precision must be bf16 or fp8")
         self.precision = precision
-        # residual trunk (ConvStack residual=True): the skip-add is fused into the bf16 conv epilogues --
-        # forward of an even layer l >= 2 adds Y[l-2], dgrad of an odd layer l adds DZ[l+1]
+        # residual trunk (ConvStack residual=True): the skip-add is fused into the conv epilogues --
+        # forward of an even layer l >= 2 adds Y[l-2], dgrad of an odd layer l adds DZ[l+1].  The fp8 kernels
+        # take the skip on the 192-wide tile only; the residual stream (Y and DZ of the even layers) stays bf16
         self.residual = bool(getattr(net.trunk, "residual", False))
-        if self.residual and precision == "fp8":
-            raise ValueError("a residual trunk trains in bf16 only: the fp8 conv kernels have no skip operand "
-                             "(precision=\"fp8\")")
+        if self.residual and precision == "fp8" and ops.pad_filters(net.trunk.filters) != 192:
+            raise ValueError("a residual trunk of %d filters trains in bf16 only: the fp8 conv kernels have their "
+                             "skip operand on the 192-wide tile alone (precision=\"fp8\")" % net.trunk.filters)
         if self.residual and self.lab_tile:
             raise ValueError("a residual trunk cannot run on a kernel-lab tiling: the kernel-lab library has no "
                              "skip operand (ALPHAGO_AMD_LAB_TILE=%d)" % self.lab_tile)
@@ -523,6 +524,13 @@ class HipConvTrainer:
         if fp8_dgrad is None:
             fp8_dgrad = self.fp8_wgrad and self.Fp == 160 and os.environ.get("ALPHAGO_AMD_FP8_DGRAD", "1") == "1"
         self.fp8_dgrad = bool(fp8_dgrad)
+        if self.residual and (self.fp8_dgrad != self.fp8_wgrad or self.fp8_bf16_layers):
+            # conv_dgrad_bits_bf8 and conv_dgrad_fp8_bf16 (the mixed arms and the per-layer bf16 fallback) have no
+            # skip operand
+            raise ValueError("a residual fp8 trunk has two backward arms: the bf16 backward (fp8_dgrad=False, "
+                             "fp8_wgrad=False, the default) and the all-fp8 backward (fp8_dgrad=True, "
+                             "fp8_wgrad=True), both without fp8_bf16_layers; got fp8_dgrad=%s, fp8_wgrad=%s, "
+                             "fp8_bf16_layers=%s" % (self.fp8_dgrad, self.fp8_wgrad, sorted(self.fp8_bf16_layers)))
         if self.fp8_wgrad:
             self.X8 = [None] + [torch.zeros(self.Y[0].shape, dtype=torch.uint8, device=dev) for _ in range(1, L)]
             self.DZ8 = [None] + [torch.zeros(self.DZ[0].shape, dtype=torch.uint8, device=dev) for _ in range(1, L)]
@@ -597,7 +605,7 @@ class HipConvTrainer:
         """The fp8 backward reads only the e5m2 copy of the head's dZ (fp8 wgrad and dgrad of the top
         layer, scales calibrated), so a head can write that copy directly."""
         return (self.precision == "fp8" and self.fp8_wgrad and self.fp8_dgrad and self._g8_calibrated
-                and (self.L - 1) in self._w8layers)
+                and (self.L - 1) in self._w8layers and not self.residual)  # residual: dZ[L-1] is a bf16 skip too
 
     def _layer_in(self, l):
         return (self.X0, self.P0) if l == 0 else (self.Y[l - 1], 1)
@@ -643,10 +651,14 @@ class HipConvTrainer:
                 if y8 is not None:
                     ops.quantize_fp8_dev(self.Y[l], y8, self.osc8[l:l + 1], self.amax8[l])
             else:
-                keep_bf16 = last or nxt_bf or not e4m3_only
+                # residual trunk: the stream (the stem's and every block end's output) is kept in bf16 next to
+                # its e4m3 copy, and a block end adds the stream of two layers below before its ReLU
+                stream = self.residual and l % 2 == 0
+                keep_bf16 = last or nxt_bf or not e4m3_only or stream
                 ops.conv_fwd_fp8(x8, self.w8[l], self.bias_p[l], self.scales8[l], self.osc8[l:l + 1], self.K[l],
                                  self.S, pin, 1, y_bf16=self.Y[l] if keep_bf16 else None, y_fp8=y8,
-                                 amax=self.amax8[l], mbits=None if last else self.MBITS[l], sr_seed=sr)
+                                 amax=self.amax8[l], mbits=None if last else self.MBITS[l], sr_seed=sr,
+                                 res=self.Y[l - 2] if stream and l >= 2 else None)
             x8, pin = y8, 1
         if sr is not None:
             self._sr_seed.add_(1)
@@ -733,11 +745,15 @@ class HipConvTrainer:
             # the output goes out as e5m2 (wgrad(l-1) and dgrad(l-1) read it) and as bf16 only
             # for the first layer's bf16 wgrad; its max |dx| comes from wgrad(l-1)'s bytes
             f8out = l - 1 in self._w8layers
+            # residual trunk, odd l (a block's first layer): the skip gradient DZ[l+1] joins before ReLU', and
+            # DZ[l-1] goes out in bf16 as well -- it is the skip gradient of the block below
+            skip = self.residual and l % 2 == 1
             ops.conv_dgrad_fp8_bits(self.DZ8[l], self.wd8[l], self.MBITS[l - 1], self.gscales8[l],
                                     self.gosc8[l - 1:l], self.K[l], self.S,
-                                    y_bf16=None if f8out else self.DZ[l - 1],
+                                    y_bf16=None if f8out and not skip else self.DZ[l - 1],
                                     y_fp8=self.DZ8[l - 1] if f8out else None,
-                                    amax=None if f8out else self.gamax8[l - 1])
+                                    amax=None if f8out else self.gamax8[l - 1],
+                                    res=self.DZ[l + 1] if skip else None)
         elif w8 and l - 1 in self._w8layers:  # bitmask dgrad + the e5m2 copy wgrad(l-1) reads
             ops.conv_dgrad_bits_bf8(self.DZ[l], self.wd[l], self.DZ[l - 1], self.MBITS[l - 1],
                                     self.DZ8[l - 1], self.gosc8[l - 1:l], self.K[l], self.S,

@@ -45,8 +45,18 @@ _KEYS = ("loss", "acc", "value_loss", "value_acc")
 _OWN_KEYS = ("own_loss", "own_acc")
 
 
+class _PVParser(argparse.ArgumentParser):
+    """train-pv's parser: flag combinations that cannot run are parse errors."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        if getattr(ns, "fp8_backward", False) and ns.precision != "fp8":
+            self.error("--fp8-backward requires --precision fp8")
+        return ns, rest
+
+
 def _parser():
-    p = argparse.ArgumentParser(
+    p = _PVParser(
         prog="alphago_amd train-pv",
         description="Train a dual policy+value network on selfplay-mcts records (states, pi, outcomes).  "
                     "Checkpoint/resume and the watchdog are out of scope: --weights restarts from a weights "
@@ -68,7 +78,12 @@ def _parser():
     p.add_argument("--train-val-test", nargs=3, type=float, default=[0.93, .05, .02])
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--backend", default="auto", choices=["auto", "hip", "torch"])
-    p.add_argument("--precision", default="bf16", choices=["bf16", "fp8"], help="HIP backend conv forward precision")
+    p.add_argument("--precision", default="bf16", choices=["bf16", "fp8"],
+                   help="HIP backend conv forward precision (fp8: e4m3 block-scaled MFMA forward, bf16 backward "
+                        "unless --fp8-backward; a residual trunk needs 192 filters for it)")
+    p.add_argument("--fp8-backward", action="store_true",
+                   help="with --precision fp8: all-fp8 trunk backward (e5m2 x e4m3 wgrad and dgrad on the 3x3 "
+                        "layers above the first; 192-wide trunks)")
     p.add_argument("--metrics", default=None, help="JSONL metrics file (per-epoch records)")
     p.add_argument("--weights", default=None, help="weights file (in out_directory) to start from")
     p.add_argument("--verbose", "-v", default=False, action="store_true")
@@ -79,6 +94,18 @@ def _pad(t: torch.Tensor, B: int, fill) -> torch.Tensor:
     if t.shape[0] == B:
         return t
     return torch.cat([t, torch.full((B - t.shape[0],) + tuple(t.shape[1:]), fill, dtype=t.dtype, device=t.device)])
+
+
+def trainer_kwargs(args, ownership: bool) -> dict:
+    """The keyword arguments make_policy_value_trainer gets for the parsed command line."""
+    kw = {"value_coef": args.value_coef}
+    if ownership:
+        kw["own_coef"] = args.ownership_coef
+    if args.precision != "bf16":
+        kw["precision"] = args.precision
+    if args.fp8_backward:
+        kw.update(fp8_wgrad=True, fp8_dgrad=True)
+    return kw
 
 
 def run_training(cmd_line_args: Optional[List[str]] = None):
@@ -131,11 +158,7 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
         meta.metadata.update(ownership_coef=args.ownership_coef)
 
     B = args.minibatch
-    kw = {"value_coef": args.value_coef}
-    if own is not None:
-        kw["own_coef"] = args.ownership_coef
-    if args.precision != "bf16":
-        kw["precision"] = args.precision
+    kw = trainer_kwargs(args, own is not None)
     trainer = make_policy_value_trainer(net, B, args.learning_rate, args.decay, backend=args.backend, device=dev, **kw)
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed * 1000 + rank)

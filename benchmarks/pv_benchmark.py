@@ -14,6 +14,10 @@
          twice); (b) the whole training step of the dual net with the head against the same net
          without it.  Prints the byte counts of one pass over the trunk output next to the times.
 
+  --precision A[,B...] with train / leaf: the dual net alone in each named arm (bf16, fp8, and for train
+         fp8-backward = the all-fp8 step), the arms alternating inside the process; --layers and --residual
+         pick its trunk (e.g. train --layers 21 --residual --precision bf16,fp8,fp8-backward)
+
 Every timed window is warmed up first and ends in a device synchronise (or the batch's own event);
 the two sides alternate inside one process and every figure is the median of ``--repeats`` windows,
 printed with their min and max.  Prints one JSON line.
@@ -107,6 +111,51 @@ def bench_genmove(pol, val, pv, n_pos, playouts, leaves):
             lat[name].append((time.perf_counter() - t) * 1e3)
     return {k + "_ms": {"p50": round(float(np.percentile(v, 50)), 2), "p95": round(float(np.percentile(v, 95)), 2)}
             for k, v in lat.items()} | {"positions": n_pos, "playouts": playouts, "leaves": leaves}
+
+
+ARM_KW = {"bf16": {}, "fp8": {"precision": "fp8"},
+          "fp8-backward": {"precision": "fp8", "fp8_dgrad": True, "fp8_wgrad": True}}
+
+
+def bench_train_arms(dev, B, steps, repeats, arms, layers, residual):
+    """The dual trainer's step in each arm of ARM_KW, alternating."""
+    from alphago_amd.models.nets import PolicyValueNet
+    from alphago_amd.train.engine import HipPolicyValueTrainer
+
+    g = torch.Generator().manual_seed(0)
+    moves = torch.randint(0, 361, (B,), dtype=torch.int32, generator=g).to(dev)
+    z = (torch.randint(0, 2, (B,), generator=g) * 2 - 1).float().to(dev)
+    sym = torch.randint(0, 8, (B,), dtype=torch.int32, generator=g).to(dev)
+    x49 = torch.randint(0, 2, (B, 49, 19, 19), dtype=torch.uint8, generator=g).to(dev)
+    sides = {}
+    for arm in arms:
+        torch.manual_seed(0)
+        t = HipPolicyValueTrainer(PolicyValueNet(49, 19, 192, layers, residual=int(residual)), B, lr=0.003,
+                                  device=dev, **ARM_KW[arm])
+        sides[arm] = lambda t=t: t.step(x49, (moves, z), sym)
+    res = _alternate(sides, 3, steps, repeats)
+    return {"B": B, "layers": layers, "residual": bool(residual)} | {k + "_step_ms": spread(v) for k, v in res.items()}
+
+
+def bench_leaf_arms(dev, B, iters, repeats, arms, layers, residual):
+    """One encoded leaf-batch evaluation of the dual engine in each precision, alternating."""
+    base = positions(min(B, 64), 1)
+    states = [base[i % len(base)] for i in range(B)]
+    engines = {}
+    for arm in arms:
+        torch.manual_seed(0)
+        os.environ["ALPHAGO_AMD_PRECISION"] = arm  # read when the engine is made
+        engines[arm] = CNNPolicyValue(VALUE_FEATURES, filters_per_layer=192, layers=layers, device=dev,
+                                      **({"residual": 1} if residual else {})).engine
+    enc = native().encode_batch(states, any(e.needs_ladder for e in engines.values()), 16)
+    enc = [torch.as_tensor(np.ascontiguousarray(e)).pin_memory() if e is not None else None for e in enc]
+    sides = {arm: (lambda e=e: e.collect(e.submit_encoded(*enc, to_host=True))) for arm, e in engines.items()}
+    res = _alternate(sides, 10, iters, repeats)
+    out = {"B": B, "layers": layers, "residual": bool(residual)}
+    for k, v in res.items():
+        out[k + "_ms"] = spread(v)
+        out[k + "_evals_per_s"] = round(B / (float(np.median(v)) * 1e-3), 1)
+    return out
 
 
 def bench_train(dev, B, steps, repeats, only=None):
@@ -239,10 +288,30 @@ def main():
     ap.add_argument("--train-only", choices=["policy", "dual"], default=None, help="one trainer only (kernel traces)")
     ap.add_argument("--own-only", choices=["fused", "unfused", "step"], default=None,
                     help="own: one arm only (kernel traces)")
+    ap.add_argument("--precision", default=None,
+                    help="train / leaf: the dual net alone in these arms, joined with commas: bf16, fp8, "
+                         "fp8-backward (train only)")
+    ap.add_argument("--layers", type=int, default=12, help="with --precision: trunk layers of the dual net")
+    ap.add_argument("--residual", action="store_true", help="with --precision: a residual trunk (odd --layers)")
+    ap.add_argument("--leaf-batch", type=int, default=1024, help="with --precision: boards per leaf batch")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("pv_benchmark measures on a GPU")
     dev = torch.device("cuda")
+    if a.precision is not None:
+        arms = a.precision.split(",")
+        if any(x not in ARM_KW for x in arms):
+            ap.error("--precision arms: " + ", ".join(ARM_KW))
+        out = {"arms": arms}
+        if "train" in a.what:
+            out["train"] = bench_train_arms(dev, a.train_batch, a.train_steps, a.repeats, arms, a.layers, a.residual)
+        if "leaf" in a.what:
+            out["leaf"] = bench_leaf_arms(dev, a.leaf_batch, 200 if a.leaf_batch <= 64 else 30, a.repeats,
+                                          [x for x in arms if x != "fp8-backward"], a.layers, a.residual)
+        print(json.dumps(out))
+        return
+    if a.residual or a.layers != 12:
+        ap.error("--layers / --residual go with --precision")
     out = {"precision": os.environ.get("ALPHAGO_AMD_PRECISION", "bf16")}
     if "leaf" in a.what or "genmove" in a.what:
         torch.manual_seed(0)

@@ -7,7 +7,12 @@ assembly files, and pairs their kernels by position within each kernel family (t
 Per kernel it prints the demangled name, a digest of the body and the register / LDS metadata.
 
 The digest is taken over the body with the kernel's own symbol masked, the `.LBB<n>_` label prefix
-renumbered per kernel and `__hip_cuid` lines dropped, so a renamed template argument does not show.
+renumbered per kernel (in the loop comments too) and `__hip_cuid` lines dropped, so a renamed template
+argument or a kernel added earlier in the file does not show.
+
+--added REGEX: kernels of the NEW side whose demangled name matches are new instantiations of an old
+template (a compile-time flag such as the fp8 skip operand).  They are taken out of the pairing and
+listed with their metadata after the families; every other kernel must still pair.
 
 Every pair is classified:
   A  the digests are equal;
@@ -62,8 +67,9 @@ def digest(sym, body):
         if "__hip_cuid" in ln:
             continue
         ln = ln.replace(sym, "<kernel>")
-        ln = re.sub(r"\.LBB\d+_", ".LBB_", ln)
+        ln = re.sub(r"BB\d+_", "BB_", ln)  # labels (.LBB<n>_) and the loop comments that name them (BB<n>_)
         ln = re.sub(r"\.Lfunc_end\d+", ".Lfunc_end", ln)
+        ln = re.sub(r"\s+;", " ;", ln)  # a comment's column moves with the digits of the label before it
         lines.append(ln.rstrip())
     return hashlib.sha256("\n".join(lines).encode()).hexdigest()[:16]
 
@@ -77,6 +83,14 @@ def kernarg_sizes(text):
 def family(dem):
     m = re.match(r"(?:void )?(?:\w+::)*(\w+)", dem)
     return m.group(1) if m else dem
+
+
+def split_added(rows, pattern):
+    """(rows to pair, rows whose demangled name matches pattern)"""
+    if not pattern:
+        return rows, []
+    rx = re.compile(pattern)
+    return [r for r in rows if not rx.search(r[1])], [r for r in rows if rx.search(r[1])]
 
 
 def load(text):
@@ -174,14 +188,19 @@ def main() -> int:
     ap.add_argument("--out", default="", help="write the listing here instead of standard output")
     ap.add_argument("--keep", default="", help="keep the assembly files in this directory")
     ap.add_argument("--brief", action="store_true", help="one line per family; kernels are listed only outside class A")
+    ap.add_argument("--added", default="", help="regular expression over demangled names: kernels of NEW that OLD "
+                    "does not have (listed apart, not paired)")
     args = ap.parse_args()
     if args.keep:
         os.makedirs(args.keep, exist_ok=True)
     sources = args.sources.split(",") if args.sources else SOURCES[args.flavor]
     old = [r for t in asm_of(args.old, args.flavor, args.keep, "old", sources) for r in load(t)]
     new = [r for t in asm_of(args.new, args.flavor, args.keep, "new", sources) for r in load(t)]
+    new, added = split_added(new, args.added)
     out = open(args.out, "w") if args.out else sys.stdout
     print("isa_compare %s build: %d / %d kernels" % (args.flavor, len(old), len(new)), file=out)
+    for r in added:
+        print("  added %s  %s | %s" % (r[2], " ".join("%s=%d" % (k, r[3].get(k, -1)) for k in META), r[1]), file=out)
     ok = compare(old, new, out, args.brief)
     if args.out:
         out.close()
