@@ -95,7 +95,12 @@ def _init_model(argv):
     p.add_argument("--ownership", action="store_true",
                    help="pv only: a third 1x1 head predicting each point's owner at the end of the game "
                         "(trained by train-pv on selfplay-mcts --ownership records)")
+    p.add_argument("--gpool", type=int, default=0, metavar="K",
+                   help="pv --residual only: a global pooling branch (mean and max over the board -> dense -> "
+                        "per-channel bias on the block's skip) in every K-th residual block")
     a = p.parse_args(argv)
+    if a.gpool and not (a.kind == "pv" and a.residual):
+        p.error("--gpool needs a residual dual net (init-model pv --residual --gpool K)")
     if a.residual and a.kind != "pv":
         p.error("--residual needs the dual net (init-model pv): a Keras Sequential cannot express a skip connection")
     if a.ownership and a.kind != "pv":
@@ -111,6 +116,8 @@ def _init_model(argv):
         kw = {"residual": 1} if a.residual else {}
         if a.ownership:
             kw["ownership"] = 1
+        if a.gpool:
+            kw["gpool"] = a.gpool
         try:
             m = CNNPolicyValue(feats, board=a.board, filters_per_layer=a.filters or 192, layers=a.layers,
                                device="cpu", **kw)

@@ -473,6 +473,30 @@ void launch_policy_head_d4(const PolicyHeadD4Args& a, hipStream_t st);
 // out[b] = (v[b] + v[B + b] + ... + v[(G - 1) B + b]) * (1 / G), fp32 in g order
 void launch_group_mean(const float* v, float* out, int B, int G, hipStream_t st);
 void launch_pack_weights(const PackWeightsArgs& a, hipStream_t st);
+
+// Global pooling branch of the residual trunk (gpool.hip).  Activations are padded NHWC bf16 (P = 1, C a
+// multiple of 8); only interior pixels are read or written.
+struct GpoolFwdArgs {
+  const __bf16* y;   // [B][S+2][S+2][C]
+  float* pooled;     // argmax given: [B][2][C] {sum * inv, max}; argmax null (sum mode): [B][C] sum * inv
+  int* argmax;       // [B][C] lowest pixel index r * S + col attaining the maximum, or null
+  int B, S, C;
+  float inv;         // float32(1 / (S * S)) for the mean; 1 for a plain sum
+  long long y_elems; // tensor extent (debug-build bounds checks)
+};
+void launch_gpool_fwd(const GpoolFwdArgs& a, hipStream_t st);
+struct GpoolMapArgs {
+  const __bf16* skip;  // bias add: [B][S+2][S+2][C] (may be out); fill: unused
+  const float* g;      // bias add: [B][C]; fill: dp [B][2][C]
+  const int* argmax;   // fill: [B][C]
+  __bf16* out;         // [B][S+2][S+2][C]
+  int B, S, C;
+  float inv;           // fill: float32(1 / (S * S))
+  long long elems;     // extent of skip and out (debug-build bounds checks)
+};
+// fill = false: out = bf16(float(skip) + g[b][c]); true: out = bf16(dp[b][0][c] * inv + (p == argmax[b][c] ?
+// dp[b][1][c] : 0)), product and sum rounded separately
+void launch_gpool_map(const GpoolMapArgs& a, bool fill, hipStream_t st);
 void launch_featurize(const FeaturizeArgs& a, hipStream_t st);
 // res: the skip operand (ConvFp8ResArgs::res) or null
 void launch_conv_fwd_fp8(const ConvFp8Args& a, hipStream_t st, const __bf16* res = nullptr);

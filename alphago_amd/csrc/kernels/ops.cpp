@@ -1137,6 +1137,85 @@ void dense_f32(const Tensor& A, const Tensor& B, const c10::optional<Tensor>& bi
   launch_check("dense_f32");
 }
 
+// ---- global pooling branch (gpool.hip)
+// (B, S + 2, S + 2, C) bf16, contiguous, C % 8 == 0, 16-byte aligned; returns B
+static int64_t gpool_check_act(const char* op, const Tensor& t, int64_t S) {
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.is_contiguous() && t.dim() == 4, op,
+              ": activations must be contiguous bfloat16 (B, S + 2, S + 2, C)");
+  TORCH_CHECK(S >= 1 && t.size(1) == S + 2 && t.size(2) == S + 2, op, ": boards must be S + 2 = ", S + 2, " on a side");
+  TORCH_CHECK(t.size(0) >= 1 && t.size(3) % 8 == 0 && t.size(3) >= 8 && t.size(3) <= 512, op,
+              ": B >= 1 and C a multiple of 8 in 8..512");
+  TORCH_CHECK(t.numel() < (1ll << 31), op, ": tensor too large for int32 offsets");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": activations must be 16-byte aligned");
+  return t.size(0);
+}
+
+void gpool_fwd(const Tensor& y, const Tensor& pooled, const c10::optional<Tensor>& argmax, int64_t S, double inv) {
+  check_dev("gpool_fwd", y, pooled, argmax);
+  const int64_t B = gpool_check_act("gpool_fwd", y, S), C = y.size(3);
+  TORCH_CHECK(pooled.scalar_type() == at::kFloat && pooled.is_contiguous(), "gpool_fwd: pooled must be contiguous float32");
+  agk::GpoolFwdArgs a{};
+  if (argmax.has_value()) {
+    TORCH_CHECK(pooled.dim() == 3 && pooled.size(0) == B && pooled.size(1) == 2 && pooled.size(2) == C,
+                "gpool_fwd: pooled must be (B, 2, C) = (", B, ", 2, ", C, ")");
+    TORCH_CHECK(argmax->scalar_type() == at::kInt && argmax->is_contiguous() && argmax->dim() == 2 &&
+                    argmax->size(0) == B && argmax->size(1) == C,
+                "gpool_fwd: argmax must be contiguous int32 (B, C) = (", B, ", ", C, ")");
+    a.argmax = argmax->data_ptr<int>();
+  } else {
+    TORCH_CHECK(pooled.dim() == 2 && pooled.size(0) == B && pooled.size(1) == C,
+                "gpool_fwd: the sum mode's output must be (B, C) = (", B, ", ", C, ")");
+  }
+  a.y = bfp(y);
+  a.pooled = pooled.data_ptr<float>();
+  a.B = (int)B; a.S = (int)S; a.C = (int)C;
+  a.inv = (float)inv;
+  a.y_elems = y.numel();
+  agk::launch_gpool_fwd(a, cur_stream());
+  launch_check("gpool_fwd");
+}
+
+void gpool_bias_add(const Tensor& skip, const Tensor& g, const Tensor& out, int64_t S) {
+  check_dev("gpool_bias_add", skip, g, out);
+  const int64_t B = gpool_check_act("gpool_bias_add", skip, S), C = skip.size(3);
+  gpool_check_act("gpool_bias_add", out, S);
+  TORCH_CHECK(out.sizes() == skip.sizes(), "gpool_bias_add: out must have skip's shape");
+  TORCH_CHECK(g.scalar_type() == at::kFloat && g.is_contiguous() && g.dim() == 2 && g.size(0) == B && g.size(1) == C,
+              "gpool_bias_add: g must be contiguous float32 (B, C) = (", B, ", ", C, ")");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 == 0, "gpool_bias_add: g must be 16-byte aligned");
+  agk::GpoolMapArgs a{};
+  a.skip = bfp(skip);
+  a.g = g.data_ptr<float>();
+  a.out = bfp_mut(out);
+  a.B = (int)B; a.S = (int)S; a.C = (int)C;
+  a.elems = out.numel();
+  agk::launch_gpool_map(a, false, cur_stream());
+  launch_check("gpool_bias_add");
+}
+
+void gpool_bwd_fill(const Tensor& dp, const Tensor& argmax, const Tensor& out, int64_t S, double inv) {
+  check_dev("gpool_bwd_fill", dp, argmax, out);
+  const int64_t B = gpool_check_act("gpool_bwd_fill", out, S), C = out.size(3);
+  TORCH_CHECK(dp.scalar_type() == at::kFloat && dp.is_contiguous() && dp.dim() == 3 && dp.size(0) == B &&
+                  dp.size(1) == 2 && dp.size(2) == C,
+              "gpool_bwd_fill: dp must be contiguous float32 (B, 2, C) = (", B, ", 2, ", C, ")");
+  TORCH_CHECK(argmax.scalar_type() == at::kInt && argmax.is_contiguous() && argmax.dim() == 2 && argmax.size(0) == B &&
+                  argmax.size(1) == C,
+              "gpool_bwd_fill: argmax must be contiguous int32 (B, C) = (", B, ", ", C, ")");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(dp.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(argmax.data_ptr()) % 16 == 0,
+              "gpool_bwd_fill: dp and argmax must be 16-byte aligned");
+  agk::GpoolMapArgs a{};
+  a.g = dp.data_ptr<float>();
+  a.argmax = argmax.data_ptr<int>();
+  a.out = bfp_mut(out);
+  a.B = (int)B; a.S = (int)S; a.C = (int)C;
+  a.inv = (float)inv;
+  a.elems = out.numel();
+  agk::launch_gpool_map(a, true, cur_stream());
+  launch_check("gpool_bwd_fill");
+}
+
 // A deliberately invalid launch (2048 threads per block, above the 1024
 // limit): the runtime rejects it, launch_check turns that into a Python
 // RuntimeError -- the test of the error path every op shares.
@@ -1210,6 +1289,9 @@ TORCH_LIBRARY(alphago_amd, m) {
   m.def("policy_head_d4(Tensor y, Tensor w, Tensor b, Tensor(a!) probs, int S, Tensor sym, int G, Tensor? legal=None, "
         "float temperature=1.0, Tensor(b!)? scratch=None) -> ()");
   m.def("group_mean(Tensor v, Tensor(a!) out, int G) -> ()");
+  m.def("gpool_fwd(Tensor y, Tensor(a!) pooled, Tensor(b!)? argmax, int S, float inv) -> ()");
+  m.def("gpool_bias_add(Tensor skip, Tensor g, Tensor(a!) out, int S) -> ()");
+  m.def("gpool_bwd_fill(Tensor dp, Tensor argmax, Tensor(a!) out, int S, float inv) -> ()");
   m.def("pack_weights(Tensor[] ws, Tensor(a!)[] wf, Tensor(b!)[] wd) -> ()");
   m.def("sgd_update(Tensor(a!) p, Tensor g, float lr, float gscale) -> ()");
   m.def("comm_proxy(Tensor src, Tensor(a!) dst, int channels, float wire_us) -> ()");
@@ -1278,6 +1360,9 @@ TORCH_LIBRARY_IMPL(alphago_amd, CUDA, m) {
   m.impl("d4_expand", &d4_expand);
   m.impl("policy_head_d4", &policy_head_d4);
   m.impl("group_mean", &group_mean);
+  m.impl("gpool_fwd", &gpool_fwd);
+  m.impl("gpool_bias_add", &gpool_bias_add);
+  m.impl("gpool_bwd_fill", &gpool_bwd_fill);
   m.impl("head_logits", &head_logits);
   m.impl("head_backward", &head_backward);
   m.impl("head_backward_add", &head_backward_add);

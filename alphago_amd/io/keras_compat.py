@@ -102,8 +102,8 @@ def model_from_keras_json(spec: str):
 
 def pv_spec(net: PolicyValueNet) -> Dict:
     """The dual net's architecture (it is no Keras Sequential: a spec key of its own, ``pv_model``);
-    ``residual: 1`` only for a residual trunk and ``ownership: 1`` only with the ownership head, so the
-    spec of a plain net is what it always was."""
+    ``residual: 1`` only for a residual trunk, ``ownership: 1`` only with the ownership head and
+    ``gpool: k`` only with pooling branches, so the spec of a plain net is what it always was."""
     return dict(net.arch)
 
 
@@ -125,6 +125,8 @@ def _weights_in_order(net) -> List[Tuple[str, List[torch.Tensor]]]:
         out.append(("value_dense_2", [net.fc2_w, net.fc2_b]))
         if getattr(net, "ownership", False):  # one more entry, only for a net with the ownership head
             out.append(("ownership_convolution2d_1", [net.ohead_w, net.ohead_b]))
+        for i, g in enumerate(getattr(tr, "gpool_w", ()), 1):  # one entry per pooling branch, after the heads
+            out.append(("gpool_dense_%d" % i, [g]))
         return out
     names = _layer_names(net)
     out = []
@@ -146,7 +148,7 @@ def save_weights(net, path: str, kernel_flip: bool = True) -> None:
         f.attrs["layer_names"] = np.array([n.encode() for n, _ in layers])
         for name, ws in layers:
             g = f.create_group(name)
-            wn = [name + "_W", name + "_b"] if ws else []
+            wn = [name + "_W", name + "_b"][:len(ws)]  # a gate (gpool_dense_%d) has no bias
             g.attrs["weight_names"] = np.array([w.encode() for w in wn]) if wn else np.zeros((0,), "S1")
             for wname, t in zip(wn, ws):
                 a = t.detach().float().cpu().numpy()

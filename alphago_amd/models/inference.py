@@ -105,6 +105,16 @@ class HipTrunkInference:
             raise ValueError("a residual trunk of %d filters runs in bf16 only: the fp8 conv kernels have their "
                              "skip operand on the 192-wide tile alone (precision=\"fp8\" argument or "
                              "ALPHAGO_AMD_PRECISION=fp8)" % tr.filters)
+        # global pooling branches (ConvStack gpool), bf16 trunk: after the first layer l of a branch block the
+        # bucket's gpool_fwd / dense_f32 / gpool_bias_add add the gate g[b, c] in place to the block's skip buffer
+        # Y[(l-1) % 3], which nothing reads after the block's last layer
+        self.gpool_blocks = list(getattr(tr, "gpool_blocks", ()))
+        if self.gpool_blocks and self.precision == "fp8":
+            raise ValueError("a trunk with global pooling branches (gpool=%d) runs in bf16 only: the fp8 trunk keeps "
+                             "no bf16 output of a block's first layer to pool (precision=\"fp8\" argument or "
+                             "ALPHAGO_AMD_PRECISION=fp8)" % tr.gpool)
+        self._gp_layer = {2 * j + 1: i for i, j in enumerate(self.gpool_blocks)}  # pooled layer -> branch
+        self.gpool_w = None
         self._ny = 3 if self.residual else 2
         self.S, self.L, self.K = net.board, tr.layers, list(tr.widths)
         self.C0, self.F = tr.in_planes, tr.filters
@@ -168,7 +178,7 @@ class HipTrunkInference:
         """Re-read the module's parameters into the engine's device copies.
 
         Contract: no device tensor that a captured graph reads is ever rebound.  A bucket's graph holds
-        the addresses of ``wf``, ``wf_ws``, ``bias_p``, ``head_w``, ``head_b``, ``w8``, ``scales8``,
+        the addresses of ``wf``, ``wf_ws``, ``bias_p``, ``head_w``, ``head_b``, ``gpool_w``, ``w8``, ``scales8``,
         ``osc8`` (and a subclass's own weights, ``_after_sync``) from the moment it is captured, so a
         refresh writes into those tensors in place; a tensor bound to a fresh allocation here would
         leave every captured bucket replaying the old weights out of freed memory."""
@@ -181,6 +191,13 @@ class HipTrunkInference:
             self.bias_p[l][:self.F].copy_(tr.biases[l].detach())
         self.head_w.copy_(self.net.head_w.detach().view(-1))
         self.head_b.copy_(self.net.head_b.detach().view(-1))
+        if self.gpool_blocks:
+            F, Fp = self.F, self.Fp
+            if self.gpool_w is None:  # allocated once; zero-padded (2 Fp, Fp): padded channels get g = 0
+                self.gpool_w = [torch.zeros(2 * Fp, Fp, device=self.device) for _ in self.gpool_blocks]
+            for dst, g in zip(self.gpool_w, tr.gpool_w):
+                dst[:F, :F].copy_(g.detach()[:F])
+                dst[Fp:Fp + F, :F].copy_(g.detach()[F:])
         if self.precision == "fp8":
             for l in range(self.L):
                 w8, self.ew[l] = ops.pack_weights_fp8(ws[l], self.Fp, self.cin_p[l])
@@ -226,6 +243,10 @@ class HipTrunkInference:
         bk.plan = [ops.plan_conv(M, self.Fp, c, K, small=small) for c, K in zip(self.cin_p, self.K)]
         n = ops.splitk_workspace_numel(bk.plan, M, self.Fp)
         bk.ws = torch.empty(n, device=dev) if n else None
+        if self.gpool_blocks:  # one set per bucket, shared by its branch blocks
+            bk.gp_P = torch.zeros(Bt, 2, self.Fp, device=dev)
+            bk.gp_arg = torch.zeros(Bt, self.Fp, dtype=torch.int32, device=dev)
+            bk.gp_g = torch.zeros(Bt, self.Fp, device=dev)
         if self.precision == "fp8":
             bk.X08 = torch.zeros(bk.X0.shape, dtype=torch.uint8, device=dev)
             bk.Y8 = [torch.zeros(bk.Y[0].shape, dtype=torch.uint8, device=dev) for _ in range(2)]
@@ -283,6 +304,10 @@ class HipTrunkInference:
                              sk_ws=bk.ws, res=res)
             if getattr(self, "_calibrating", False):
                 self._cal_amax[l] = max(self._cal_amax[l], float(y.amax()))
+            if l in self._gp_layer:  # the block's skip Y[(l-1) % 3] += g, before layer l + 1 reads it as res
+                ops.gpool_fwd(y, bk.gp_P, bk.gp_arg, self.S)
+                ops.dense_f32(bk.gp_P.view(bk.Bt, -1), self.gpool_w[self._gp_layer[l]], bk.gp_g)
+                ops.gpool_bias_add(bk.Y[(l - 1) % 3], bk.gp_g, bk.Y[(l - 1) % 3], self.S)
             x, pin = y, 1
         return x
 

@@ -43,7 +43,9 @@ def he_uniform_(net: nn.Module, generator=None) -> nn.Module:
     A residual trunk gets the Fixup rule for two-layer branches: the first conv of each block its He bound
     times ``n_blocks ** -0.5``, the second conv of each block zero; the stem and the heads as above.  With
     the zero biases every block is then the identity on its (non-negative) input, so the trunk's output
-    equals the stem's exactly."""
+    equals the stem's exactly.  The gates of the pooling branches (``trunk.gpool_w``) are the last linear
+    map of their branch and get zero by the same rule: right after this init the net computes exactly what
+    the same net without ``gpool`` computes."""
     with torch.no_grad():
         residual = getattr(net.trunk, "residual", False)
         n_blocks = (net.trunk.layers - 1) // 2
@@ -68,7 +70,21 @@ def he_uniform_(net: nn.Module, generator=None) -> nn.Module:
         if oh is not None:                  # tensors get the values they get in a net without it
             bound = (6.0 / (oh.shape[1] * oh.shape[2] * oh.shape[3])) ** 0.5
             oh.uniform_(-bound, bound, generator=generator)
+        for g in getattr(net.trunk, "gpool_w", ()):
+            g.zero_()
     return net
+
+
+def first_argmax(z: torch.Tensor) -> torch.Tensor:
+    """(B,) smallest index among each row's maxima."""
+    n = z.shape[1]
+    idx = torch.arange(n, device=z.device).expand_as(z)
+    return torch.where(z == z.max(1, keepdim=True).values, idx, torch.full_like(idx, n)).min(1).values
+
+
+def gpool_blocks(layers: int, k: int) -> List[int]:
+    """Blocks j = 0 .. n_blocks - 1 of a residual trunk that carry a pooling branch: (j + 1) % k == 0."""
+    return [j for j in range((layers - 1) // 2) if (j + 1) % k == 0] if k else []
 
 
 class ConvStack(nn.Module):
@@ -76,9 +92,20 @@ class ConvStack(nn.Module):
 
     ``residual``: layer 0 is the stem and layers 1..L-1 form blocks of two, (1, 2), (3, 4), ...; the last
     layer of a block adds the block's input before its ReLU, ``Y[l] = relu(conv_l(Y[l-1]) + b_l + Y[l-2])``
-    for even ``l >= 2``.  Parameter names, shapes and order are those of the plain stack."""
+    for even ``l >= 2``.  Parameter names, shapes and order are those of the plain stack.
 
-    def __init__(self, in_planes: int, filters: int, layers: int, widths: List[int], residual: bool = False):
+    ``gpool = k >= 1`` (residual trunks only): block j (layers l = 2j + 1 and l + 1) has a global pooling
+    branch when ``(j + 1) % k == 0``.  With NP = S * S,
+
+        P[b, 0, c] = (sum_p Y[l][b, p, c]) * float32(1 / NP)
+        P[b, 1, c] = max_p Y[l][b, p, c]          (ties: the lowest pixel index r * S + col)
+        g[b, :]    = P[b].reshape(2F) @ Wg_j      (Wg_j (2F, F), Keras Dense layout, no bias)
+        Y[l+1]     = relu(conv_{l+1}(Y[l]) + b_{l+1} + (Y[l-1] + g[b]))
+
+    ``gpool_w`` holds one ``Wg_j`` per branch block, in block order."""
+
+    def __init__(self, in_planes: int, filters: int, layers: int, widths: List[int], residual: bool = False,
+                 gpool: int = 0):
         super().__init__()
         assert len(widths) == layers
         if residual and (layers < 3 or layers % 2 == 0):
@@ -86,6 +113,16 @@ class ConvStack(nn.Module):
             raise ValueError("a residual trunk is a stem plus whole two-layer blocks: layers must be odd and "
                              ">= 3, not %d (nearest valid depths: %d and %d)" % (layers, lo, max(lo + 2, layers + 1)))
         self.residual = bool(residual)
+        gpool = int(gpool)
+        n_blocks = (layers - 1) // 2
+        if gpool and not residual:
+            raise ValueError("gpool=%d needs a residual trunk (residual=1): the pooling branch adds to a block's "
+                             "skip; valid choices: residual=1 with gpool in 1..n_blocks, or no gpool" % gpool)
+        if gpool and not 1 <= gpool <= n_blocks:
+            raise ValueError("gpool=%d: a branch in every gpool-th block needs 1 <= gpool <= n_blocks = %d "
+                             "(valid choices: %s)" % (gpool, n_blocks, ", ".join(map(str, range(1, n_blocks + 1)))))
+        self.gpool = gpool
+        self.gpool_blocks = gpool_blocks(layers, gpool)
         for w in widths:
             if w % 2 != 1:
                 raise ValueError("filter widths must be odd")
@@ -98,6 +135,15 @@ class ConvStack(nn.Module):
             self.biases.append(nn.Parameter(torch.zeros(filters)))
             cin = filters
         self.reset_parameters()
+
+    def init_gpool(self, generator=None) -> None:
+        """Create and draw the gates of the pooling branches.  The owning net calls it after it has drawn
+        every other parameter, so those get the values they get without ``gpool``."""
+        if self.gpool:
+            self.gpool_w = nn.ParameterList(nn.Parameter(torch.empty(2 * self.filters, self.filters))
+                                            for _ in self.gpool_blocks)
+            for g in self.gpool_w:
+                keras_uniform_(g, generator=generator)
 
     def reset_parameters(self, generator=None):
         for w in self.weights:
@@ -113,7 +159,19 @@ class ConvStack(nn.Module):
                 x = skip = F.relu(z if l == 0 else z + skip)
             else:
                 x = F.relu(z)
+                if self.gpool and (l - 1) // 2 in self.gpool_blocks:  # the block's pooling branch joins its skip
+                    skip = skip + self.gate_torch(x, self.gpool_blocks.index((l - 1) // 2))[:, :, None, None]
         return x
+
+    def gate_torch(self, y: torch.Tensor, i: int) -> torch.Tensor:
+        """(B, F) gate of branch ``i`` from a block's first-layer output ``y`` (B, F, S, S): mean and max over
+        the board (the max gathered at the lowest pixel index attaining it, which pins its gradient), then
+        the dense layer ``gpool_w[i]``."""
+        B, C = y.shape[:2]
+        flat = y.reshape(B * C, -1)
+        mean = flat.sum(1) * torch.tensor(1.0 / flat.shape[1], dtype=torch.float32).to(y.dtype)
+        mx = flat.gather(1, first_argmax(flat.detach())[:, None])[:, 0]
+        return torch.cat([mean.view(B, C), mx.view(B, C)], 1) @ self.gpool_w[i].to(y.dtype)
 
 
 class PolicyNet(nn.Module):
@@ -212,10 +270,12 @@ class PolicyValueNet(nn.Module):
     Reads the value net's planes (49 with ``color``).  ``residual``: a residual trunk (ConvStack), kept in
     ``arch`` only when set; ``layers`` must then be odd.  ``ownership``: a third 1x1 head (``ohead_w``,
     ``ohead_b``) with a tanh per board point, the owner of the point at the end of the game in the
-    mover's frame (+1 = the player to move); kept in ``arch`` only when set."""
+    mover's frame (+1 = the player to move); kept in ``arch`` only when set.  ``gpool = k``: a global pooling
+    branch in every k-th block of a residual trunk (ConvStack; ``trunk.gpool_w``), kept in ``arch`` only when
+    set."""
 
     def __init__(self, input_dim: int = 49, board: int = 19, filters_per_layer: int = 192, layers: int = 12,
-                 dense: int = 256, residual: int = 0, ownership: int = 0, **kwargs):
+                 dense: int = 256, residual: int = 0, ownership: int = 0, gpool: int = 0, **kwargs):
         super().__init__()
         widths = [int(kwargs.get("filter_width_%d" % i, 5 if i == 1 else 3)) for i in range(1, layers + 1)]
         self.arch = dict(input_dim=input_dim, board=board, filters_per_layer=filters_per_layer, layers=layers,
@@ -227,9 +287,12 @@ class PolicyValueNet(nn.Module):
             self.arch["residual"] = 1
         if ownership:
             self.arch["ownership"] = 1
+        if gpool:
+            self.arch["gpool"] = int(gpool)
         self.ownership = bool(ownership)
         self.board = board
-        self.trunk = ConvStack(input_dim, filters_per_layer, layers, widths, residual=bool(residual))
+        self.trunk = ConvStack(input_dim, filters_per_layer, layers, widths, residual=bool(residual),
+                               gpool=int(gpool))
         self.head_w = nn.Parameter(torch.empty(1, filters_per_layer, 1, 1))
         self.head_b = nn.Parameter(torch.zeros(1))
         self.vhead_w = nn.Parameter(torch.empty(1, filters_per_layer, 1, 1))
@@ -244,6 +307,7 @@ class PolicyValueNet(nn.Module):
             self.ohead_w = nn.Parameter(torch.empty(1, filters_per_layer, 1, 1))
             self.ohead_b = nn.Parameter(torch.zeros(1))
             keras_uniform_(self.ohead_w)
+        self.trunk.init_gpool()  # after every other parameter: they draw what they draw without the branch
 
     @property
     def input_dim(self):
@@ -257,6 +321,7 @@ class PolicyValueNet(nn.Module):
             tot += 2.0 * s2 * cin * self.trunk.filters * k * k
             cin = self.trunk.filters
         d = self.arch["dense"]
+        tot += len(self.trunk.gpool_blocks) * 2.0 * 2 * cin * cin  # the gates: Dense(2F -> F) per branch block
         return tot + (3 if self.ownership else 2) * (2.0 * s2 * cin) + 2.0 * s2 * d + 2.0 * d
 
     def heads_torch(self, h: torch.Tensor):

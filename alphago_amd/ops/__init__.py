@@ -11,6 +11,7 @@ are bf16 ``(K*K, Cout_p, Cin_p)``.
 """
 from __future__ import annotations
 
+import functools
 import os
 import threading
 from typing import NamedTuple, Optional
@@ -429,6 +430,38 @@ def policy_head_probs_d4(y, w, b, probs, S: int, sym, G: int, legal=None, temper
 def group_mean(v, out, G: int):
     """out[b] = (v[b] + v[B + b] + ... + v[(G-1) B + b]) * float32(1 / G), fp32 in that order."""
     _ops().group_mean(v, out, G)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def gpool_inv(S: int) -> float:
+    """float32(1 / (S * S)) as a Python float: the factor of the pooling branch's mean, computed once on the
+    host (ConvStack.gate_torch multiplies by the same fp32 value)."""
+    return float(torch.tensor(1.0 / (S * S), dtype=torch.float32))
+
+
+def gpool_fwd(y, pooled, argmax, S: int):
+    """Global pooling of a padded NHWC bf16 activation ``y`` (B, S+2, S+2, C) over its interior, per board and
+    channel: ``pooled`` (B, 2, C) fp32 = {sum * float32(1 / S*S), max}, ``argmax`` (B, C) int32 = the lowest
+    pixel index r * S + col attaining the maximum.  fp32 sums in a fixed order, no atomics: two runs give
+    the same bits.  ``argmax=None`` is the sum mode: ``pooled`` (B, C) = the plain sum (the same summation),
+    the column sum of the branch's backward."""
+    _ops().gpool_fwd(y, pooled, argmax, S, 1.0 if argmax is None else gpool_inv(S))
+    return pooled
+
+
+def gpool_bias_add(skip, g, out, S: int):
+    """out[b, p, c] = bf16(float(skip[b, p, c]) + g[b, c]) over the interior (one fp32 add, round to nearest
+    even); borders are not written.  ``out`` may be ``skip`` (in place)."""
+    _ops().gpool_bias_add(skip, g, out, S)
+    return out
+
+
+def gpool_bwd_fill(dp, argmax, out, S: int):
+    """Gradient of ``gpool_fwd`` with respect to its input from ``dp`` (B, 2, C) fp32:
+    out[b, p, c] = bf16(dp[b, 0, c] * inv + (p == argmax[b, c] ? dp[b, 1, c] : 0)), inv = float32(1 / S*S),
+    product and sum rounded separately (no FMA).  Interior only."""
+    _ops().gpool_bwd_fill(dp, argmax, out, S, gpool_inv(S))
     return out
 
 

@@ -37,7 +37,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..utils.profiling import trace_range
-from ..models.nets import PolicyNet, ValueNet
+from ..models.nets import PolicyNet, ValueNet, first_argmax  # noqa: F401 - first_argmax: its users import it from here
 from ..parallel import dist as agdist
 
 # The 8 D4 symmetries as flat-index permutations (numpy semantics of the
@@ -124,13 +124,6 @@ def soft_target_loss(logits: torch.Tensor, dist: torch.Tensor):
     ce = -torch.where(qh > 0, qh * logp, torch.zeros_like(logp)).sum(1)
     correct = ((first_argmax(logits) == first_argmax(q)) & has).float()
     return ce, correct, has
-
-
-def first_argmax(z: torch.Tensor) -> torch.Tensor:
-    """(B,) smallest index among each row's maxima."""
-    n = z.shape[1]
-    idx = torch.arange(n, device=z.device).expand_as(z)
-    return torch.where(z == z.max(1, keepdim=True).values, idx, torch.full_like(idx, n)).min(1).values
 
 
 class FlatParams:
@@ -242,8 +235,14 @@ MERGED_REDUCE_MAX_PIXELS = 0
 
 
 def _trunk_named(tr) -> List[Tuple[str, torch.nn.Parameter]]:
-    """(name, parameter) of a ConvStack in flat-buffer order: w0, b0, w1, b1, ..."""
-    return [(n % l, p[l]) for l in range(tr.layers) for n, p in (("w%d", tr.weights), ("b%d", tr.biases))]
+    """(name, parameter) of a ConvStack in flat-buffer order: w0, b0, w1, b1, ...  A trunk with pooling
+    branches (gpool) has the gate of a branch block right after the bias of the block's last layer l,
+    ``g<l>``: its gradient is complete when that layer's is, so it belongs to the layer's bucket segment."""
+    named = [(n % l, p[l]) for l in range(tr.layers) for n, p in (("w%d", tr.weights), ("b%d", tr.biases))]
+    for i, j in enumerate(getattr(tr, "gpool_blocks", ())):
+        at = [n for n, _ in named].index("b%d" % (2 * j + 2)) + 1
+        named.insert(at, ("g%d" % (2 * j + 2), tr.gpool_w[i]))
+    return named
 
 
 class _Layer(NamedTuple):
@@ -282,6 +281,17 @@ class HipConvTrainer:
         if precision not in ("bf16", "fp8"):
             raise ValueError("precision must be bf16 or fp8")
         self.precision = precision
+        # global pooling branches (ConvStack gpool): after the first layer l of a branch block, gpool_fwd pools
+        # Y[l], dense_f32 makes the gate g and gpool_bias_add writes R = Y[l-1] + g, which layer l + 1 takes as its
+        # skip operand in Y[l-1]'s place; the backward mirrors it before wgrad(l + 1) (_gpool_backward).  bf16 only
+        self.gpool_blocks = list(getattr(net.trunk, "gpool_blocks", ()))
+        if self.gpool_blocks and precision == "fp8":
+            raise ValueError("a trunk with global pooling branches (gpool=%d) trains in bf16 only: the fp8 trunk keeps "
+                             "no bf16 output of a block's first layer to pool (precision=\"fp8\")" % net.trunk.gpool)
+        if self.gpool_blocks and self.lab_tile:
+            raise ValueError("a trunk with global pooling branches (gpool=%d) cannot run on a kernel-lab tiling: the "
+                             "kernel-lab library has no skip operand (ALPHAGO_AMD_LAB_TILE=%d)"
+                             % (net.trunk.gpool, self.lab_tile))
         # residual trunk (ConvStack residual=True): the skip-add is fused into the conv epilogues --
         # forward of an even layer l >= 2 adds Y[l-2], dgrad of an odd layer l adds DZ[l+1].  The fp8 kernels
         # take the skip on the 192-wide tile only; the residual stream (Y and DZ of the even layers) stays bf16
@@ -381,6 +391,56 @@ class HipConvTrainer:
         self.MBITS = [torch.zeros(hw, dtype=torch.int32, device=dev) for _ in range(self.L - 1)]
         self.loss = torch.zeros(B, device=dev)
         self.correct = torch.zeros(B, device=dev)
+        if self.gpool_blocks:
+            self._init_gpool()
+
+    def _init_gpool(self) -> None:
+        """Buffers of the pooling branches.  Per branch block (keyed by its last layer l + 1): the pooled
+        vector P and the argmax, kept for the backward.  Shared by all blocks: the gate g, the skip operand
+        R = Y[l-1] + g (its gradient with respect to Y[l-1] is the identity, so the backward never reads it),
+        and the backward's dg, dP and G2 (the pooling's gradient into Y[l], the skip operand of dgrad(l + 1)).
+        Padded widths (F < Fp): the kernels see zero-padded (2 Fp, Fp) copies of the gates (rows F.. of each
+        half and columns F.. stay zero, so padded channels get g = 0) and dWg lands in a padded scratch whose
+        real blocks are copied into the flat gradient; unpadded, both are the flat views themselves."""
+        dev, B, S, Fp, F = self.device, self.batch, self.S, self.Fp, self.F
+        self._gp_layers = [2 * j + 2 for j in self.gpool_blocks]
+        self._gp_P = {l: torch.zeros(B, 2, Fp, device=dev) for l in self._gp_layers}
+        self._gp_arg = {l: torch.zeros(B, Fp, dtype=torch.int32, device=dev) for l in self._gp_layers}
+        self._gp_g = torch.zeros(B, Fp, device=dev)
+        self._gp_dg = torch.zeros(B, Fp, device=dev)
+        self._gp_dP = torch.zeros(B, 2, Fp, device=dev)
+        self._gp_R = ops.padded_empty(B, S, 1, Fp, dev)
+        self._gp_G2 = ops.padded_empty(B, S, 1, Fp, dev)
+        if self._bias_alias:
+            self._gp_w = {l: self.fp.views["g%d" % l] for l in self._gp_layers}
+            self._gp_dw = {l: self.fp.grad_views["g%d" % l] for l in self._gp_layers}
+        else:
+            self._gp_w = {l: torch.zeros(2 * Fp, Fp, device=dev) for l in self._gp_layers}
+            self._gp_dw = {l: torch.zeros(2 * Fp, Fp, device=dev) for l in self._gp_layers}
+
+    def _gpool_forward(self, l: int) -> torch.Tensor:
+        """After layer l - 1, the first layer of a branch block ending at l: pool Y[l-1], gate, and the skip
+        operand R = Y[l-2] + g of layer l."""
+        S = self.S
+        ops.gpool_fwd(self.Y[l - 1], self._gp_P[l], self._gp_arg[l], S)
+        ops.dense_f32(self._gp_P[l].view(self.batch, -1), self._gp_w[l], self._gp_g)  # g = P Wg
+        return ops.gpool_bias_add(self.Y[l - 2], self._gp_g, self._gp_R, S)
+
+    def _gpool_backward(self, l: int) -> None:
+        """Before wgrad(l) and dgrad(l) of a branch block's last layer l: dg = sum_p DZ[l], dWg = P^T dg into
+        the flat gradient, dP = dg Wg^T, and G2 = the pooling's gradient into Y[l-1], which dgrad(l) adds
+        before ReLU'.  All on the caller's stream, ahead of the event wgrad(l) waits on: dWg is complete
+        when layer l's bucket is launched."""
+        B, F, Fp = self.batch, self.F, self.Fp
+        P = self._gp_P[l].view(B, -1)
+        ops.gpool_fwd(self.DZ[l], self._gp_dg, None, self.S)
+        ops.dense_f32(P, self._gp_dg, self._gp_dw[l], trans_a=True)  # dWg = P^T dg
+        if not self._bias_alias:
+            gv = self.fp.grad_views["g%d" % l]
+            gv[:F].copy_(self._gp_dw[l][:F, :F])
+            gv[F:].copy_(self._gp_dw[l][Fp:Fp + F, :F])
+        ops.dense_f32(self._gp_dg, self._gp_w[l], self._gp_dP.view(B, -1), trans_b=True)  # dP = dg Wg^T
+        ops.gpool_bwd_fill(self._gp_dP, self._gp_arg[l], self._gp_G2, self.S)
 
     def _init_plans(self, wgrad_target_wgs: int, wgrad_direct: Optional[bool], reduce_stream: bool) -> None:
         """Per-layer kernel choices (wgrad variant and split, forward / dgrad plans) and what they need."""
@@ -444,7 +504,8 @@ class HipConvTrainer:
         for l in reversed(range(self.L)):
             ow, nw = self.fp.segments["w%d" % l]
             _, nb = self.fp.segments["b%d" % l]
-            segs.append((ow, nw + nb))
+            ng = self.fp.segments["g%d" % l][1] if "g%d" % l in self.fp.segments else 0  # a branch block's gate
+            segs.append((ow, nw + nb + ng))
         self.buckets = agdist.make_buckets(segs, int(bucket_mb * (1 << 20)), last_alone=True)
         self._bucket_after_layer = {self._seg_layer[ids[-1]]: bi for bi, (_, _, ids) in enumerate(self.buckets)}
         self.reducer = agdist.BucketAllReducer(self.fp.grad, self.buckets)
@@ -582,6 +643,10 @@ class HipConvTrainer:
         the fused update already wrote them: ``bf16=False``) and the fp8 packs."""
         if not self._bias_alias:
             torch._foreach_copy_([b[:self.F] for b in self.bias_p], [self.fp.views["b%d" % l] for l in range(self.L)])
+            for l in (self._gp_layers if self.gpool_blocks else ()):  # the gates' zero-padded copies
+                g = self.fp.views["g%d" % l]
+                self._gp_w[l][:self.F, :self.F].copy_(g[:self.F])
+                self._gp_w[l][self.Fp:self.Fp + self.F, :self.F].copy_(g[self.F:])
         ws = [self.fp.views["w%d" % l] for l in range(self.L)]
         if bf16:
             ops.pack_weights(ws, self.wf, self.wd)
@@ -631,6 +696,8 @@ class HipConvTrainer:
         else:
             # residual trunk: a block's last layer adds the block's input before its ReLU
             res = self.Y[l - 2] if self.residual and l >= 2 and l % 2 == 0 else None
+            if res is not None and self.gpool_blocks and l in self._gp_layers:
+                res = self._gpool_forward(l)
             ops.conv_planned(self.fwd_plan[l], x, self.wf[l], self.wf_ws[l], self.bias_p[l], self.Y[l], self.K[l],
                              self.S, pin, ops.MODE_BIAS_RELU, mbits, self._sk_ws, res=res)
 
@@ -777,6 +844,8 @@ class HipConvTrainer:
             # already-masked gradient at the block's output, which nothing writes again in this backward
             # (the side-stream wgrad only reads it)
             res = self.DZ[l + 1] if self.residual and l % 2 == 1 else None
+            if self.gpool_blocks and l in self._gp_layers:  # a branch block's last layer: the pooling's gradient
+                res = self._gp_G2
             ops.conv_planned(self.dg_plan[l], self.DZ[l], self.wd[l], self.wd_ws[l], None, self.DZ[l - 1],
                              self.K[l], self.S, 1, ops.MODE_MASKBITS, self.MBITS[l - 1], self._sk_ws, res=res)
 
@@ -792,6 +861,8 @@ class HipConvTrainer:
             # the head's dZ in e5m2 for wgrad(L-1), and its max |dZ| (the value head writes it itself)
             ops.quantize_bf8(self.DZ[top], self.DZ8[top], self.gosc8[top:top + 1], self.gamax8[top])
         for l in reversed(range(self.L)):
+            if self.gpool_blocks and l in self._gp_layers:
+                self._gpool_backward(l)
             if self.s_w is not None:
                 ev = main.record_event()
                 with torch.cuda.stream(self.s_w):
