@@ -98,7 +98,13 @@ def _init_model(argv):
     p.add_argument("--gpool", type=int, default=0, metavar="K",
                    help="pv --residual only: a global pooling branch (mean and max over the board -> dense -> "
                         "per-channel bias on the block's skip) in every K-th residual block")
+    p.add_argument("--pass-head", action="store_true",
+                   help="pv only: a learned pass logit next to the S*S move logits (mean and max of the trunk "
+                        "output over the board -> dense), trained by train-pv on the pass column of "
+                        "selfplay-mcts records and searched as a child of every node")
     a = p.parse_args(argv)
+    if a.pass_head and a.kind != "pv":
+        p.error("--pass-head needs the dual net (init-model pv): the pass logit joins its policy softmax")
     if a.gpool and not (a.kind == "pv" and a.residual):
         p.error("--gpool needs a residual dual net (init-model pv --residual --gpool K)")
     if a.residual and a.kind != "pv":
@@ -118,6 +124,8 @@ def _init_model(argv):
             kw["ownership"] = 1
         if a.gpool:
             kw["gpool"] = a.gpool
+        if a.pass_head:
+            kw["pass_head"] = 1
         try:
             m = CNNPolicyValue(feats, board=a.board, filters_per_layer=a.filters or 192, layers=a.layers,
                                device="cpu", **kw)

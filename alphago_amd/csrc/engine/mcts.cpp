@@ -407,7 +407,8 @@ double Forest::rollout(GameState& s, std::mt19937_64& rng) const {
   return (double)(s.get_winner() * p0);
 }
 
-void Forest::apply_range(int i0, int i1, const float* priors, const float* values, const uint8_t* mask) {
+void Forest::apply_range(int i0, int i1, const float* priors, const float* values, const uint8_t* mask,
+                         const float* pass_priors) {
   std::vector<int> moves;
   std::vector<float> ps;
   for (int i = i0; i < i1; ++i) {
@@ -430,7 +431,13 @@ void Forest::apply_range(int i0, int i1, const float* priors, const float* value
       moves.push_back(PASS);
       ps.push_back(1.f);
       sum = 1.0;
-    } else if (sum <= 0) {
+    } else if (pass_priors) {  // a net with a pass logit: PASS is a child of every node, stored last
+      moves.push_back(PASS);
+      float v = std::max(pass_priors[i], 0.f);
+      ps.push_back(v);
+      sum += v;
+    }
+    if (sum <= 0) {
       for (auto& v : ps) v = 1.f;
       sum = (double)ps.size();
     }
@@ -451,13 +458,13 @@ void Forest::apply_range(int i0, int i1, const float* priors, const float* value
   }
 }
 
-void Forest::apply(const float* priors, const float* values, const uint8_t* mask) {
+void Forest::apply(const float* priors, const float* values, const uint8_t* mask, const float* pass_priors) {
   const int L = (int)pending_.size();
   // rollouts draw from their tree's own stream, so they run on every worker (results are
   // independent of the worker count); without rollouts small batches stay on one thread
   const int T = std::max(1, std::min(threads_, lmbda_ > 0 ? L : L / 64));
   if (T == 1) {
-    apply_range(0, L, priors, values, mask);
+    apply_range(0, L, priors, values, mask, pass_priors);
   } else {
     // split at tree boundaries (pending_ is grouped by tree): no two workers touch one tree
     std::vector<int> cut(T + 1, L);
@@ -467,7 +474,7 @@ void Forest::apply(const float* priors, const float* values, const uint8_t* mask
       while (c < L && c > 0 && pending_[c].tree == pending_[c - 1].tree) ++c;
       cut[w] = std::max(c, cut[w - 1]);
     }
-    run_parts(T, [&](int w) { apply_range(cut[w], cut[w + 1], priors, values, mask); });
+    run_parts(T, [&](int w) { apply_range(cut[w], cut[w + 1], priors, values, mask, pass_priors); });
   }
   pending_.clear();
   leaf_slot_.clear();
@@ -502,6 +509,14 @@ void Forest::root_stats(int t, std::vector<int>& moves, std::vector<int>& visits
     visits.push_back(c.N);
     q.push_back(c.N > 0 ? c.W / c.N : 0.f);
   }
+}
+
+std::vector<float> Forest::root_priors(int t) const {
+  const SearchTree& tr = trees_.at(t);
+  const Node& r = tr.nodes[0];
+  std::vector<float> p;
+  for (int i = 0; i < r.nchild; ++i) p.push_back(tr.nodes[r.first_child + i].P);
+  return p;
 }
 
 int Forest::best_move(int t, double temperature) {

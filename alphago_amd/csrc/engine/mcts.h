@@ -183,7 +183,10 @@ class Forest {
   }
   // priors (L, n*n) float32 (any non-negative scores; renormalised over sensible moves), values (L,);
   // mask (L, n*n) optional sensible-move mask (e.g. from the GPU featurizer) — skips the legality/eye scan
-  void apply(const float* priors, const float* values, const uint8_t* mask = nullptr);
+  // pass_priors (one per pending leaf, or null): every expanded node with a sensible move also gets a PASS
+  // child, stored last, with prior max(pass_prior, 0) normalised together with the others
+  void apply(const float* priors, const float* values, const uint8_t* mask = nullptr,
+             const float* pass_priors = nullptr);
   // worker threads for gather/apply (trees are independent; results are identical for any count)
   void set_threads(int n) {
     threads_ = n < 1 ? 1 : n;
@@ -204,6 +207,8 @@ class Forest {
   int rollout_policy() const { return rollout_kind_; }
   // Root statistics
   void root_stats(int t, std::vector<int>& moves, std::vector<int>& visits, std::vector<float>& q) const;
+  // the priors of the root's children, in root_stats' order
+  std::vector<float> root_priors(int t) const;
   int best_move(int t, double temperature);
   void advance(int t, int move);
   int64_t sims(int t) const { return trees_[t].sims; }
@@ -243,7 +248,8 @@ class Forest {
   mutable std::unique_ptr<WorkPool> pool_;  // threads_ - 1 persistent workers (set_threads)
   void gather_trees(const int* trees, int ntrees, int lpt, std::vector<Leaf>& pend, std::vector<int>& slot_ids,
                     int slot_base);
-  void apply_range(int i0, int i1, const float* priors, const float* values, const uint8_t* mask);
+  void apply_range(int i0, int i1, const float* priors, const float* values, const uint8_t* mask,
+                   const float* pass_priors = nullptr);
 };
 
 

@@ -112,7 +112,7 @@ void bind_mcts(py::module_& m) {
       .def(
           "apply",
           [](Forest& f, py::array_t<float, py::array::c_style | py::array::forcecast> priors, py::object values,
-             py::object mask) {
+             py::object mask, py::object pass_priors) {
             int L = f.n_pending();
             if (L == 0) return;
             int np = f.leaf_state(0).np;
@@ -133,10 +133,18 @@ void bind_mcts(py::module_& m) {
               if (ma.size() != (ssize_t)L * np) throw py::value_error("mask must be (n_pending, size*size)");
               mv = ma.data();
             }
+            const float* pp = nullptr;
+            py::array_t<float, py::array::c_style | py::array::forcecast> pa;
+            if (!pass_priors.is_none()) {
+              pa = pass_priors.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+              if (pa.size() != L) throw py::value_error("pass_priors must have n_pending entries");
+              pp = pa.data();
+            }
             py::gil_scoped_release r;
-            f.apply(pv, vv, mv);
+            f.apply(pv, vv, mv, pp);
           },
-          py::arg("priors"), py::arg("values") = py::none(), py::arg("mask") = py::none())
+          py::arg("priors"), py::arg("values") = py::none(), py::arg("mask") = py::none(),
+          py::arg("pass_priors") = py::none())
       .def("set_threads", &Forest::set_threads, py::arg("n"))
       .def_property("ladder_cache", &Forest::ladder_cache, &Forest::set_ladder_cache)
       .def("clear_ladder_cache", &Forest::clear_ladder_cache)
@@ -166,6 +174,7 @@ void bind_mcts(py::module_& m) {
              for (int p : mv) moves.append(idx_to_tup(f.root_state(t), p));
              return py::make_tuple(moves, vis, q);
            })
+      .def("root_priors", &Forest::root_priors, py::arg("tree"))
       .def(
           "best_move",
           [](Forest& f, int t, double temp) { return idx_to_tup(f.root_state(t), f.best_move(t, temp)); },

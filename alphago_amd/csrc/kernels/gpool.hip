@@ -1,4 +1,4 @@
-// Global pooling branch of the residual trunk (ConvStack gpool): three memory-bound kernels over the
+// Global pooling branch of the residual trunk (ConvStack gpool): four memory-bound kernels over the
 // zero-bordered NHWC bf16 activations (B, S + 2, S + 2, C), border 1.  They read and write interior pixels
 // only.  The gate's dense layer and its two backward products run on dense_f32.
 //  * gpool_fwd: per board and channel the sum over the S * S pixels times inv, and (FULL) the maximum and
@@ -8,6 +8,8 @@
 //    operand; out may be skip itself.
 //  * gpool_bwd_fill: the gradient of the pooling with respect to its input,
 //    out = bf16(dp[b, 0, c] * inv + (p == argmax[b, c] ? dp[b, 1, c] : 0)), two fp32 roundings.
+//  * gpool_bwd_add_masked (the pass head of the dual net): that gradient for dp[b, k, c] = dpass[b] * w[k, c],
+//    added into an existing dZ where the pooled activation is positive; a kernel of its own at the end of the file.
 // Summation order of gpool_fwd (fixed, no atomics): thread (pg, cg) owns the 8 channels 8 cg .. 8 cg + 7
 // and adds the pixels pg, pg + PG, pg + 2 PG, ... in that order; then thread c adds the PG partials of
 // channel c in pg order.  Two runs give the same bits.
@@ -200,6 +202,57 @@ void launch_gpool_map(const GpoolMapArgs& a, bool fill, hipStream_t st) {
   else hipLaunchKernelGGL(gpool_map_kernel<false>, dim3(a.B, ny), dim3(kGpoolNT), 0, st, a);
 #ifdef AGK_DEBUG
   gpool_debug_check(fill ? "gpool_bwd_fill" : "gpool_bias_add", st);
+#endif
+}
+
+// The pass head's pooling gradient added into the dZ of the trunk's top layer (gpool_map_kernel's layout, a
+// read-modify-write).  With dP[b, k, c] = dpass[b] * w[k, c] and y the top layer's output after its ReLU:
+//   dz[b, p, c] = bf16(float(dz[b, p, c]) + (dP[b, 0, c] * inv + (p == argmax[b, c] ? dP[b, 1, c] : 0)))  where y > 0
+// every product and sum an fp32 rounding of its own (no FMA); where y <= 0 the element keeps its bits.
+__global__ __launch_bounds__(kGpoolNT) void gpool_bwd_add_masked_kernel(GpoolBwdAddArgs a) {
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int C = a.C, C8 = C >> 3, NP = a.S * a.S;
+  const int PG = kGpoolNT / C8;
+  const int pg = tid / C8, cg = tid - pg * C8;
+  if (pg >= PG) return;
+  float v0[8], v01[8];
+  int am[8];
+  const float g = a.dpass[b];
+  const float* w0 = a.w + cg * 8;
+  const float* w1 = a.w + C + cg * 8;
+  const int* ap = a.argmax + (size_t)b * C + cg * 8;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int4 xa = *(const int4*)(ap + 4 * h);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {  // dword loads: w may be a view into the flat parameters at any 4-byte offset
+      v0[4 * h + e] = __fmul_rn(__fmul_rn(g, w0[4 * h + e]), a.inv);
+      v01[4 * h + e] = __fadd_rn(v0[4 * h + e], __fmul_rn(g, w1[4 * h + e]));  // the argmax pixel's addend
+    }
+    am[4 * h + 0] = xa.x; am[4 * h + 1] = xa.y; am[4 * h + 2] = xa.z; am[4 * h + 3] = xa.w;
+  }
+#pragma unroll 4
+  for (int p = pg + PG * blockIdx.y; p < NP; p += PG * gridDim.y) {
+    int64_t o = gpool_pixel(b, p, a.S, C) + cg * 8;
+    if (!GPOOL_DCHECK(o >= 0 && o + 8 <= a.elems)) o = 0;
+    const bf16x8 v = *(const bf16x8*)(a.y + o);
+    bf16x8 r = *(const bf16x8*)(a.dz + o);
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (bf2f(v[e]) > 0.f) r[e] = f2bf(__fadd_rn(bf2f(r[e]), am[e] == p ? v01[e] : v0[e]));
+    *(bf16x8*)(a.dz + o) = r;
+  }
+}
+
+void launch_gpool_bwd_add_masked(const GpoolBwdAddArgs& a, hipStream_t st) {
+  if (a.C % 8 || a.C < 8 || a.C > kGpoolNT || a.B < 1)
+    throw std::invalid_argument("gpool_bwd_add_masked: C must be a multiple of 8 in 8..512 and B >= 1");
+  int ny = (512 + a.B - 1) / a.B;  // launch_gpool_map's split
+  ny = ny > 8 ? 8 : ny;
+  hipLaunchKernelGGL(gpool_bwd_add_masked_kernel, dim3(a.B, ny), dim3(kGpoolNT), 0, st, a);
+#ifdef AGK_DEBUG
+  gpool_debug_check("gpool_bwd_add_masked", st);
 #endif
 }
 

@@ -1216,6 +1216,117 @@ void gpool_bwd_fill(const Tensor& dp, const Tensor& argmax, const Tensor& out, i
   launch_check("gpool_bwd_fill");
 }
 
+// ---- pass head of the dual net (head_pass.hip, gpool.hip)
+// pooled (B, 2, C), pass_w (2, C) zero-padded, pass_b (1): the operands of z_pass shared by both head ops
+static void pass_operands(const char* op, const Tensor& pooled, const Tensor& pass_w, const Tensor& pass_b, int64_t B,
+                          int64_t C) {
+  CHECK_F32(pooled); CHECK_CONTIG(pooled); CHECK_F32(pass_w); CHECK_CONTIG(pass_w); CHECK_F32(pass_b);
+  TORCH_CHECK(pooled.dim() == 3 && pooled.size(0) == B && pooled.size(1) == 2 && pooled.size(2) == C, op,
+              ": pooled must be (B, 2, C) = (", B, ", 2, ", C, ")");
+  TORCH_CHECK(pass_w.dim() == 2 && pass_w.size(0) == 2 && pass_w.size(1) == C, op,
+              ": pass_w must be the zero-padded (2, C) = (2, ", C, ") copy");
+  TORCH_CHECK(pass_b.numel() >= 1, op, ": pass_b must hold one entry");
+}
+
+void policy_head_soft_pass(const Tensor& y, const Tensor& w, const Tensor& b, const Tensor& pooled,
+                           const Tensor& pass_w, const Tensor& pass_b, const Tensor& tdist,
+                           const c10::optional<Tensor>& sym, const c10::optional<Tensor>& weight, const Tensor& dz,
+                           const Tensor& loss, const Tensor& correct, const Tensor& dhead, const Tensor& dpass,
+                           const Tensor& dpw, int64_t S, double grad_scale) {
+  const char* op = "policy_head_soft_pass";
+  check_dev(op, y, w, b, pooled, pass_w, pass_b, tdist, sym, weight, dz, loss, correct, dhead, dpass, dpw);
+  head_geometry(op, y, S, {&w}, {&b});
+  const int64_t B = y.size(0), C = y.size(3), Cr = w.numel();
+  pass_operands(op, pooled, pass_w, pass_b, B, C);
+  CHECK_F32(tdist); CHECK_CONTIG(tdist);
+  TORCH_CHECK(tdist.dim() == 2 && tdist.size(0) == B && tdist.size(1) == S * S + 1, op,
+              ": tdist must be (B, S*S + 1) with the pass last (a narrower row has no pass entry)");
+  CHECK_BF16(dz); CHECK_CONTIG(dz); CHECK_F32(loss); CHECK_F32(correct); CHECK_F32(dhead); CHECK_F32(dpass); CHECK_F32(dpw);
+  CHECK_CONTIG(loss); CHECK_CONTIG(correct); CHECK_CONTIG(dhead); CHECK_CONTIG(dpass); CHECK_CONTIG(dpw);
+  TORCH_CHECK(dz.sizes() == y.sizes(), op, ": dz must match y");
+  TORCH_CHECK(loss.numel() >= B && correct.numel() >= B, op, ": loss and correct must hold B entries");
+  TORCH_CHECK(dhead.numel() >= B * (Cr + 1), op, ": dhead too small");
+  TORCH_CHECK(dpass.numel() >= B, op, ": dpass must hold B entries");
+  TORCH_CHECK(dpw.numel() >= B * (2 * Cr + 1), op, ": dpw must hold (B, 2 C_real + 1)");
+  agk::PolicyHeadSoftPassArgs a{};
+  a.y = bfp(y);
+  a.w = w.data_ptr<float>(); a.b = b.data_ptr<float>();
+  a.pooled = pooled.data_ptr<float>(); a.pass_w = pass_w.data_ptr<float>(); a.pass_b = pass_b.data_ptr<float>();
+  a.tdist = tdist.data_ptr<float>();
+  a.dz = bfp_mut(dz);
+  a.loss = loss.data_ptr<float>(); a.correct = correct.data_ptr<float>(); a.dhead = dhead.data_ptr<float>();
+  a.dpass = dpass.data_ptr<float>(); a.dpw = dpw.data_ptr<float>();
+  a.B = (int)B; a.S = (int)S; a.C = (int)C; a.C_real = (int)Cr;
+  a.grad_scale = (float)grad_scale;
+  a.pooled_elems = pooled.numel(); a.tdist_elems = tdist.numel(); a.dpass_elems = dpass.numel(); a.dpw_elems = dpw.numel();
+  a.sym = head_sym(op, sym, B);
+  a.weight = head_board_weight(op, "weight", weight, B);
+  if (B == 0) return;
+  agk::launch_policy_head_soft_pass(a, cur_stream());
+  launch_check(op);
+}
+
+void policy_value_pass_head(const Tensor& y, const Tensor& wp, const Tensor& bp, const Tensor& wv, const Tensor& bv,
+                            const c10::optional<Tensor>& wo, const c10::optional<Tensor>& bo, const Tensor& pooled,
+                            const Tensor& pass_w, const Tensor& pass_b, const Tensor& probs, const Tensor& zv,
+                            const c10::optional<Tensor>& own, int64_t S, const c10::optional<Tensor>& legal) {
+  const char* op = "policy_value_pass_head";
+  check_dev(op, y, wp, bp, wv, bv, wo, bo, pooled, pass_w, pass_b, probs, zv, own, legal);
+  TORCH_CHECK(wo.has_value() == bo.has_value() && wo.has_value() == own.has_value(), op,
+              ": wo, bo and own go together (the ownership row)");
+  if (wo.has_value()) head_geometry(op, y, S, {&wp, &wv, &*wo}, {&bp, &bv, &*bo});
+  else head_geometry(op, y, S, {&wp, &wv}, {&bp, &bv});
+  TORCH_CHECK(y.numel() < (1ll << 31), op, ": tensor too large");
+  const int64_t B = y.size(0), C = y.size(3), SS = S * S;
+  pass_operands(op, pooled, pass_w, pass_b, B, C);
+  CHECK_F32(probs); CHECK_CONTIG(probs); CHECK_F32(zv); CHECK_CONTIG(zv);
+  TORCH_CHECK(probs.numel() == B * (SS + 1) && zv.numel() == B * SS, op, ": probs must be (B, S*S + 1) and zv (B, S*S)");
+  agk::PolicyValuePassHeadArgs a{};
+  a.y = bfp(y);
+  a.wp = wp.data_ptr<float>(); a.bp = bp.data_ptr<float>();
+  a.wv = wv.data_ptr<float>(); a.bv = bv.data_ptr<float>();
+  if (wo.has_value()) {
+    CHECK_F32(*own); CHECK_CONTIG(*own);
+    TORCH_CHECK(own->numel() == B * SS, op, ": own must be (B, S*S)");
+    a.wo = wo->data_ptr<float>(); a.bo = bo->data_ptr<float>(); a.own = own->data_ptr<float>();
+  }
+  a.pooled = pooled.data_ptr<float>(); a.pass_w = pass_w.data_ptr<float>(); a.pass_b = pass_b.data_ptr<float>();
+  a.probs = probs.data_ptr<float>(); a.zv = zv.data_ptr<float>();
+  a.B = (int)B; a.S = (int)S; a.C = (int)C; a.C_real = (int)wp.numel();
+  a.pooled_elems = pooled.numel(); a.probs_elems = probs.numel();
+  a.legal = head_legal(op, legal, B, S);
+  if (B == 0) return;
+  agk::launch_policy_value_pass_head(a, cur_stream());
+  launch_check(op);
+}
+
+void gpool_bwd_add_masked(const Tensor& dpass, const Tensor& pass_w, const Tensor& argmax, const Tensor& y,
+                          const Tensor& dz, int64_t S, double inv) {
+  const char* op = "gpool_bwd_add_masked";
+  check_dev(op, dpass, pass_w, argmax, y, dz);
+  const int64_t B = gpool_check_act(op, y, S), C = y.size(3);
+  gpool_check_act(op, dz, S);
+  TORCH_CHECK(dz.sizes() == y.sizes(), op, ": dz must have y's shape");
+  TORCH_CHECK(dpass.scalar_type() == at::kFloat && dpass.is_contiguous() && dpass.numel() >= B, op,
+              ": dpass must be contiguous float32 with B = ", B, " entries");
+  TORCH_CHECK(pass_w.scalar_type() == at::kFloat && pass_w.is_contiguous() && pass_w.dim() == 2 && pass_w.size(0) == 2 &&
+                  pass_w.size(1) == C, op, ": pass_w must be the contiguous float32 zero-padded (2, C) = (2, ", C, ") copy");
+  TORCH_CHECK(argmax.scalar_type() == at::kInt && argmax.is_contiguous() && argmax.dim() == 2 && argmax.size(0) == B &&
+                  argmax.size(1) == C, op, ": argmax must be contiguous int32 (B, C) = (", B, ", ", C, ")");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(argmax.data_ptr()) % 16 == 0, op, ": argmax must be 16-byte aligned");
+  agk::GpoolBwdAddArgs a{};
+  a.dpass = dpass.data_ptr<float>();
+  a.w = pass_w.data_ptr<float>();
+  a.argmax = argmax.data_ptr<int>();
+  a.y = bfp(y);
+  a.dz = bfp_mut(dz);
+  a.B = (int)B; a.S = (int)S; a.C = (int)C;
+  a.inv = (float)inv;
+  a.elems = dz.numel();
+  agk::launch_gpool_bwd_add_masked(a, cur_stream());
+  launch_check(op);
+}
+
 // A deliberately invalid launch (2048 threads per block, above the 1024
 // limit): the runtime rejects it, launch_check turns that into a Python
 // RuntimeError -- the test of the error path every op shares.
@@ -1292,6 +1403,13 @@ TORCH_LIBRARY(alphago_amd, m) {
   m.def("gpool_fwd(Tensor y, Tensor(a!) pooled, Tensor(b!)? argmax, int S, float inv) -> ()");
   m.def("gpool_bias_add(Tensor skip, Tensor g, Tensor(a!) out, int S) -> ()");
   m.def("gpool_bwd_fill(Tensor dp, Tensor argmax, Tensor(a!) out, int S, float inv) -> ()");
+  m.def("policy_head_soft_pass(Tensor y, Tensor w, Tensor b, Tensor pooled, Tensor pass_w, Tensor pass_b, Tensor tdist, "
+        "Tensor? sym, Tensor? weight, Tensor(a!) dz, Tensor(b!) loss, Tensor(c!) correct, Tensor(d!) dhead, "
+        "Tensor(e!) dpass, Tensor(f!) dpw, int S, float grad_scale) -> ()");
+  m.def("policy_value_pass_head(Tensor y, Tensor wp, Tensor bp, Tensor wv, Tensor bv, Tensor? wo, Tensor? bo, "
+        "Tensor pooled, Tensor pass_w, Tensor pass_b, Tensor(a!) probs, Tensor(b!) zv, Tensor(c!)? own, int S, "
+        "Tensor? legal=None) -> ()");
+  m.def("gpool_bwd_add_masked(Tensor dpass, Tensor pass_w, Tensor argmax, Tensor y, Tensor(a!) dz, int S, float inv) -> ()");
   m.def("pack_weights(Tensor[] ws, Tensor(a!)[] wf, Tensor(b!)[] wd) -> ()");
   m.def("sgd_update(Tensor(a!) p, Tensor g, float lr, float gscale) -> ()");
   m.def("comm_proxy(Tensor src, Tensor(a!) dst, int channels, float wire_us) -> ()");
@@ -1363,6 +1481,9 @@ TORCH_LIBRARY_IMPL(alphago_amd, CUDA, m) {
   m.impl("gpool_fwd", &gpool_fwd);
   m.impl("gpool_bias_add", &gpool_bias_add);
   m.impl("gpool_bwd_fill", &gpool_bwd_fill);
+  m.impl("policy_head_soft_pass", &policy_head_soft_pass);
+  m.impl("policy_value_pass_head", &policy_value_pass_head);
+  m.impl("gpool_bwd_add_masked", &gpool_bwd_add_masked);
   m.impl("head_logits", &head_logits);
   m.impl("head_backward", &head_backward);
   m.impl("head_backward_add", &head_backward_add);

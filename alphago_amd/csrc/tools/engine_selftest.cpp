@@ -194,6 +194,40 @@ int main(int argc, char** argv) {
     }
     CHECK(visits_by_threads[0] == visits_by_threads[1], "threaded search differs from serial search");
   }
+  // pass priors: every expanded node with a sensible move also gets a PASS child, stored last, with prior
+  // p / (sum + p); a search under a dominant pass prior passes, and advancing through the pass keeps the tree
+  {
+    std::vector<int> pf;
+    for (int f : {F_BOARD, F_ONES, F_SENSIBLENESS}) pf.push_back(f);
+    Forest forest(2, 5.0, 0.0, 60, 1000, 3, 11, pf);
+    forest.set_threads(2);
+    for (int t = 0; t < 2; ++t) forest.set_root(t, pool[(t * 7) % pool.size()]);
+    for (int round = 0; round < 20; ++round) {
+      int L = forest.gather(4);
+      if (L == 0) continue;
+      const int np = forest.leaf_state(0).np;
+      std::vector<float> pri((size_t)L * np, 1.f), val(L, 0.f), pp(L, 3.f * np);
+      forest.apply(pri.data(), val.data(), nullptr, pp.data());
+      if (round == 0) {
+        for (int t = 0; t < 2; ++t) {
+          std::vector<int> mv, vs;
+          std::vector<float> q;
+          forest.root_stats(t, mv, vs, q);
+          CHECK(mv.size() >= 2 && mv.back() == PASS, "tree %d: the last child is not PASS", t);
+          int passes = 0;
+          for (int m : mv) passes += m == PASS;
+          CHECK(passes == 1, "tree %d: %d PASS children", t, passes);
+        }
+      }
+    }
+    for (int t = 0; t < 2; ++t) {
+      // prior 3 np / (n + 3 np) >= 3/4 with n <= np sensible moves of prior 1 each
+      CHECK(forest.best_move(t, 0.0) == PASS, "tree %d: a dominant pass prior did not lead to a pass", t);
+      forest.advance(t, PASS);
+      check_invariants(forest.root_state(t));
+    }
+    std::printf("forest (pass priors): ok\n");
+  }
   if (g_fail) {
     std::printf("FAILED (%d checks)\n", g_fail);
     return 1;

@@ -102,8 +102,9 @@ def model_from_keras_json(spec: str):
 
 def pv_spec(net: PolicyValueNet) -> Dict:
     """The dual net's architecture (it is no Keras Sequential: a spec key of its own, ``pv_model``);
-    ``residual: 1`` only for a residual trunk, ``ownership: 1`` only with the ownership head and
-    ``gpool: k`` only with pooling branches, so the spec of a plain net is what it always was."""
+    ``residual: 1`` only for a residual trunk, ``ownership: 1`` only with the ownership head,
+    ``gpool: k`` only with pooling branches and ``pass_head: 1`` only with the pass head, so the spec of a
+    plain net is what it always was."""
     return dict(net.arch)
 
 
@@ -127,6 +128,8 @@ def _weights_in_order(net) -> List[Tuple[str, List[torch.Tensor]]]:
             out.append(("ownership_convolution2d_1", [net.ohead_w, net.ohead_b]))
         for i, g in enumerate(getattr(tr, "gpool_w", ()), 1):  # one entry per pooling branch, after the heads
             out.append(("gpool_dense_%d" % i, [g]))
+        if getattr(net, "pass_head", False):  # one more entry after the gpool entries
+            out.append(("pass_dense_1", [net.pass_w, net.pass_b]))
         return out
     names = _layer_names(net)
     out = []

@@ -563,7 +563,13 @@ class HipPolicyValueInference(HipTrunkInference):
     ``ownership=True`` (a net with the ownership head only; off by default, so search does not pay for
     it): ``policy_value_own_head`` takes the place of ``policy_value_head`` and also fills the bucket's
     ``own`` (B, S*S), tanh of the third head in the mover's frame.  The output rows stay (B, S*S + 1);
-    ``ownership_view`` gives the device rows of a submission."""
+    ``ownership_view`` gives the device rows of a submission.
+
+    A net with the pass head (``pass_head=1``): per bucket ``gpool_fwd`` pools the trunk output and
+    ``policy_value_pass_head`` takes the head's place (with ``ownership=True`` it fills ``own`` too), both
+    inside the captured graph.  The output rows are (B, S*S + 2), the S*S + 1 probabilities (the pass last)
+    and the value; ``split_outputs`` and ``evaluate`` return ``probs`` of shape (n, S*S + 1).  ``pass_head``
+    on the engine tells search to take the pass prior from the last column."""
 
     dual = True
 
@@ -574,8 +580,10 @@ class HipPolicyValueInference(HipTrunkInference):
         if ownership and not getattr(net, "ownership", False):
             raise ValueError("ownership=True needs a PolicyValueNet with the ownership head (ownership=1)")
         self.ownership = bool(ownership)
+        self.pass_head = bool(getattr(net, "pass_head", False))
         self.vhead = None
         self.ohead = None
+        self.phead = None
         super().__init__(net, device, **kw)
 
     def _after_sync(self):
@@ -592,37 +600,56 @@ class HipPolicyValueInference(HipTrunkInference):
                 self.ohead = [torch.empty(t.shape, dtype=torch.float32, device=self.device) for t in osrc]
             for dst, t in zip(self.ohead, osrc):
                 dst.copy_(t)
+        if self.pass_head:
+            if self.phead is None:  # [pass_w zero-padded (2, Fp), pass_b (1)], allocated once
+                self.phead = [torch.zeros(2, self.Fp, device=self.device), torch.zeros(1, device=self.device)]
+            self.phead[0][:, :self.F].copy_(n.pass_w.detach().view(2, self.F))
+            self.phead[1].copy_(n.pass_b.detach().view(-1))
+
+    @property
+    def NE(self) -> int:
+        """Entries of a probability row: S*S, with the pass head S*S + 1."""
+        return self.S * self.S + (1 if self.pass_head else 0)
 
     def _alloc_outputs(self, bk):
         SS = self.S * self.S
-        bk.probs = torch.zeros((bk.B, SS), device=self.device)
+        bk.probs = torch.zeros((bk.B, self.NE), device=self.device)
+        if self.pass_head:
+            bk.ps_P = torch.zeros((bk.B, 2, self.Fp), device=self.device)
+            bk.ps_arg = torch.zeros((bk.B, self.Fp), dtype=torch.int32, device=self.device)
         bk.z = torch.zeros((bk.B, SS), device=self.device)
         if self.ownership:
             bk.own = torch.zeros((bk.B, SS), device=self.device)
         bk.h = torch.zeros((bk.B, self.vhead[2].shape[1]), device=self.device)
         bk.values = torch.zeros((bk.B,), device=self.device)
-        bk.out = torch.zeros((bk.B, SS + 1), device=self.device)
+        bk.out = torch.zeros((bk.B, self.NE + 1), device=self.device)
 
     def _head(self, bk, y):
         vw, vb, w1, b1, w2, b2 = self.vhead
-        SS = self.S * self.S
-        if self.ownership:
+        NE = self.NE
+        if self.pass_head:
+            ops.gpool_fwd(y, bk.ps_P, bk.ps_arg, self.S)
+            own = dict(wo=self.ohead[0], bo=self.ohead[1], own=bk.own) if self.ownership else {}
+            ops.policy_value_pass_head(y, self.head_w, self.head_b, vw, vb, bk.ps_P, self.phead[0], self.phead[1],
+                                       bk.probs, bk.z, self.S, legal=bk.legal, **own)
+        elif self.ownership:
             ops.policy_value_own_head(y, self.head_w, self.head_b, vw, vb, self.ohead[0], self.ohead[1], bk.probs,
                                       bk.z, bk.own, self.S, legal=bk.legal)
         else:
             ops.policy_value_head(y, self.head_w, self.head_b, vw, vb, bk.probs, bk.z, self.S, legal=bk.legal)
         ops.dense_f32(bk.z, w1, bk.h, bias=b1)
         ops.value_out(bk.h, w2.view(-1), b2, bk.values)
-        bk.out[:, :SS].copy_(bk.probs)
-        bk.out[:, SS].copy_(bk.values)
+        bk.out[:, :NE].copy_(bk.probs)
+        bk.out[:, NE].copy_(bk.values)
 
     def _outputs(self, bk, n):
         return bk.out[:n]
 
     def split_outputs(self, out):
-        """(probs (n, S*S), values (n,)) views of output rows (device tensor or collect()'s numpy)."""
-        SS = self.S * self.S
-        return out[:, :SS], out[:, SS]
+        """(probs (n, S*S), with the pass head (n, S*S + 1), values (n,)) views of output rows (device tensor
+        or collect()'s numpy)."""
+        NE = self.NE
+        return out[:, :NE], out[:, NE]
 
     def ownership_view(self, handle=None):
         """Device rows (n, S*S) of the ownership head for the last submission (or ``handle``'s bucket,
@@ -639,7 +666,7 @@ class HipPolicyValueInference(HipTrunkInference):
 
     @torch.no_grad()
     def evaluate(self, planes, legal=None, slot: int = 0):
-        """As HipTrunkInference.evaluate; returns (probs (n, S*S), values (n,))."""
+        """As HipTrunkInference.evaluate; returns (probs (n, S*S), with the pass head (n, S*S + 1), values (n,))."""
         return self.split_outputs(super().evaluate(planes, legal, slot))
 
 
@@ -750,7 +777,8 @@ class TorchValueInference(_TorchSymmetries):
 
 class TorchPolicyValueInference:
     """CPU / fp32 oracle of the dual net: TorchPolicyInference._plain's and TorchValueInference's op
-    sequences on one shared trunk output.  ``evaluate`` returns (probs (n, S*S), values (n,))."""
+    sequences on one shared trunk output.  ``evaluate`` returns (probs (n, S*S), values (n,)); with the pass
+    head the rows have S*S + 1 entries, the pass last and always legal."""
 
     supports_encoded = False
     needs_ladder = False
@@ -766,6 +794,7 @@ class TorchPolicyValueInference:
             raise ValueError("ownership=True needs a PolicyValueNet with the ownership head (ownership=1)")
         self.net, self.device = net, torch.device(device)
         self.ownership = bool(ownership)
+        self.pass_head = bool(getattr(net, "pass_head", False))
         self._own = None
 
     def sync_weights(self):
@@ -789,7 +818,10 @@ class TorchPolicyValueInference:
         else:
             logits, values = self.net.logits_value_torch(x.float())
         if legal is not None:
-            logits = logits.masked_fill(torch.as_tensor(legal).to(self.device) == 0, float("-inf"))
+            legal = torch.as_tensor(legal).to(self.device)
+            if self.pass_head:  # (n, S*S + 1) logits: the pass is always legal
+                legal = torch.cat([legal, torch.ones_like(legal[:, :1])], 1)
+            logits = logits.masked_fill(legal == 0, float("-inf"))
         return torch.nan_to_num(torch.softmax(logits, 1), nan=0.0), values
 
 

@@ -72,6 +72,8 @@ def he_uniform_(net: nn.Module, generator=None) -> nn.Module:
             oh.uniform_(-bound, bound, generator=generator)
         for g in getattr(net.trunk, "gpool_w", ()):
             g.zero_()
+        if getattr(net, "pass_head", False):  # the last linear map of its branch: the pass logit starts at pass_b
+            net.pass_w.zero_()
     return net
 
 
@@ -272,10 +274,23 @@ class PolicyValueNet(nn.Module):
     ``ohead_b``) with a tanh per board point, the owner of the point at the end of the game in the
     mover's frame (+1 = the player to move); kept in ``arch`` only when set.  ``gpool = k``: a global pooling
     branch in every k-th block of a residual trunk (ConvStack; ``trunk.gpool_w``), kept in ``arch`` only when
-    set."""
+    set.
+
+    ``pass_head``: a learned pass logit next to the S*S board logits (``pass_w`` (2F, 1) in the Keras Dense
+    layout, ``pass_b`` (1)), kept in ``arch`` only when set.  With h = Y[L-1] the trunk output after its ReLU,
+    NP = S * S and inv = float32(1 / NP):
+
+        P[b, 0, c] = (sum_p h[b, p, c]) * inv
+        P[b, 1, c] = max_p h[b, p, c]             (ties: the lowest pixel index, which pins the gradient)
+        z_pass[b]  = P[b].reshape(2F) @ pass_w + pass_b
+        z[b]       = [1x1 policy head logits (NP), z_pass[b]]     (NP + 1 entries, the pass last)
+
+    ``pass_w`` is drawn after every other parameter (``trunk.gpool_w`` included) and zeroed by ``he_uniform_``;
+    a net without the head draws what it always drew."""
 
     def __init__(self, input_dim: int = 49, board: int = 19, filters_per_layer: int = 192, layers: int = 12,
-                 dense: int = 256, residual: int = 0, ownership: int = 0, gpool: int = 0, **kwargs):
+                 dense: int = 256, residual: int = 0, ownership: int = 0, gpool: int = 0, pass_head: int = 0,
+                 **kwargs):
         super().__init__()
         widths = [int(kwargs.get("filter_width_%d" % i, 5 if i == 1 else 3)) for i in range(1, layers + 1)]
         self.arch = dict(input_dim=input_dim, board=board, filters_per_layer=filters_per_layer, layers=layers,
@@ -289,6 +304,9 @@ class PolicyValueNet(nn.Module):
             self.arch["ownership"] = 1
         if gpool:
             self.arch["gpool"] = int(gpool)
+        if pass_head:
+            self.arch["pass_head"] = 1
+        self.pass_head = bool(pass_head)
         self.ownership = bool(ownership)
         self.board = board
         self.trunk = ConvStack(input_dim, filters_per_layer, layers, widths, residual=bool(residual),
@@ -308,6 +326,10 @@ class PolicyValueNet(nn.Module):
             self.ohead_b = nn.Parameter(torch.zeros(1))
             keras_uniform_(self.ohead_w)
         self.trunk.init_gpool()  # after every other parameter: they draw what they draw without the branch
+        if pass_head:  # last of all, for the same reason
+            self.pass_w = nn.Parameter(torch.empty(2 * filters_per_layer, 1))
+            self.pass_b = nn.Parameter(torch.zeros(1))
+            keras_uniform_(self.pass_w)
 
     @property
     def input_dim(self):
@@ -322,12 +344,36 @@ class PolicyValueNet(nn.Module):
             cin = self.trunk.filters
         d = self.arch["dense"]
         tot += len(self.trunk.gpool_blocks) * 2.0 * 2 * cin * cin  # the gates: Dense(2F -> F) per branch block
+        if self.pass_head:
+            tot += 2.0 * 2 * cin  # the pass logit: Dense(2F -> 1)
         return tot + (3 if self.ownership else 2) * (2.0 * s2 * cin) + 2.0 * s2 * d + 2.0 * d
+
+    def pass_logit_torch(self, h: torch.Tensor) -> torch.Tensor:
+        """(B,) pass logit from the trunk output (B, F, S, S): mean and max over the board (the max gathered at
+        the lowest pixel index attaining it), then the dense layer ``pass_w``, ``pass_b``."""
+        if not self.pass_head:
+            raise ValueError("this PolicyValueNet has no pass head (pass_head=1)")
+        B, C = h.shape[:2]
+        flat = h.reshape(B * C, -1)
+        flat = flat if flat.dtype == torch.float64 else flat.float()  # fp32 sums of a bf16 trunk; an fp64 oracle stays fp64
+        mean = flat.sum(1) * torch.tensor(1.0 / flat.shape[1], dtype=torch.float32).to(flat.dtype)
+        mx = flat.gather(1, first_argmax(flat.detach())[:, None])[:, 0]
+        P = torch.cat([mean.view(B, C), mx.view(B, C)], 1)
+        return (P @ self.pass_w.to(P.dtype)).squeeze(1) + self.pass_b.to(P.dtype)
+
+    def policy_logits_torch(self, h: torch.Tensor) -> torch.Tensor:
+        """Policy logits from the trunk output, in its dtype: (B, S*S) of the 1x1 head, with the pass head
+        (B, S*S + 1) with the pass logit last."""
+        z = F.conv2d(h, self.head_w.to(h.dtype), self.head_b.to(h.dtype)).flatten(1)
+        if self.pass_head:
+            z = torch.cat([z, self.pass_logit_torch(h).to(z.dtype)[:, None]], 1)
+        return z
 
     def heads_torch(self, h: torch.Tensor):
         """(policy logits (B, S*S), value (B,)) from the trunk output: PolicyNet.logits_torch's and
-        ValueNet.forward_torch's op sequences."""
-        z = F.conv2d(h, self.head_w.to(h.dtype), self.head_b.to(h.dtype)).flatten(1).float()
+        ValueNet.forward_torch's op sequences.  With the pass head the logits are (B, S*S + 1), the pass
+        last."""
+        z = self.policy_logits_torch(h).float()
         zv = F.conv2d(h, self.vhead_w.to(h.dtype), self.vhead_b.to(h.dtype)).flatten(1).float()
         zv = zv @ self.fc1_w + self.fc1_b
         return z, torch.tanh(zv @ self.fc2_w + self.fc2_b).squeeze(1)
@@ -343,7 +389,7 @@ class PolicyValueNet(nn.Module):
         return self.heads_torch(self.trunk.forward_torch(x))
 
     def forward(self, x: torch.Tensor):
-        """x: (B, C, S, S) float/uint8 planes -> (probs (B, S*S), value (B,))."""
+        """x: (B, C, S, S) float/uint8 planes -> (probs (B, S*S), or (B, S*S + 1) with the pass head, value (B,))."""
         if x.dtype == torch.uint8:
             x = x.float()
         z, v = self.logits_value_torch(x)

@@ -225,7 +225,8 @@ class CNNPolicyValue(_NetWrapper):
 
     # ----------------------------------------------------------- evaluation
     def forward(self, planes, legal=None):
-        """(B, F, S, S) planes -> (probs (B, S*S), values (B,)) numpy."""
+        """(B, F, S, S) planes -> (probs (B, S*S), values (B,)) numpy; a net with the pass head gives
+        (B, S*S + 1) with the pass last (the move lists of ``eval_state`` read the board part only)."""
         planes = np.asarray(planes)
         if planes.dtype != np.uint8:
             planes = planes.astype(np.uint8)

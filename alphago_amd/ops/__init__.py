@@ -465,6 +465,35 @@ def gpool_bwd_fill(dp, argmax, out, S: int):
     return out
 
 
+def policy_head_soft_pass(y, w, b, pooled, pass_w, pass_b, tdist, dz, loss, correct, dhead, dpass, dpw, S: int,
+                          grad_scale: float, weight=None, sym=None):
+    """``policy_head_train_soft`` for a net with the pass head: the softmax, the loss, ``correct`` and the
+    gradient run over S*S + 1 entries, the pass last.  ``pooled`` (B, 2, C) is ``gpool_fwd(y)``, ``pass_w`` the
+    zero-padded (2, C) copy of the net's (2F, 1) weight, ``pass_b`` (1); z_pass = pooled . pass_w + pass_b.
+    ``tdist`` must be (B, S*S + 1); its board part moves with ``sym``, the pass entry does not.  Besides
+    ``policy_head_train_soft``'s outputs: ``dpass`` (B) = dL/dz_pass and ``dpw`` (B, 2 C_real + 1) =
+    [dpass * pooled | dpass] per board, the partials ``head_grad_sums`` turns into d pass_w and d pass_b."""
+    _ops().policy_head_soft_pass(y, w, b, pooled, pass_w, pass_b, tdist, sym, weight, dz, loss, correct, dhead, dpass,
+                                 dpw, S, float(grad_scale))
+
+
+def policy_value_pass_head(y, wp, bp, wv, bv, pooled, pass_w, pass_b, probs, zv, S: int, legal=None, wo=None, bo=None,
+                           own=None):
+    """``policy_value_head`` (with ``wo``, ``bo``, ``own``: ``policy_value_own_head``) for a net with the pass
+    head: ``probs`` (B, S*S + 1) is the softmax at temperature 1 over the legal board points and the pass,
+    which is always legal; ``zv`` and ``own`` carry the other op's bits."""
+    _ops().policy_value_pass_head(y, wp, bp, wv, bv, wo, bo, pooled, pass_w, pass_b, probs, zv, own, S, legal)
+
+
+def gpool_bwd_add_masked(dpass, pass_w, argmax, y, dz, S: int):
+    """The pass head's pooling gradient, accumulated into the top layer's ``dz`` where ``y`` > 0:
+    dz[b, p, c] = bf16(float(dz[b, p, c]) + (dpass[b] * pass_w[0, c] * inv + (p == argmax[b, c] ?
+    dpass[b] * pass_w[1, c] : 0))), inv = float32(1 / S*S), every product and sum rounded separately.
+    Interior only; elements with ``y`` <= 0 keep their bits."""
+    _ops().gpool_bwd_add_masked(dpass, pass_w, argmax, y, dz, S, gpool_inv(S))
+    return dz
+
+
 def pack_weights(ws, wf, wd=()):
     _ops().pack_weights(list(ws), list(wf), list(wd))
 

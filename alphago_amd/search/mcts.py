@@ -48,6 +48,14 @@ def _fallback_eval_dual(engine, planes, masks=None):
     return p.float().cpu().numpy(), v.float().cpu().numpy()
 
 
+def _split_pass(engine, probs: np.ndarray):
+    """(board priors (L, S*S), pass priors (L,) or None) of a dual engine's probability rows: an engine of a
+    net with the pass head returns S*S + 1 entries per row, the pass last."""
+    if not getattr(engine, "pass_head", False):
+        return probs, None
+    return np.ascontiguousarray(probs[:, :-1]), np.ascontiguousarray(probs[:, -1])
+
+
 class _ForestGroup(object):
     """Several native Forests presented as one (tree t -> (forest, local index))."""
 
@@ -219,7 +227,7 @@ class BatchedMCTS(object):
         # mask: sensible moves from the GPU featurizer, so apply() skips its own scan
         probs, mask, bad = pe.collect(hp)
         values = None
-        if self._dual:  # rows of S*S probabilities and the value, from the one submission
+        if self._dual:  # rows of S*S probabilities (S*S + 1 with the pass head) and the value, from the one submission
             probs, values = pe.split_outputs(probs)
             values = np.array(values, dtype=np.float32, copy=True)
         probs = np.array(probs, copy=True)
@@ -244,7 +252,8 @@ class BatchedMCTS(object):
             mask[bad] = masks
             if ve is not None:
                 values[bad] = _fallback_eval(ve, self.value.preprocessor.states_to_uint8(states))
-        f.apply(probs, values, mask)
+        probs, pass_priors = _split_pass(pe, probs) if self._dual else (probs, None)
+        f.apply(probs, values, mask, pass_priors)
 
     def _evaluate_encoded(self, pe, ve, f=None, slot: int = 0) -> None:
         f = f if f is not None else self._forests[0]
@@ -278,7 +287,8 @@ class BatchedMCTS(object):
                 states = [f.leaf_state(i) for i in range(L)]
                 vplanes = self.value.preprocessor.states_to_uint8(states)
             values = self.value.engine.evaluate(vplanes).float().cpu().numpy()
-        f.apply(probs, values)
+        probs, pass_priors = _split_pass(self.policy.engine, probs) if self._dual else (probs, None)
+        f.apply(probs, values, None, pass_priors)
 
     def _sync_roots(self, states: Sequence, which: Optional[Sequence[int]] = None) -> None:
         """Bring tree i's root to states[i]: advance through the moves played since (subtree reuse,

@@ -1303,6 +1303,22 @@ def _pv_targets(targets, ownership: bool = False):
     return targets[0], targets[1], None
 
 
+def pass_target_rows(moves: torch.Tensor, NP: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B, NP + 1) one-hot rows of hard move targets for a net with the pass head: a move of -1 (a pass) has
+    its 1 at column NP.  The rows take the soft-target path, which moves them with the board."""
+    idx = moves.long().view(-1)
+    idx = torch.where(idx < 0, torch.full_like(idx, NP), idx)
+    rows = torch.zeros(idx.numel(), NP + 1, device=moves.device) if out is None else out.zero_()
+    return rows.scatter_(1, idx[:, None], 1.0)
+
+
+def _pass_rows_checked(pi, batch: int, NP: int):
+    if tuple(pi.shape) != (batch, NP + 1):
+        raise ValueError("a net with the pass head takes soft targets of shape (%d, %d) with the pass last (a row "
+                         "of %d has no pass entry), got %s" % (batch, NP + 1, NP, tuple(pi.shape)))
+    return pi
+
+
 def own_agreement_share(own, own_t):
     """Per board, the share of the points with a non-zero target whose sign ``own`` matches (0 for a
     board without such points): the trainers' sixth metric before the sum over valid boards."""
@@ -1341,6 +1357,15 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
     the step of a net without the head, leaves ``ohead_*`` without gradient and reports 0 for both.
     A net without the head launches exactly the kernels above and returns four sums.
 
+    A net with the pass head (``PolicyValueNet(pass_head=1)``): the policy softmax, loss and top-1 run over
+    S*S + 1 entries, the pass last.  Soft targets must be (B, S*S + 1); hard moves become one-hot rows of that
+    width (a move of -1, a pass, at column S*S) and take the same path.  Per step: ``gpool_fwd(Y[L-1])``, then
+    ``policy_head_soft_pass`` in the soft head's place; the value and ownership steps unchanged;
+    ``gpool_bwd_add_masked`` adds the pooling's ReLU'-masked gradient into dZ[L-1] last; one more
+    ``head_grad_sums`` for ``pass_w`` / ``pass_b``, which follow the ownership entries in the flat parameters.
+    The metric sums are the same; policy loss and top-1 now count pass rows.  A net without the head
+    launches exactly the kernels above.
+
     fp8: the head writes the bf16 dZ only (``_top_e5m2_fusable`` is False: a sum of two heads cannot
     be accumulated in e5m2), so an fp8 backward works through the unfused ``quantize_bf8`` pass over
     the summed dZ[L-1], the policy trainer's path.  Graph mode and the regularised head options
@@ -1351,6 +1376,7 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
         self.value_coef = float(value_coef)
         self.own_coef = float(own_coef)
         self.has_own = bool(getattr(net, "ownership", False))
+        self.has_pass = bool(getattr(net, "pass_head", False))
         super().__init__(net, batch, lr, decay, **kw)
 
     def _head_named_params(self):
@@ -1359,11 +1385,22 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
                  ("fc1_w", n.fc1_w), ("fc1_b", n.fc1_b), ("fc2_w", n.fc2_w), ("fc2_b", n.fc2_b)]
         if self.has_own:  # appended: the existing segments keep their offsets
             named += [("ohead_w", n.ohead_w), ("ohead_b", n.ohead_b)]
+        if self.has_pass:  # after the ownership entries
+            named += [("pass_w", n.pass_w), ("pass_b", n.pass_b)]
         return named
 
     def _init_head(self):
         super()._init_head()
         B, NP, dev = self.batch, self.S * self.S, self.device
+        if self.has_pass:
+            F, Fp = self.F, self.Fp
+            self._ps_P = torch.zeros(B, 2, Fp, device=dev)
+            self._ps_arg = torch.zeros(B, Fp, dtype=torch.int32, device=dev)
+            self._ps_d = torch.zeros(B, device=dev)
+            self._ps_dpw = torch.zeros(B, 2 * F + 1, device=dev)
+            self._ps_rows = torch.zeros(B, NP + 1, device=dev)
+            # the kernels read a (2, Fp) weight: the flat view itself, or a zero-padded copy (repack)
+            self._ps_w = self.fp.views["pass_w"].view(2, F) if F == Fp else torch.zeros(2, Fp, device=dev)
         D = self.net.fc1_w.shape[1]
         self.z = torch.zeros(B, NP, device=dev)
         self.h = torch.zeros(B, D, device=dev)
@@ -1384,10 +1421,36 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
             self.own_t = torch.zeros(B, NP, dtype=torch.int8, device=dev)
             self.own_valid = torch.zeros(B, device=dev)
 
+    def repack(self, bf16: bool = True) -> None:
+        super().repack(bf16)
+        if self.has_pass and self.F < self.Fp:  # the pass head's zero-padded weight copy
+            self._ps_w[:, :self.F].copy_(self.fp.views["pass_w"].view(2, self.F))
+
     def enable_graphs(self, on: bool = True) -> None:
         if on:
             raise RuntimeError(_PV_NO_GRAPH)
         super().enable_graphs(False)
+
+    def _pass_pi(self, pi):
+        """The policy target of a pass-head net as (B, S*S + 1) rows: soft rows checked, hard moves as one-hot
+        rows in the planes' original frame (the head kernel moves them with ``sym``)."""
+        NP = self.S * self.S
+        if is_soft_target(pi):
+            return _pass_rows_checked(pi, self.batch, NP)
+        if pi.numel() != self.batch:
+            raise ValueError("move targets must hold %d entries, got %d" % (self.batch, pi.numel()))
+        return pass_target_rows(pi.to(self.device), NP, self._ps_rows)
+
+    def _head_soft(self, dist, gscale, weight, sym) -> None:
+        if not self.has_pass:
+            return super()._head_soft(dist, gscale, weight, sym)
+        if dist.dtype != torch.float32 or not dist.is_contiguous():
+            dist = dist.float().contiguous()
+        v = self.fp.views
+        ops.gpool_fwd(self.Y[-1], self._ps_P, self._ps_arg, self.S)
+        ops.policy_head_soft_pass(self.Y[-1], v["head_w"].view(-1), v["head_b"], self._ps_P, self._ps_w, v["pass_b"],
+                                  dist, self.DZ[-1], self.loss, self.correct, self.dhead, self._ps_d, self._ps_dpw,
+                                  self.S, gscale, weight=weight, sym=sym)
 
     def _top_e5m2_fusable(self) -> bool:
         return False
@@ -1405,6 +1468,8 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
             raise ValueError("outcomes must hold %d entries, got %d" % (self.batch, z.numel()))
         if own is not None:
             self._check_own(own)
+        if self.has_pass:
+            pi = self._pi_rows = self._pass_pi(pi)  # converted once per step: _head_train takes these rows
         super()._forward_for_head(planes, pi, sym)
 
     def _check_own(self, own) -> None:
@@ -1437,6 +1502,8 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
     def _head_train(self, targets, gscale, weight, sym=None):
         pi, z, own = _pv_targets(targets, self.has_own)
         v, gv = self.fp.views, self.fp.grad_views
+        if self.has_pass:  # (B, S*S + 1) rows, hard moves included (_forward_for_head made them)
+            pi = self._pi_rows
         # 1. the policy head, unchanged: dZ[L-1] and its [dW_head | db_head] partials
         if is_soft_target(pi):
             self._head_soft(pi, gscale, weight, sym)
@@ -1479,6 +1546,13 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
             else:  # a pair: no ownership term
                 self._ometric_sums = torch.zeros(2, device=self.device)
                 self.fp.grad[oo:oo + on + 1].zero_()
+        if self.has_pass:
+            # 5. the pass head: its pooling's ReLU'-masked gradient into dZ[L-1], last of the accumulations,
+            #    and [d pass_w | d pass_b] from the per-board partial rows
+            ops.gpool_bwd_add_masked(self._ps_d, self._ps_w, self._ps_arg, self.Y[-1], self.DZ[-1], self.S)
+            po, pn = self.fp.segments["pass_w"]
+            ops.head_grad_sums(self._ps_dpw, self.loss, self.correct, self.fp.grad[po:po + pn + 1],
+                               torch.empty(2, device=self.device))
 
     def step(self, planes, targets, sym: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None,
              rows: Optional[torch.Tensor] = None):
@@ -1510,6 +1584,8 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
         pi, z, own = _pv_targets(targets, self.has_own)
         if own is not None:
             self._check_own(own)
+        if self.has_pass:
+            pi = self._pass_pi(pi)
         pl, pc = super().evaluate(planes, pi)  # leaves the trunk output in Y[-1]
         if own is not None:
             self._own_forward(own, None, None, 0.0)
@@ -1720,15 +1796,20 @@ class TorchPolicyValueTrainer(_TorchTrainerBase):
         self.value_coef = float(value_coef)
         self.own_coef = float(own_coef)
         self.has_own = bool(getattr(net, "ownership", False))
+        self.has_pass = bool(getattr(net, "pass_head", False))
         named = _trunk_named(net.trunk) + [(n, getattr(net, n)) for n in (
             "head_w", "head_b", "vhead_w", "vhead_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b") +
-            (("ohead_w", "ohead_b") if self.has_own else ())]
+            (("ohead_w", "ohead_b") if self.has_own else ()) + (("pass_w", "pass_b") if self.has_pass else ())]
         self._setup(net, batch, lr, decay, device, dtype, iterations, named, optimizer, momentum, nesterov)
 
     def _loss(self, planes, targets, sym, weight):
         if self.policy_loss != "ce" or self.ent_coef or self.kl_coef or self.collect_stats or self.collect_probs:
             raise ValueError(_PV_REFUSED)
         pi, z, own = _pv_targets(targets, self.has_own)
+        if self.has_pass:  # logits of S*S + 1 entries: rows with the pass last, hard moves as one-hot rows
+            NP = self.net.board ** 2
+            pi = (_pass_rows_checked(pi, planes.shape[0], NP) if is_soft_target(pi)
+                  else pass_target_rows(pi.to(planes.device), NP))
         soft = is_soft_target(pi)
         if own is not None:
             own_t, own_valid = own[0].to(self.dtype), own[1].to(self.dtype)

@@ -7,7 +7,9 @@ step: cross-entropy of the policy head against the search's visit distribution (
 the soft-target head, rows at their full S*S + 1 width) or against the played move
 (``--targets played``), plus ``--value-coef`` times the squared error of the value head against the
 game outcome for the player to move.  A position whose visit mass is all on the pass has no policy
-loss and still trains the value head.
+loss and still trains the value head -- unless the model has the pass head (``init-model pv --pass-head``):
+then the policy softmax has S*S + 1 entries, the pass column is a target like any other and a played pass
+(move -1) is the one-hot row of the pass.
 
 A model with the ownership head (``init-model pv --ownership``) also reads ``ownership`` and
 ``ownership_valid`` (``selfplay-mcts --ownership``) and adds ``--ownership-coef`` times the mean squared
@@ -38,7 +40,7 @@ from ..io.h5lite import H5File
 from ..models.policy import CNNPolicyValue
 from ..parallel import dist as agdist
 from ..utils.metrics import MetricsLogger
-from .engine import make_policy_value_trainer
+from .engine import make_policy_value_trainer, pass_target_rows
 from .sl import MetadataWriter
 
 _KEYS = ("loss", "acc", "value_loss", "value_acc")
@@ -173,6 +175,8 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
         zt = _pad(torch.from_numpy(z[idx]).to(dev), B, 0.0)
         if moves is None:
             tgt = _pad(torch.from_numpy(pi[idx]).to(dev), B, 0.0)
+        elif getattr(net, "pass_head", False):  # -1 is a played pass here: one-hot rows, padded with no-loss rows
+            tgt = _pad(pass_target_rows(torch.from_numpy(moves[idx]).to(dev), S * S), B, 0.0)
         else:
             tgt = _pad(torch.from_numpy(moves[idx]).to(dev), B, -1)
         if own is not None:  # padding rows are invalid: no ownership term
