@@ -22,6 +22,32 @@ inline void hip_check(hipError_t e, const char* what) {
   if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// Debug build (AGK_DEBUG): device bounds checks of the head and pooling kernels (the conv kernels keep
+// their coded AGK_DCHECK, conv_common.h).  AGK_BOUNDS_CHECK(cond) evaluates to cond; when it is false it sets
+// the translation unit's error word and the caller redirects the access to element 0.  A launcher of that
+// translation unit then calls bounds_debug_check, which waits for the stream and raises on the word.  The
+// production build holds neither the word nor the checks.
+#ifdef AGK_DEBUG
+[[maybe_unused]] static __device__ unsigned g_bounds_err;
+#define AGK_BOUNDS_CHECK(cond) ((cond) ? true : (atomicOr(&::agk::g_bounds_err, 1u), false))
+[[maybe_unused]] static void bounds_debug_check(const char* what, hipStream_t st) {
+  hip_check(hipStreamSynchronize(st), "debug: stream synchronize");
+  unsigned code = 0, zero = 0;
+  hip_check(hipMemcpyFromSymbol(&code, HIP_SYMBOL(g_bounds_err), sizeof(code)), "debug: read error word");
+  if (code) {
+    hip_check(hipMemcpyToSymbol(HIP_SYMBOL(g_bounds_err), &zero, sizeof(zero)), "debug: clear error word");
+    throw std::runtime_error(std::string(what) + ": device bounds check failed (debug build)");
+  }
+}
+#else
+#define AGK_BOUNDS_CHECK(cond) true
+inline void bounds_debug_check(const char*, hipStream_t) {}
+#endif
+// index i into a tensor of n elements, 0 after a failed debug check
+__device__ __forceinline__ long long bounds_at(long long i, long long n) {
+  return AGK_BOUNDS_CHECK(i >= 0 && i < n) ? i : 0;
+}
+
 // Exact unsigned division by a runtime constant d (x < 2^32, d < 2^16):
 // q = (x * m) >> 40 with m = ceil(2^40 / d), computed once on the host.
 struct FastDiv {

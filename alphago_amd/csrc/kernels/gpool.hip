@@ -20,23 +20,8 @@
 
 namespace agk {
 
-#ifdef AGK_DEBUG
-// Debug build: every 16-byte activation access is checked against the tensor's extent; a violation sets
-// this word and the access is redirected to element 0.  The launchers wait and raise on it.
-static __device__ unsigned g_gpool_err;
-#define GPOOL_DCHECK(cond) ((cond) ? true : (atomicOr(&::agk::g_gpool_err, 1u), false))
-static void gpool_debug_check(const char* what, hipStream_t st) {
-  hip_check(hipStreamSynchronize(st), "debug: stream synchronize");
-  unsigned code = 0, zero = 0;
-  hip_check(hipMemcpyFromSymbol(&code, HIP_SYMBOL(g_gpool_err), sizeof(code)), "debug: read error word");
-  if (code) {
-    hip_check(hipMemcpyToSymbol(HIP_SYMBOL(g_gpool_err), &zero, sizeof(zero)), "debug: clear error word");
-    throw std::runtime_error(std::string(what) + ": device bounds check failed (debug build)");
-  }
-}
-#else
-#define GPOOL_DCHECK(cond) true
-#endif
+// Debug build: every 16-byte activation access is checked against the tensor's extent (AGK_BOUNDS_CHECK,
+// common.h); a violation redirects the access to element 0, and the launchers wait and raise on it.
 
 constexpr int kGpoolNT = 512;          // threads of a gpool_fwd workgroup
 constexpr int kGpoolSlots = 8 * kGpoolNT;  // PG * C <= 8 * NT partials per quantity
@@ -72,7 +57,7 @@ __global__ __launch_bounds__(kGpoolNT) void gpool_fwd_kernel(GpoolFwdArgs a) {
 #pragma unroll 4
     for (int p = pg; p < NP; p += PG) {
       int64_t o = gpool_pixel(b, p, a.S, C) + cg * 8;
-      if (!GPOOL_DCHECK(o >= 0 && o + 8 <= a.y_elems)) o = 0;
+      if (!AGK_BOUNDS_CHECK(o >= 0 && o + 8 <= a.y_elems)) o = 0;
       const bf16x8 v = *(const bf16x8*)(a.y + o);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -126,9 +111,7 @@ void launch_gpool_fwd(const GpoolFwdArgs& a, hipStream_t st) {
     throw std::invalid_argument("gpool_fwd: C must be a multiple of 8 in 8..512 and B >= 1");
   if (a.argmax) hipLaunchKernelGGL(gpool_fwd_kernel<true>, dim3(a.B), dim3(kGpoolNT), 0, st, a);
   else hipLaunchKernelGGL(gpool_fwd_kernel<false>, dim3(a.B), dim3(kGpoolNT), 0, st, a);
-#ifdef AGK_DEBUG
-  gpool_debug_check("gpool_fwd", st);
-#endif
+  bounds_debug_check("gpool_fwd", st);
 }
 
 // The two elementwise kernels.  Workgroup (b, s) covers board b; thread (pg, cg) as in gpool_fwd keeps the 8
@@ -176,7 +159,7 @@ __global__ __launch_bounds__(kGpoolNT) void gpool_map_kernel(GpoolMapArgs a) {
 #pragma unroll 4
   for (int p = pg + PG * blockIdx.y; p < NP; p += PG * gridDim.y) {
     int64_t o = gpool_pixel(b, p, a.S, C) + cg * 8;
-    if (!GPOOL_DCHECK(o >= 0 && o + 8 <= a.elems)) o = 0;
+    if (!AGK_BOUNDS_CHECK(o >= 0 && o + 8 <= a.elems)) o = 0;
     bf16x8 r;
     if (FILL) {
       r = base;
@@ -200,9 +183,7 @@ void launch_gpool_map(const GpoolMapArgs& a, bool fill, hipStream_t st) {
   ny = ny > 8 ? 8 : ny;
   if (fill) hipLaunchKernelGGL(gpool_map_kernel<true>, dim3(a.B, ny), dim3(kGpoolNT), 0, st, a);
   else hipLaunchKernelGGL(gpool_map_kernel<false>, dim3(a.B, ny), dim3(kGpoolNT), 0, st, a);
-#ifdef AGK_DEBUG
-  gpool_debug_check(fill ? "gpool_bwd_fill" : "gpool_bias_add", st);
-#endif
+  bounds_debug_check(fill ? "gpool_bwd_fill" : "gpool_bias_add", st);
 }
 
 // The pass head's pooling gradient added into the dZ of the trunk's top layer (gpool_map_kernel's layout, a
@@ -235,7 +216,7 @@ __global__ __launch_bounds__(kGpoolNT) void gpool_bwd_add_masked_kernel(GpoolBwd
 #pragma unroll 4
   for (int p = pg + PG * blockIdx.y; p < NP; p += PG * gridDim.y) {
     int64_t o = gpool_pixel(b, p, a.S, C) + cg * 8;
-    if (!GPOOL_DCHECK(o >= 0 && o + 8 <= a.elems)) o = 0;
+    if (!AGK_BOUNDS_CHECK(o >= 0 && o + 8 <= a.elems)) o = 0;
     const bf16x8 v = *(const bf16x8*)(a.y + o);
     bf16x8 r = *(const bf16x8*)(a.dz + o);
 #pragma unroll
@@ -251,9 +232,7 @@ void launch_gpool_bwd_add_masked(const GpoolBwdAddArgs& a, hipStream_t st) {
   int ny = (512 + a.B - 1) / a.B;  // launch_gpool_map's split
   ny = ny > 8 ? 8 : ny;
   hipLaunchKernelGGL(gpool_bwd_add_masked_kernel, dim3(a.B, ny), dim3(kGpoolNT), 0, st, a);
-#ifdef AGK_DEBUG
-  gpool_debug_check("gpool_bwd_add_masked", st);
-#endif
+  bounds_debug_check("gpool_bwd_add_masked", st);
 }
 
 }  // namespace agk

@@ -16,6 +16,11 @@
 // policy_value_own_head: policy_value_head_body (policy_head.h) with the ownership row, for inference;
 // probs and zv carry policy_value_head's bits.
 //
+// policy_value_pass_head: the same body with the pass entry (PASS) in the softmax, with the ownership row
+// (head.wo given) or without; probs rows have S * S + 1 entries, zv (and own) carry policy_value_head's
+// (policy_value_own_head's) bits.  It lives here because its arguments are policy_value_own_head's plus
+// the pass operands.
+//
 // No atomics: every sum has a fixed order.
 #include <hip/hip_runtime.h>
 
@@ -114,6 +119,27 @@ void launch_policy_value_own_head(const PolicyValueOwnHeadArgs& a, hipStream_t s
     hipLaunchKernelGGL((policy_value_own_head_kernel<512, BoardRows<512>>), dim3(a.pv.B), dim3(512), 0, st, a);
   else
     hipLaunchKernelGGL((policy_value_own_head_kernel<1024, BoardRegs<1024>>), dim3(a.pv.B), dim3(1024), 0, st, a);
+}
+
+template <int NT, class Board, bool OWN>
+__global__ __launch_bounds__(NT) void policy_value_pass_head_kernel(PolicyValuePassHeadArgs a) {
+  policy_value_head_body<NT, Board, OWN, true>(a.head.pv, a.head.wo, a.head.bo, a.head.own, a.pass);
+}
+
+template <bool OWN>
+static void policy_value_pass_head_go(const PolicyValuePassHeadArgs& a, hipStream_t st) {
+  const int B = a.head.pv.B;
+  if (head_rows_mapping(B, a.head.pv.S, a.head.pv.C))
+    hipLaunchKernelGGL((policy_value_pass_head_kernel<512, BoardRows<512>, OWN>), dim3(B), dim3(512), 0, st, a);
+  else
+    hipLaunchKernelGGL((policy_value_pass_head_kernel<1024, BoardRegs<1024>, OWN>), dim3(B), dim3(1024), 0, st, a);
+}
+
+void launch_policy_value_pass_head(const PolicyValuePassHeadArgs& a, hipStream_t st) {
+  head_check_geometry("policy_value_pass_head", a.head.pv.B, a.head.pv.S, a.head.pv.C, a.head.pv.C_real);
+  if (a.head.wo) policy_value_pass_head_go<true>(a, st);
+  else policy_value_pass_head_go<false>(a, st);
+  bounds_debug_check("policy_value_pass_head", st);
 }
 
 }  // namespace agk

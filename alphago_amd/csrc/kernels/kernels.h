@@ -498,49 +498,30 @@ struct GpoolMapArgs {
 // dp[b][1][c] : 0)), product and sum rounded separately
 void launch_gpool_map(const GpoolMapArgs& a, bool fill, hipStream_t st);
 
-// The pass head of the dual net (head_pass.hip; the pooling gradient in gpool.hip): one more policy logit
+// The pass head of the dual net (the pooling gradient in gpool.hip): one more policy logit
 // z_pass[b] = pooled[b].reshape(2 C) . pass_w + pass_b from gpool_fwd's (B, 2, C) of the trunk output, the
-// softmax over S*S + 1 entries with the pass last.  The *_elems fields are tensor extents for the debug
-// build's bounds checks.
-struct PolicyHeadSoftPassArgs {
-  const __bf16* y;       // padded NHWC (HP = S+2, P = 1, C)
-  const float* w;        // [C_real] policy head
-  const float* b;        // [1]
+// softmax over S*S + 1 entries with the pass last.  Both pass kernels take their plain sibling's arguments
+// plus these operands; the *_elems fields are tensor extents for the debug build's bounds checks.
+struct PassHeadOperands {
   const float* pooled;   // [B][2][C] gpool_fwd(y)
   const float* pass_w;   // [2][C] zero-padded copy of the (2 C_real, 1) weight
   const float* pass_b;   // [1]
-  const float* tdist;    // [B][S*S + 1] target distribution, pass last (PolicyHeadSoftArgs' conventions)
-  const int* sym;        // [B] in 0..7 or null; the pass entry does not move
-  const float* weight;   // [B] or null
-  __bf16* dz;            // padded NHWC grad (overwritten as by policy_head_soft)
-  float* loss;           // [B]
-  float* correct;        // [B]
-  float* dhead;          // [B][C_real + 1] partials of the 1x1 policy head
-  float* dpass;          // [B] dL/dz_pass
-  float* dpw;            // [B][2 C_real + 1] partials [dzp * pooled (2 C_real) | dzp]
-  int B, S, C, C_real;
-  float grad_scale;
-  long long pooled_elems, tdist_elems, dpass_elems, dpw_elems;
+  float* dpass;          // [B] dL/dz_pass                                              (training head)
+  float* dpw;            // [B][2 C_real + 1] partials [dzp * pooled (2 C_real) | dzp]  (training head)
+  long long pooled_elems, tdist_elems, dpass_elems, dpw_elems, probs_elems;
+};
+// policy_head_soft over S*S + 1 entries (head_soft.hip): head.tdist rows are [S*S + 1] with the pass last
+// (head.T == S*S + 1); the board part moves with sym, the pass entry does not
+struct PolicyHeadSoftPassArgs {
+  PolicyHeadSoftArgs head;
+  PassHeadOperands pass;
 };
 void launch_policy_head_soft_pass(const PolicyHeadSoftPassArgs& a, hipStream_t st);
-// policy_value_head / policy_value_own_head (wo given) with the pass entry: probs rows of S*S + 1
+// policy_value_head / policy_value_own_head (head.wo given) with the pass entry (head_own.hip): probs rows of
+// S*S + 1; the pass is always legal
 struct PolicyValuePassHeadArgs {
-  const __bf16* y;
-  const float* wp;       // [C_real]
-  const float* bp;       // [1]
-  const float* wv;       // [C_real]
-  const float* bv;       // [1]
-  const float* wo;       // [C_real] or null (no ownership row)
-  const float* bo;       // [1] or null
-  const float* pooled;   // [B][2][C]
-  const float* pass_w;   // [2][C]
-  const float* pass_b;   // [1]
-  const uint8_t* legal;  // [B][S*S] or null; the pass is always legal
-  float* probs;          // [B][S*S + 1]
-  float* zv;             // [B][S*S]
-  float* own;            // [B][S*S] (with wo)
-  int B, S, C, C_real;
-  long long pooled_elems, probs_elems;
+  PolicyValueOwnHeadArgs head;  // wo, bo, own null: no ownership row
+  PassHeadOperands pass;
 };
 void launch_policy_value_pass_head(const PolicyValuePassHeadArgs& a, hipStream_t st);
 // dz += ReLU'(y) * (dpass[b] * w[0][c] * inv + (p == argmax[b][c] ? dpass[b] * w[1][c] : 0)), interior only

@@ -278,24 +278,18 @@ void policy_head(const Tensor& y, const Tensor& w, const Tensor& b, const c10::o
   launch_check("policy_head");
 }
 
-// Soft-target training head (head_soft.hip): tdist (B, S*S or S*S + 1) f32 is a target distribution per
-// board in the planes' original frame, sym the symmetry pack_input gave the board.  Only what the schema
-// names exists here: no legal mask, temperature, binary-CE loss, entropy / KL terms, stats, probs or e5m2
-// dz (those stay with policy_head, which takes no distribution).
-void policy_head_soft(const Tensor& y, const Tensor& w, const Tensor& b, const Tensor& tdist,
-                      const c10::optional<Tensor>& sym, const c10::optional<Tensor>& weight, const Tensor& dz,
-                      const Tensor& loss, const Tensor& correct, const Tensor& dhead, int64_t S, double grad_scale) {
-  check_dev("policy_head_soft", y, w, b, tdist, sym, weight, dz, loss, correct, dhead);
-  head_geometry("policy_head_soft", y, S, {&w}, {&b});
+// What policy_head_soft and policy_head_soft_pass share: the checks of the head's operands and outputs (the
+// width of tdist's rows is the caller's check) and the fill of PolicyHeadSoftArgs.
+static agk::PolicyHeadSoftArgs soft_head_args(const char* op, const Tensor& y, const Tensor& w, const Tensor& b,
+                                              const Tensor& tdist, const c10::optional<Tensor>& sym,
+                                              const c10::optional<Tensor>& weight, const Tensor& dz, const Tensor& loss,
+                                              const Tensor& correct, const Tensor& dhead, int64_t S, double grad_scale) {
   const int64_t B = y.size(0), C = y.size(3);
-  CHECK_F32(tdist); CHECK_CONTIG(tdist);
-  TORCH_CHECK(tdist.dim() == 2 && tdist.size(0) == B && (tdist.size(1) == S * S || tdist.size(1) == S * S + 1),
-              "tdist must be (B, S*S) or (B, S*S + 1)");
   CHECK_BF16(dz); CHECK_CONTIG(dz); CHECK_F32(loss); CHECK_F32(correct); CHECK_F32(dhead);
   CHECK_CONTIG(loss); CHECK_CONTIG(correct); CHECK_CONTIG(dhead);
-  TORCH_CHECK(dz.sizes() == y.sizes(), "dz must match y");
-  TORCH_CHECK(loss.numel() >= B && correct.numel() >= B, "loss and correct must hold B entries");
-  TORCH_CHECK(dhead.numel() >= B * (w.numel() + 1), "dhead too small");
+  TORCH_CHECK(dz.sizes() == y.sizes(), op, ": dz must match y");
+  TORCH_CHECK(loss.numel() >= B && correct.numel() >= B, op, ": loss and correct must hold B entries");
+  TORCH_CHECK(dhead.numel() >= B * (w.numel() + 1), op, ": dhead too small");
   agk::PolicyHeadSoftArgs a{};
   a.y = bfp(y);
   a.w = w.data_ptr<float>();
@@ -307,11 +301,29 @@ void policy_head_soft(const Tensor& y, const Tensor& w, const Tensor& b, const T
   a.dhead = dhead.data_ptr<float>();
   a.B = (int)B; a.S = (int)S; a.C = (int)C; a.C_real = (int)w.numel(); a.T = (int)tdist.size(1);
   a.grad_scale = (float)grad_scale;
-  a.sym = head_sym("policy_head_soft", sym, B);
-  a.weight = head_board_weight("policy_head_soft", "weight", weight, B);
+  a.sym = head_sym(op, sym, B);
+  a.weight = head_board_weight(op, "weight", weight, B);
+  return a;
+}
+
+// Soft-target training head (head_soft.hip): tdist (B, S*S or S*S + 1) f32 is a target distribution per
+// board in the planes' original frame, sym the symmetry pack_input gave the board.  Only what the schema
+// names exists here: no legal mask, temperature, binary-CE loss, entropy / KL terms, stats, probs or e5m2
+// dz (those stay with policy_head, which takes no distribution).
+void policy_head_soft(const Tensor& y, const Tensor& w, const Tensor& b, const Tensor& tdist,
+                      const c10::optional<Tensor>& sym, const c10::optional<Tensor>& weight, const Tensor& dz,
+                      const Tensor& loss, const Tensor& correct, const Tensor& dhead, int64_t S, double grad_scale) {
+  const char* op = "policy_head_soft";
+  check_dev(op, y, w, b, tdist, sym, weight, dz, loss, correct, dhead);
+  head_geometry(op, y, S, {&w}, {&b});
+  const int64_t B = y.size(0);
+  CHECK_F32(tdist); CHECK_CONTIG(tdist);
+  TORCH_CHECK(tdist.dim() == 2 && tdist.size(0) == B && (tdist.size(1) == S * S || tdist.size(1) == S * S + 1),
+              "tdist must be (B, S*S) or (B, S*S + 1)");
+  const agk::PolicyHeadSoftArgs a = soft_head_args(op, y, w, b, tdist, sym, weight, dz, loss, correct, dhead, S, grad_scale);
   if (B == 0) return;
   agk::launch_policy_head_soft(a, cur_stream());
-  launch_check("policy_head_soft");
+  launch_check(op);
 }
 
 // z: (B, S*S) f32 <- y (B, S+2, S+2, C) bf16 . w + b
@@ -391,25 +403,43 @@ void head_backward_add(const Tensor& y, const Tensor& w, const Tensor& dlogits, 
   launch_check("head_backward_add");
 }
 
-// Dual-head inference: probs (B, S*S) = policy_head's masked softmax at temperature 1 of y . wp + bp, and
-// zv (B, S*S) = y . wv + bv (head_logits' quantity), from one read of the board (head_pv.hip)
-void policy_value_head(const Tensor& y, const Tensor& wp, const Tensor& bp, const Tensor& wv, const Tensor& bv,
-                       const Tensor& probs, const Tensor& zv, int64_t S, const c10::optional<Tensor>& legal) {
-  check_dev("policy_value_head", y, wp, bp, wv, bv, probs, zv, legal);
-  head_geometry("policy_value_head", y, S, {&wp, &wv}, {&bp, &bv});
+// What the three dual inference ops share: the checks of probs (B, NE) and zv (B, S*S) and the fill of
+// PolicyValueHeadArgs.  NE = S*S, or S*S + 1 with the pass entry.
+static agk::PolicyValueHeadArgs pv_head_args(const char* op, const Tensor& y, const Tensor& wp, const Tensor& bp,
+                                             const Tensor& wv, const Tensor& bv, const Tensor& probs, const Tensor& zv,
+                                             int64_t S, const c10::optional<Tensor>& legal, int64_t NE) {
+  const int64_t B = y.size(0), C = y.size(3), SS = S * S;
   CHECK_F32(probs); CHECK_CONTIG(probs); CHECK_F32(zv); CHECK_CONTIG(zv);
-  const int64_t B = y.size(0), C = y.size(3);
-  TORCH_CHECK(probs.numel() == B * S * S && zv.numel() == B * S * S, "probs and zv must be (B, S*S)");
+  TORCH_CHECK(probs.numel() == B * NE && zv.numel() == B * SS, op, ": probs must be (B, ", NE == SS ? "S*S" : "S*S + 1",
+              ") and zv (B, S*S)");
   agk::PolicyValueHeadArgs a{};
   a.y = bfp(y);
   a.wp = wp.data_ptr<float>(); a.bp = bp.data_ptr<float>();
   a.wv = wv.data_ptr<float>(); a.bv = bv.data_ptr<float>();
   a.probs = probs.data_ptr<float>(); a.zv = zv.data_ptr<float>();
   a.B = (int)B; a.S = (int)S; a.C = (int)C; a.C_real = (int)wp.numel();
-  a.legal = head_legal("policy_value_head", legal, B, S);
-  if (B == 0) return;
+  a.legal = head_legal(op, legal, B, S);
+  return a;
+}
+// the ownership row of policy_value_own_head and policy_value_pass_head: own (B, S*S) = tanhf(y . wo + bo)
+static void pv_head_own_row(const char* op, agk::PolicyValueOwnHeadArgs& a, const Tensor& wo, const Tensor& bo,
+                            const Tensor& own) {
+  CHECK_F32(own); CHECK_CONTIG(own);
+  TORCH_CHECK(own.numel() == (int64_t)a.pv.B * a.pv.S * a.pv.S, op, ": own must be (B, S*S)");
+  a.wo = wo.data_ptr<float>(); a.bo = bo.data_ptr<float>(); a.own = own.data_ptr<float>();
+}
+
+// Dual-head inference: probs (B, S*S) = policy_head's masked softmax at temperature 1 of y . wp + bp, and
+// zv (B, S*S) = y . wv + bv (head_logits' quantity), from one read of the board (head_pv.hip)
+void policy_value_head(const Tensor& y, const Tensor& wp, const Tensor& bp, const Tensor& wv, const Tensor& bv,
+                       const Tensor& probs, const Tensor& zv, int64_t S, const c10::optional<Tensor>& legal) {
+  const char* op = "policy_value_head";
+  check_dev(op, y, wp, bp, wv, bv, probs, zv, legal);
+  head_geometry(op, y, S, {&wp, &wv}, {&bp, &bv});
+  const agk::PolicyValueHeadArgs a = pv_head_args(op, y, wp, bp, wv, bv, probs, zv, S, legal, S * S);
+  if (a.B == 0) return;
   agk::launch_policy_value_head(a, cur_stream());
-  launch_check("policy_value_head");
+  launch_check(op);
 }
 
 // Training / evaluation forward of the value and ownership heads from one read of the board (head_own.hip):
@@ -497,24 +527,16 @@ void head_backward_add2(const Tensor& y, const Tensor& w1, const Tensor& g1, con
 void policy_value_own_head(const Tensor& y, const Tensor& wp, const Tensor& bp, const Tensor& wv, const Tensor& bv,
                            const Tensor& wo, const Tensor& bo, const Tensor& probs, const Tensor& zv, const Tensor& own,
                            int64_t S, const c10::optional<Tensor>& legal) {
-  check_dev("policy_value_own_head", y, wp, bp, wv, bv, wo, bo, probs, zv, own, legal);
-  head_geometry("policy_value_own_head", y, S, {&wp, &wv, &wo}, {&bp, &bv, &bo});
-  TORCH_CHECK(y.numel() < (1ll << 31), "policy_value_own_head: tensor too large");
-  const int64_t B = y.size(0), C = y.size(3), SS = S * S;
-  CHECK_F32(probs); CHECK_CONTIG(probs); CHECK_F32(zv); CHECK_CONTIG(zv); CHECK_F32(own); CHECK_CONTIG(own);
-  TORCH_CHECK(probs.numel() == B * SS && zv.numel() == B * SS && own.numel() == B * SS,
-              "policy_value_own_head: probs, zv and own must be (B, S*S)");
+  const char* op = "policy_value_own_head";
+  check_dev(op, y, wp, bp, wv, bv, wo, bo, probs, zv, own, legal);
+  head_geometry(op, y, S, {&wp, &wv, &wo}, {&bp, &bv, &bo});
+  TORCH_CHECK(y.numel() < (1ll << 31), op, ": tensor too large");
   agk::PolicyValueOwnHeadArgs a{};
-  a.pv.y = bfp(y);
-  a.pv.wp = wp.data_ptr<float>(); a.pv.bp = bp.data_ptr<float>();
-  a.pv.wv = wv.data_ptr<float>(); a.pv.bv = bv.data_ptr<float>();
-  a.wo = wo.data_ptr<float>(); a.bo = bo.data_ptr<float>();
-  a.pv.probs = probs.data_ptr<float>(); a.pv.zv = zv.data_ptr<float>(); a.own = own.data_ptr<float>();
-  a.pv.B = (int)B; a.pv.S = (int)S; a.pv.C = (int)C; a.pv.C_real = (int)wp.numel();
-  a.pv.legal = head_legal("policy_value_own_head", legal, B, S);
-  if (B == 0) return;
+  a.pv = pv_head_args(op, y, wp, bp, wv, bv, probs, zv, S, legal, S * S);
+  pv_head_own_row(op, a, wo, bo, own);
+  if (a.pv.B == 0) return;
   agk::launch_policy_value_own_head(a, cur_stream());
-  launch_check("policy_value_own_head");
+  launch_check(op);
 }
 
 void value_out(const Tensor& h, const Tensor& w2, const Tensor& b2, const c10::optional<Tensor>& target,
@@ -1216,16 +1238,21 @@ void gpool_bwd_fill(const Tensor& dp, const Tensor& argmax, const Tensor& out, i
   launch_check("gpool_bwd_fill");
 }
 
-// ---- pass head of the dual net (head_pass.hip, gpool.hip)
-// pooled (B, 2, C), pass_w (2, C) zero-padded, pass_b (1): the operands of z_pass shared by both head ops
-static void pass_operands(const char* op, const Tensor& pooled, const Tensor& pass_w, const Tensor& pass_b, int64_t B,
-                          int64_t C) {
+// ---- pass head of the dual net (head_soft.hip, head_own.hip, gpool.hip)
+// pooled (B, 2, C), pass_w (2, C) zero-padded, pass_b (1): the operands of z_pass that both head ops add to
+// their plain sibling's
+static agk::PassHeadOperands pass_operands(const char* op, const Tensor& pooled, const Tensor& pass_w,
+                                           const Tensor& pass_b, int64_t B, int64_t C) {
   CHECK_F32(pooled); CHECK_CONTIG(pooled); CHECK_F32(pass_w); CHECK_CONTIG(pass_w); CHECK_F32(pass_b);
   TORCH_CHECK(pooled.dim() == 3 && pooled.size(0) == B && pooled.size(1) == 2 && pooled.size(2) == C, op,
               ": pooled must be (B, 2, C) = (", B, ", 2, ", C, ")");
   TORCH_CHECK(pass_w.dim() == 2 && pass_w.size(0) == 2 && pass_w.size(1) == C, op,
               ": pass_w must be the zero-padded (2, C) = (2, ", C, ") copy");
   TORCH_CHECK(pass_b.numel() >= 1, op, ": pass_b must hold one entry");
+  agk::PassHeadOperands ps{};
+  ps.pooled = pooled.data_ptr<float>(); ps.pass_w = pass_w.data_ptr<float>(); ps.pass_b = pass_b.data_ptr<float>();
+  ps.pooled_elems = pooled.numel();
+  return ps;
 }
 
 void policy_head_soft_pass(const Tensor& y, const Tensor& w, const Tensor& b, const Tensor& pooled,
@@ -1237,30 +1264,17 @@ void policy_head_soft_pass(const Tensor& y, const Tensor& w, const Tensor& b, co
   check_dev(op, y, w, b, pooled, pass_w, pass_b, tdist, sym, weight, dz, loss, correct, dhead, dpass, dpw);
   head_geometry(op, y, S, {&w}, {&b});
   const int64_t B = y.size(0), C = y.size(3), Cr = w.numel();
-  pass_operands(op, pooled, pass_w, pass_b, B, C);
+  agk::PolicyHeadSoftPassArgs a{};
+  a.pass = pass_operands(op, pooled, pass_w, pass_b, B, C);
   CHECK_F32(tdist); CHECK_CONTIG(tdist);
   TORCH_CHECK(tdist.dim() == 2 && tdist.size(0) == B && tdist.size(1) == S * S + 1, op,
               ": tdist must be (B, S*S + 1) with the pass last (a narrower row has no pass entry)");
-  CHECK_BF16(dz); CHECK_CONTIG(dz); CHECK_F32(loss); CHECK_F32(correct); CHECK_F32(dhead); CHECK_F32(dpass); CHECK_F32(dpw);
-  CHECK_CONTIG(loss); CHECK_CONTIG(correct); CHECK_CONTIG(dhead); CHECK_CONTIG(dpass); CHECK_CONTIG(dpw);
-  TORCH_CHECK(dz.sizes() == y.sizes(), op, ": dz must match y");
-  TORCH_CHECK(loss.numel() >= B && correct.numel() >= B, op, ": loss and correct must hold B entries");
-  TORCH_CHECK(dhead.numel() >= B * (Cr + 1), op, ": dhead too small");
+  CHECK_F32(dpass); CHECK_F32(dpw); CHECK_CONTIG(dpass); CHECK_CONTIG(dpw);
+  a.head = soft_head_args(op, y, w, b, tdist, sym, weight, dz, loss, correct, dhead, S, grad_scale);
   TORCH_CHECK(dpass.numel() >= B, op, ": dpass must hold B entries");
   TORCH_CHECK(dpw.numel() >= B * (2 * Cr + 1), op, ": dpw must hold (B, 2 C_real + 1)");
-  agk::PolicyHeadSoftPassArgs a{};
-  a.y = bfp(y);
-  a.w = w.data_ptr<float>(); a.b = b.data_ptr<float>();
-  a.pooled = pooled.data_ptr<float>(); a.pass_w = pass_w.data_ptr<float>(); a.pass_b = pass_b.data_ptr<float>();
-  a.tdist = tdist.data_ptr<float>();
-  a.dz = bfp_mut(dz);
-  a.loss = loss.data_ptr<float>(); a.correct = correct.data_ptr<float>(); a.dhead = dhead.data_ptr<float>();
-  a.dpass = dpass.data_ptr<float>(); a.dpw = dpw.data_ptr<float>();
-  a.B = (int)B; a.S = (int)S; a.C = (int)C; a.C_real = (int)Cr;
-  a.grad_scale = (float)grad_scale;
-  a.pooled_elems = pooled.numel(); a.tdist_elems = tdist.numel(); a.dpass_elems = dpass.numel(); a.dpw_elems = dpw.numel();
-  a.sym = head_sym(op, sym, B);
-  a.weight = head_board_weight(op, "weight", weight, B);
+  a.pass.dpass = dpass.data_ptr<float>(); a.pass.dpw = dpw.data_ptr<float>();
+  a.pass.tdist_elems = tdist.numel(); a.pass.dpass_elems = dpass.numel(); a.pass.dpw_elems = dpw.numel();
   if (B == 0) return;
   agk::launch_policy_head_soft_pass(a, cur_stream());
   launch_check(op);
@@ -1277,24 +1291,12 @@ void policy_value_pass_head(const Tensor& y, const Tensor& wp, const Tensor& bp,
   if (wo.has_value()) head_geometry(op, y, S, {&wp, &wv, &*wo}, {&bp, &bv, &*bo});
   else head_geometry(op, y, S, {&wp, &wv}, {&bp, &bv});
   TORCH_CHECK(y.numel() < (1ll << 31), op, ": tensor too large");
-  const int64_t B = y.size(0), C = y.size(3), SS = S * S;
-  pass_operands(op, pooled, pass_w, pass_b, B, C);
-  CHECK_F32(probs); CHECK_CONTIG(probs); CHECK_F32(zv); CHECK_CONTIG(zv);
-  TORCH_CHECK(probs.numel() == B * (SS + 1) && zv.numel() == B * SS, op, ": probs must be (B, S*S + 1) and zv (B, S*S)");
+  const int64_t B = y.size(0), C = y.size(3);
   agk::PolicyValuePassHeadArgs a{};
-  a.y = bfp(y);
-  a.wp = wp.data_ptr<float>(); a.bp = bp.data_ptr<float>();
-  a.wv = wv.data_ptr<float>(); a.bv = bv.data_ptr<float>();
-  if (wo.has_value()) {
-    CHECK_F32(*own); CHECK_CONTIG(*own);
-    TORCH_CHECK(own->numel() == B * SS, op, ": own must be (B, S*S)");
-    a.wo = wo->data_ptr<float>(); a.bo = bo->data_ptr<float>(); a.own = own->data_ptr<float>();
-  }
-  a.pooled = pooled.data_ptr<float>(); a.pass_w = pass_w.data_ptr<float>(); a.pass_b = pass_b.data_ptr<float>();
-  a.probs = probs.data_ptr<float>(); a.zv = zv.data_ptr<float>();
-  a.B = (int)B; a.S = (int)S; a.C = (int)C; a.C_real = (int)wp.numel();
-  a.pooled_elems = pooled.numel(); a.probs_elems = probs.numel();
-  a.legal = head_legal(op, legal, B, S);
+  a.pass = pass_operands(op, pooled, pass_w, pass_b, B, C);
+  a.pass.probs_elems = probs.numel();
+  a.head.pv = pv_head_args(op, y, wp, bp, wv, bv, probs, zv, S, legal, S * S + 1);
+  if (wo.has_value()) pv_head_own_row(op, a.head, *wo, *bo, *own);
   if (B == 0) return;
   agk::launch_policy_value_pass_head(a, cur_stream());
   launch_check(op);

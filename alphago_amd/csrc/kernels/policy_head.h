@@ -1,7 +1,7 @@
 // The building blocks of the 1x1 head family (head.hip, head_reg.hip, head_soft.hip, head_pv.hip,
-// head_own.hip, symmetry.hip): block reductions, weight staging, the board holders with their dot
-// products and backward, the masked softmax, the dW / dbias reductions, the accumulating backward
-// for NH heads and the two launch rules.  The fused policy head kernel is a template here because
+// head_own.hip, symmetry.hip): block reductions, weight staging, the pass logit, the board holders with
+// their dot products and backward, the masked softmax, the dW / dbias reductions, the accumulating
+// backward for NH heads and the launch rules.  The fused policy head kernel is a template here because
 // two translation units instantiate it: head.hip holds the plain kernels of the SL / RL step,
 // head_reg.hip the regularised variants (REG).  Every file of the family is a module of its own, so
 // that one file's code objects do not depend on another's kernels (LDS variables are laid out per
@@ -27,7 +27,18 @@ inline bool head_rows_mapping(int64_t boards, int S, int C) {
 // The kernels that stream a board (head_dots, the backward walkers): 1024 threads for few boards,
 // for the same reason, else 256.
 inline bool head_wide_block(int64_t boards) { return boards < kHeadWideBelow; }
+// what the launchers of the pass variants check before they choose a mapping
+inline void head_check_geometry(const char* op, int B, int S, int C, int C_real) {
+  if (C % 8 || C < 8 || C > 256 || C_real < 1 || C_real > C || B < 1 || S < 1 || S > 19)
+    throw std::invalid_argument(std::string(op) +
+                                ": C a multiple of 8 in 8..256, 1 <= C_real <= C, B >= 1, S in 1..19");
+}
 
+// The block reductions: the waves' results in wave order.  NW is the workgroup's wave count where the caller
+// knows it (0: blockDim.x >> 6).  The bodies that several __global__s share pass it: inside a __device__
+// function the compiler does not fold blockDim.x to the kernel's uniform workgroup size, and the read it
+// leaves is a global load whose wait also drains the board's loads in flight.
+template <int NW = 0>
 __device__ __forceinline__ float block_reduce_max(float v, float* red) {
   v = wave_max(v);
   const int w = threadIdx.x >> 6;
@@ -35,9 +46,10 @@ __device__ __forceinline__ float block_reduce_max(float v, float* red) {
   if ((threadIdx.x & 63) == 0) red[w] = v;
   __syncthreads();
   float r = red[0];
-  for (int i = 1; i < (int)(blockDim.x >> 6); ++i) r = fmaxf(r, red[i]);
+  for (int i = 1; i < (NW ? NW : (int)(blockDim.x >> 6)); ++i) r = fmaxf(r, red[i]);
   return r;
 }
+template <int NW = 0>
 __device__ __forceinline__ float block_reduce_sum(float v, float* red) {
   v = wave_sum(v);
   const int w = threadIdx.x >> 6;
@@ -45,7 +57,7 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* red) {
   if ((threadIdx.x & 63) == 0) red[w] = v;
   __syncthreads();
   float r = 0.f;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += red[i];
+  for (int i = 0; i < (NW ? NW : (int)(blockDim.x >> 6)); ++i) r += red[i];
   return r;
 }
 
@@ -99,6 +111,27 @@ __device__ __forceinline__ void head_stage_weights(float* const (&w_s)[NH], cons
   }
 }
 
+// The pass entry of the PASS kernels: one more logit after the S * S board logits,
+//   z_pass[b] = pooled[b].reshape(2 C) . pass_w + pass_b,
+// with pooled (B, 2, C) the mean and max of the trunk output over the board (a preceding gpool_fwd) and
+// pass_w a zero-padded (2, C) copy of the net's (2 F, 1) weight.  It is the last entry of the softmax (index
+// S * S, so it loses ties in every argmax) and thread S * S owns it in every loop and reduction.
+// pass_logit: this thread's term of z_pass without the bias (thread t < 2 C owns entry t of the board's
+// pooled row; pv keeps the pooled value for the training head's partial row) summed over the block in a
+// fixed order.  The accesses the PASS kernels add are bounds-checked in the debug build (bounds_at, common.h).
+template <int NT>
+__device__ __forceinline__ float pass_logit(const PassHeadOperands& ps, int b, int C, float* red, float& pv) {
+  static_assert(NT >= 512, "one pooled entry per thread (2 C <= 512)");
+  const int tid = threadIdx.x;
+  float term = 0.f;
+  pv = 0.f;
+  if (tid < 2 * C) {
+    pv = ps.pooled[bounds_at((long long)b * 2 * C + tid, ps.pooled_elems)];
+    term = pv * ps.pass_w[tid];
+  }
+  return block_reduce_sum<NT / 64>(term, red);
+}
+
 // The masked softmax of one board's logits, in three steps that share z_s.
 // 1. head_mask_logits: z_s holds the dot products on entry and the masked logits (z + bias) * inv_temp,
 //    -inf where legal[p] == 0, on return; the result is this thread's maximum and its first index.
@@ -120,11 +153,11 @@ __device__ __forceinline__ ArgMax head_mask_logits(float* z_s, int SS, float bia
 }
 // 2. the block's maximum zmax: block_argmax where the arg-max is wanted (policy_head_kernel), inside
 //    head_masked_softmax otherwise.  3. head_exp_sum: the sum of exp(z - zmax) over the unmasked points.
-template <int NT>
+template <int NT, int NW = 0>
 __device__ __forceinline__ float head_exp_sum(const float* z_s, int SS, float zmax, float* red) {
   float ls = 0.f;
   for (int p = threadIdx.x; p < SS; p += NT) ls += (z_s[p] == -INFINITY) ? 0.f : __expf(z_s[p] - zmax);
-  return block_reduce_sum(ls, red);
+  return block_reduce_sum<NW>(ls, red);
 }
 struct HeadSoftmax {
   float zmax, inv;
@@ -173,15 +206,16 @@ __device__ __forceinline__ void head_channel_sums(float* part, const float (&acc
 
 // The bias gradient of one board, dhead[b][C_real]: the fixed-order block sum of the dlogits, from the
 // threads' partial sums or from the row in LDS.
+template <int NW = 0>
 __device__ __forceinline__ void head_bias_grad(float gs, float* red, float* dst) {
-  gs = block_reduce_sum(gs, red);
+  gs = block_reduce_sum<NW>(gs, red);
   if (threadIdx.x == 0) *dst = gs;
 }
-template <int NT>
+template <int NT, int NW = 0>
 __device__ __forceinline__ void head_bias_grad(const float* g_s, int SS, float* red, float* dst) {
   float gs = 0.f;
   for (int p = threadIdx.x; p < SS; p += NT) gs += g_s[p];
-  head_bias_grad(gs, red, dst);
+  head_bias_grad<NW>(gs, red, dst);
 }
 
 // The board's registers made opaque between two uses (a second dots, the backward): otherwise the
@@ -525,9 +559,11 @@ static void policy_head_go(const PolicyHeadArgs& a, hipStream_t st) {
 // heads' dot products come from the one register copy of the board.  The policy row goes through
 // policy_head_kernel<false>'s masked softmax at temperature 1 (policy_head_probs' bits), the value
 // row plus its bias leaves as fp32 logits (head_logits' quantity), the ownership row as tanh.
-template <int NT, class Board, bool OWN>
+// PASS: the softmax has the pass entry behind the board points (always legal; probs rows of S * S + 1); zv
+// and own keep their bits.
+template <int NT, class Board, bool OWN, bool PASS = false>
 __device__ __forceinline__ void policy_value_head_body(const PolicyValueHeadArgs& a, const float* wo, const float* bo,
-                                                       float* own) {
+                                                       float* own, const PassHeadOperands& ps = {}) {
   __shared__ float wp_s[256];
   __shared__ float wv_s[256];
   __shared__ float z_s[368];
@@ -550,7 +586,12 @@ __device__ __forceinline__ void policy_value_head_body(const PolicyValueHeadArgs
   }
   Board board;
   board.load(a.y + (size_t)b * HP * HP * a.C, a.S, a.C);
-  __syncthreads();
+  float zp = 0.f;
+  if constexpr (PASS) {
+    float pv;
+    zp = pass_logit<NT>(ps, b, a.C, red, pv) + ps.pass_b[0];
+  }
+  __syncthreads();  // the weights are staged; red is free again
   const float bias = a.bp[0];
   const float vbias = a.bv[0];
   const float obias = OWN ? bo[0] : 0.f;
@@ -567,8 +608,21 @@ __device__ __forceinline__ void policy_value_head_body(const PolicyValueHeadArgs
     a.zv[(size_t)b * SS + p] = zv_s[p] + vbias;
     if constexpr (OWN) own[(size_t)b * SS + p] = tanhf(zo_s[p] + obias);
   }
-  const HeadSoftmax sm = head_masked_softmax<NT>(z_s, SS, bias, 1.f, legal, red);
-  head_write_probs<NT>(a.probs + (size_t)b * SS, z_s, SS, sm.zmax, sm.inv);
+  if constexpr (PASS) {  // thread SS owns the pass entry
+    const int NE = SS + 1;
+    float lmax = head_mask_logits<NT>(z_s, SS, bias, 1.f, legal).v;
+    if (tid == SS) {
+      z_s[SS] = zp;
+      lmax = zp;
+    }
+    const float zmax = block_reduce_max<NT / 64>(lmax, red);  // its barriers publish z_s
+    const float inv = 1.f / head_exp_sum<NT, NT / 64>(z_s, NE, zmax, red);
+    float* row = a.probs + bounds_at((long long)b * NE, ps.probs_elems - SS);
+    head_write_probs<NT>(row, z_s, NE, zmax, inv);
+  } else {
+    const HeadSoftmax sm = head_masked_softmax<NT>(z_s, SS, bias, 1.f, legal, red);
+    head_write_probs<NT>(a.probs + (size_t)b * SS, z_s, SS, sm.zmax, sm.inv);
+  }
 }
 
 // The walker of the streaming backward kernels.  Thread (r, cg) = (tid / (C / 8), tid % (C / 8)) visits

@@ -1,6 +1,6 @@
 """Float64 reference, written from its formulas, and input builders for the pass head of the dual net
-(head_pass.hip, gpool_bwd_add_masked): shared by test_pass_head_cpu.py (which holds the net's torch
-expression and its autograd to this reference) and test_pass_head_kernels.py (GPU).
+(the PASS variants of head_soft.hip / head_own.hip, gpool_bwd_add_masked): shared by test_pass_head_cpu.py (which
+holds the net's torch expression and its autograd to this reference) and test_pass_head_kernels.py (GPU).
 
 Activations, 1x1 head weights and per-board weights are head_refs.head_case's.  With h the (B, S, S, C)
 activations (after their ReLU), NP = S * S and inv = float32(1 / NP):

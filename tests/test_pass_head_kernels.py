@@ -1,5 +1,5 @@
-"""The pass-head kernels (head_pass.hip and gpool_bwd_add_masked in gpool.hip) against the float64 reference of
-pass_head_refs.py, against the kernels they extend, and exactly on integer data.
+"""The pass-head kernels (the PASS variants in head_soft.hip / head_own.hip and gpool_bwd_add_masked in gpool.hip)
+against the float64 reference of pass_head_refs.py, against the kernels they extend, and exactly on integer data.
 
 policy_head_soft_pass holds the tolerances of tests/test_policy_head_soft.py (loss rtol 1e-3 / atol 1e-4; dz max
 error under 1e-2 of the reference max; dhead weight part under 1e-3 of the reference max, per board and summed;
@@ -272,6 +272,41 @@ def test_policy_value_pass_head(ops, cuda_device, C, C_real, B, S, legal, own):
     assert torch.equal(zv.view(torch.int32), zv0.view(torch.int32))
     if own:
         assert torch.equal(ownr.view(torch.int32), own0.view(torch.int32))
+
+
+@pytest.mark.parametrize("own", [False, True])
+@pytest.mark.parametrize("legal", [False, True])
+@pytest.mark.parametrize("C,C_real,B,S", PR.PASS_SHAPES)
+def test_silent_pass_probs_are_the_own_head_bit_for_bit(ops, cuda_device, C, C_real, B, S, legal, own):
+    """pass_w = 0 and pass_b = -1e30: the pass entry is never the maximum and adds one exact zero to the sum of
+    exponentials, so on every board with a legal point the S * S board columns of probs carry
+    policy_value_own_head's bits and the pass column is 0.  (A board with no legal point has the pass as its
+    only entry: probability 1, where the own head writes zeros.)"""
+    dev = cuda_device
+    c, yp, w, b, wt, P, a, pw, pwp = _dev(ops, C, C_real, B, S, dev)
+    SS = S * S
+    g = torch.Generator().manual_seed(31 * C + 5 * B + S)
+    wv, bv = (torch.randn(C_real, generator=g) * 0.05).to(dev), torch.randn(1, generator=g).to(dev)
+    wo, bo = (torch.randn(C_real, generator=g) * 0.05).to(dev), torch.randn(1, generator=g).to(dev)
+    lg = (torch.rand(B, SS, generator=g) > 1.0 / 3.0).to(torch.uint8)
+    lg[B - 1] = 0  # a board with no legal point
+    lgd = lg.to(dev) if legal else None
+    nan = float("nan")
+    probs = torch.full((B, SS + 1), nan, device=dev)
+    zv, ownr = torch.full((B, SS), nan, device=dev), torch.full((B, SS), nan, device=dev)
+    kw = dict(wo=wo, bo=bo, own=ownr) if own else {}
+    ops.policy_value_pass_head(yp, w, b, wv, bv, P, torch.zeros_like(pwp), torch.tensor([-1e30], device=dev), probs, zv,
+                               S, legal=lgd, **kw)
+    p0, zv0, own0 = (torch.full((B, SS), nan, device=dev) for _ in range(3))
+    ops.policy_value_own_head(yp, w, b, wv, bv, wo, bo, p0, zv0, own0, S, legal=lgd)
+    torch.cuda.synchronize()
+    live = lgd.bool().any(1) if legal else torch.ones(B, dtype=torch.bool, device=dev)
+    assert int(live.sum()) == (B - 1 if legal else B)
+    assert float(p0[live].sum()) > 0
+    assert torch.equal(probs[live, :SS].view(torch.int32), p0[live].view(torch.int32))
+    assert not bool(probs[live, SS].any())
+    if legal:
+        assert probs[B - 1, SS].item() == 1.0 and not bool(probs[B - 1, :SS].any())
 
 
 # ----------------------------------------------------------------------------- host checks, debug library
