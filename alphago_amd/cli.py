@@ -43,7 +43,14 @@ def add_symmetries_arg(p: argparse.ArgumentParser) -> None:
                         "(default: $ALPHAGO_AMD_SYMMETRIES or none)")
 
 
-def make_player(spec: str, device=None, symmetries: str = "none"):
+def add_score_utility_arg(p: argparse.ArgumentParser) -> None:
+    p.add_argument("--score-utility", type=float, default=0.0, metavar="LAMBDA",
+                   help="dual nets with the score head: search on (v + LAMBDA * tanh(score / (2 S))) / (1 + LAMBDA) "
+                        "instead of the win/loss value v; root values and the resign threshold then speak of this "
+                        "utility.  LAMBDA has no tuned value (default 0: the pure value)")
+
+
+def make_player(spec: str, device=None, symmetries: str = "none", score_utility: float = 0.0):
     from .gtp.client import GTPClientPlayer
     from .models.policy import CNNPolicy, CNNPolicyValue, CNNValue, is_dual_spec
     from .search.arena import RandomPlayer
@@ -68,8 +75,10 @@ def make_player(spec: str, device=None, symmetries: str = "none"):
         if is_dual_spec(paths[0]):  # a dual (policy + value) net: the one file is the whole player
             if len(paths) > 1:
                 raise ValueError("%s holds a dual policy+value net: no separate value net goes with it" % paths[0])
-            return MCTSPlayer(CNNPolicyValue.load_model(paths[0], device=device, symmetries=symmetries),
-                              None, n_playout=int(n))
+            pv = CNNPolicyValue.load_model(paths[0], device=device, symmetries=symmetries)
+            if score_utility:
+                pv.set_score_utility(score_utility)
+            return MCTSPlayer(pv, None, n_playout=int(n))
         pol = CNNPolicy.load_model(paths[0], device=device, symmetries=symmetries)
         val = CNNValue.load_model(paths[1], device=device, symmetries=symmetries) if len(paths) > 1 else None
         return MCTSPlayer(pol, val, n_playout=int(n))
@@ -102,7 +111,15 @@ def _init_model(argv):
                    help="pv only: a learned pass logit next to the S*S move logits (mean and max of the trunk "
                         "output over the board -> dense), trained by train-pv on the pass column of "
                         "selfplay-mcts records and searched as a child of every node")
+    p.add_argument("--score-head", action="store_true",
+                   help="pv only: an estimate of the score lead of the player to move (mean and max of the trunk "
+                        "output over the board -> dense -> ReLU -> dense), trained by train-pv on selfplay-mcts "
+                        "--score records; GTP estimate_score and --score-utility read it")
+    p.add_argument("--score-dense", type=int, default=64, metavar="D",
+                   help="--score-head: width of the head's hidden layer, a multiple of 8 in 8..512 (default 64)")
     a = p.parse_args(argv)
+    if a.score_head and a.kind != "pv":
+        p.error("--score-head needs the dual net (init-model pv): the head reads its trunk")
     if a.pass_head and a.kind != "pv":
         p.error("--pass-head needs the dual net (init-model pv): the pass logit joins its policy softmax")
     if a.gpool and not (a.kind == "pv" and a.residual):
@@ -126,6 +143,10 @@ def _init_model(argv):
             kw["gpool"] = a.gpool
         if a.pass_head:
             kw["pass_head"] = 1
+        if a.score_head:
+            kw["score_head"] = 1
+            if a.score_dense != 64:
+                kw["score_dense"] = a.score_dense
         try:
             m = CNNPolicyValue(feats, board=a.board, filters_per_layer=a.filters or 192, layers=a.layers,
                                device="cpu", **kw)
@@ -143,6 +164,7 @@ def gtp_parser() -> argparse.ArgumentParser:
     p.add_argument("--player", default="random")
     p.add_argument("--size", type=int, default=19)
     add_symmetries_arg(p)
+    add_score_utility_arg(p)
     return p
 
 
@@ -150,7 +172,7 @@ def _gtp(argv):
     a = gtp_parser().parse_args(argv)
     from .gtp.engine import run_gtp
 
-    run_gtp(make_player(a.player, symmetries=a.symmetries), size=a.size)
+    run_gtp(make_player(a.player, symmetries=a.symmetries, score_utility=a.score_utility), size=a.size)
 
 
 def match_parser() -> argparse.ArgumentParser:
@@ -162,6 +184,7 @@ def match_parser() -> argparse.ArgumentParser:
     p.add_argument("--komi", type=float, default=7.5)
     p.add_argument("--sgf-dir", default=None)
     add_symmetries_arg(p)
+    add_score_utility_arg(p)
     return p
 
 
@@ -169,7 +192,8 @@ def _match(argv):
     a = match_parser().parse_args(argv)
     from .search.arena import play_match
 
-    res = play_match(make_player(a.player1, symmetries=a.symmetries), make_player(a.player2, symmetries=a.symmetries),
+    res = play_match(make_player(a.player1, symmetries=a.symmetries, score_utility=a.score_utility),
+                     make_player(a.player2, symmetries=a.symmetries, score_utility=a.score_utility),
                      a.games, a.size, a.komi, sgf_dir=a.sgf_dir)
     print(json.dumps(res))
     return res

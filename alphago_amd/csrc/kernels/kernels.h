@@ -536,6 +536,41 @@ struct GpoolBwdAddArgs {
   long long elems;     // extent of y and dz
 };
 void launch_gpool_bwd_add_masked(const GpoolBwdAddArgs& a, hipStream_t st);
+// dz += ReLU'(y) * (dp[b][0][c] * inv + (p == argmax[b][c] ? dp[b][1][c] : 0)) for a general dp (the score head),
+// with GpoolBwdAddArgs' pass term in the same pass when dpass / w are given (gpool.hip)
+struct GpoolBwdAddDpArgs {
+  const float* dp;     // [B][2][C], 16-byte aligned
+  const float* dpass;  // [B] or null
+  const float* w;      // [2][C] zero-padded pass_w, or null
+  const int* argmax;   // [B][C] gpool_fwd's
+  const __bf16* y;     // [B][S+2][S+2][C] the pooled activation (after its ReLU)
+  __bf16* dz;          // [B][S+2][S+2][C] read-modify-write
+  int B, S, C;
+  float inv;           // float32(1 / (S * S))
+  long long elems;     // extent of y and dz
+};
+void launch_gpool_bwd_add_masked_dp(const GpoolBwdAddDpArgs& a, hipStream_t st);
+// The score head's output layer (head_score.hip): s = relu(upre) . w2 + b2; with a target the Huber loss, |e|,
+// du and the per-board partial row [g * u | g]; with value, the score utility written over the value column.
+// The *_elems fields are tensor extents for the debug build's bounds checks.
+struct ScoreOutArgs {
+  const float* upre;    // [B][D]
+  const float* w2;      // [D]
+  const float* b2;      // [1]
+  float* s;             // [B]
+  const float* target;  // [B] in units of S points, or null (forward only)
+  const float* valid;   // [B] or null
+  const float* weight;  // [B] or null
+  float* loss;          // [B]
+  float* abserr;        // [B]
+  float* du;            // [B][D]
+  float* dout;          // [B][D + 1]
+  float* value;         // [B] or null: rewritten as (value + lam * tanh(s / 2)) / (1 + lam)
+  int B, D;
+  float grad_scale, delta, lam;
+  long long upre_elems, du_elems, dout_elems;
+};
+void launch_score_out(const ScoreOutArgs& a, hipStream_t st);
 void launch_featurize(const FeaturizeArgs& a, hipStream_t st);
 // res: the skip operand (ConvFp8ResArgs::res) or null
 void launch_conv_fwd_fp8(const ConvFp8Args& a, hipStream_t st, const __bf16* res = nullptr);

@@ -1329,6 +1329,93 @@ void gpool_bwd_add_masked(const Tensor& dpass, const Tensor& pass_w, const Tenso
   launch_check(op);
 }
 
+// ---- score head of the dual net (head_score.hip, gpool.hip)
+void score_out(const Tensor& upre, const Tensor& w2, const Tensor& b2, const Tensor& s,
+               const c10::optional<Tensor>& target, const c10::optional<Tensor>& valid,
+               const c10::optional<Tensor>& weight, const c10::optional<Tensor>& loss,
+               const c10::optional<Tensor>& abserr, const c10::optional<Tensor>& du,
+               const c10::optional<Tensor>& dout, double grad_scale, double delta,
+               const c10::optional<Tensor>& value, double utility) {
+  const char* op = "score_out";
+  check_dev(op, upre, w2, b2, s, target, valid, weight, loss, abserr, du, dout, value);
+  CHECK_F32(upre); CHECK_CONTIG(upre); CHECK_F32(w2); CHECK_CONTIG(w2); CHECK_F32(b2); CHECK_F32(s); CHECK_CONTIG(s);
+  TORCH_CHECK(upre.dim() == 2, op, ": upre must be (B, D)");
+  const int64_t B = upre.size(0), D = upre.size(1);
+  TORCH_CHECK(D % 8 == 0 && D >= 8 && D <= 512, op, ": D must be a multiple of 8 in 8..512, got ", D);
+  TORCH_CHECK(w2.numel() == D, op, ": w2 must hold D = ", D, " entries");
+  TORCH_CHECK(b2.numel() >= 1, op, ": b2 must hold one entry");
+  TORCH_CHECK(s.numel() == B, op, ": s must hold B = ", B, " entries");
+  TORCH_CHECK(delta > 0, op, ": delta must be positive");
+  agk::ScoreOutArgs a{};
+  a.upre = upre.data_ptr<float>(); a.w2 = w2.data_ptr<float>(); a.b2 = b2.data_ptr<float>(); a.s = s.data_ptr<float>();
+  a.B = (int)B; a.D = (int)D;
+  a.grad_scale = (float)grad_scale; a.delta = (float)delta; a.lam = (float)utility;
+  a.upre_elems = upre.numel();
+  auto vec = [&](const c10::optional<Tensor>& t, const char* name) -> float* {
+    CHECK_F32(*t); CHECK_CONTIG(*t);
+    TORCH_CHECK(t->numel() == B, op, ": ", name, " must hold B = ", B, " entries");
+    return t->data_ptr<float>();
+  };
+  if (target.has_value()) {
+    TORCH_CHECK(loss && abserr && du && dout, op, ": a target needs loss, abserr, du and dout");
+    a.target = vec(target, "target");
+    a.loss = vec(loss, "loss");
+    a.abserr = vec(abserr, "abserr");
+    CHECK_F32(*du); CHECK_CONTIG(*du); CHECK_F32(*dout); CHECK_CONTIG(*dout);
+    TORCH_CHECK(du->numel() == B * D, op, ": du must be (B, D)");
+    TORCH_CHECK(dout->numel() == B * (D + 1), op, ": dout must be (B, D + 1)");
+    a.du = du->data_ptr<float>(); a.dout = dout->data_ptr<float>();
+    a.du_elems = du->numel(); a.dout_elems = dout->numel();
+    if (valid.has_value()) a.valid = vec(valid, "valid");
+    if (weight.has_value()) a.weight = vec(weight, "weight");
+  } else {
+    TORCH_CHECK(!valid && !weight && !loss && !abserr && !du && !dout, op,
+                ": valid, weight, loss, abserr, du and dout go with a target");
+  }
+  if (value.has_value()) {
+    TORCH_CHECK(utility >= 0, op, ": utility must be >= 0");
+    a.value = vec(value, "value");
+  }
+  if (B == 0) return;
+  agk::launch_score_out(a, cur_stream());
+  launch_check(op);
+}
+
+void gpool_bwd_add_masked_dp(const Tensor& dp, const Tensor& argmax, const Tensor& y, const Tensor& dz, int64_t S,
+                             double inv, const c10::optional<Tensor>& dpass, const c10::optional<Tensor>& pass_w) {
+  const char* op = "gpool_bwd_add_masked_dp";
+  check_dev(op, dp, argmax, y, dz, dpass, pass_w);
+  const int64_t B = gpool_check_act(op, y, S), C = y.size(3);
+  gpool_check_act(op, dz, S);
+  TORCH_CHECK(dz.sizes() == y.sizes(), op, ": dz must have y's shape");
+  TORCH_CHECK(dp.scalar_type() == at::kFloat && dp.is_contiguous() && dp.dim() == 3 && dp.size(0) == B &&
+                  dp.size(1) == 2 && dp.size(2) == C, op, ": dp must be contiguous float32 (B, 2, C) = (", B, ", 2, ", C, ")");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(dp.data_ptr()) % 16 == 0, op, ": dp must be 16-byte aligned");
+  TORCH_CHECK(argmax.scalar_type() == at::kInt && argmax.is_contiguous() && argmax.dim() == 2 && argmax.size(0) == B &&
+                  argmax.size(1) == C, op, ": argmax must be contiguous int32 (B, C) = (", B, ", ", C, ")");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(argmax.data_ptr()) % 16 == 0, op, ": argmax must be 16-byte aligned");
+  TORCH_CHECK(dpass.has_value() == pass_w.has_value(), op, ": dpass and pass_w go together (the pass head's term)");
+  agk::GpoolBwdAddDpArgs a{};
+  if (dpass.has_value()) {
+    TORCH_CHECK(dpass->scalar_type() == at::kFloat && dpass->is_contiguous() && dpass->numel() >= B, op,
+                ": dpass must be contiguous float32 with B = ", B, " entries");
+    TORCH_CHECK(pass_w->scalar_type() == at::kFloat && pass_w->is_contiguous() && pass_w->dim() == 2 &&
+                    pass_w->size(0) == 2 && pass_w->size(1) == C, op,
+                ": pass_w must be the contiguous float32 zero-padded (2, C) = (2, ", C, ") copy");
+    a.dpass = dpass->data_ptr<float>();
+    a.w = pass_w->data_ptr<float>();
+  }
+  a.dp = dp.data_ptr<float>();
+  a.argmax = argmax.data_ptr<int>();
+  a.y = bfp(y);
+  a.dz = bfp_mut(dz);
+  a.B = (int)B; a.S = (int)S; a.C = (int)C;
+  a.inv = (float)inv;
+  a.elems = dz.numel();
+  agk::launch_gpool_bwd_add_masked_dp(a, cur_stream());
+  launch_check(op);
+}
+
 // A deliberately invalid launch (2048 threads per block, above the 1024
 // limit): the runtime rejects it, launch_check turns that into a Python
 // RuntimeError -- the test of the error path every op shares.
@@ -1412,6 +1499,11 @@ TORCH_LIBRARY(alphago_amd, m) {
         "Tensor pooled, Tensor pass_w, Tensor pass_b, Tensor(a!) probs, Tensor(b!) zv, Tensor(c!)? own, int S, "
         "Tensor? legal=None) -> ()");
   m.def("gpool_bwd_add_masked(Tensor dpass, Tensor pass_w, Tensor argmax, Tensor y, Tensor(a!) dz, int S, float inv) -> ()");
+  m.def("gpool_bwd_add_masked_dp(Tensor dp, Tensor argmax, Tensor y, Tensor(a!) dz, int S, float inv, Tensor? dpass, "
+        "Tensor? pass_w) -> ()");
+  m.def("score_out(Tensor upre, Tensor w2, Tensor b2, Tensor(a!) s, Tensor? target, Tensor? valid, Tensor? weight, "
+        "Tensor(b!)? loss, Tensor(c!)? abserr, Tensor(d!)? du, Tensor(e!)? dout, float grad_scale, float delta, "
+        "Tensor(f!)? value, float utility) -> ()");
   m.def("pack_weights(Tensor[] ws, Tensor(a!)[] wf, Tensor(b!)[] wd) -> ()");
   m.def("sgd_update(Tensor(a!) p, Tensor g, float lr, float gscale) -> ()");
   m.def("comm_proxy(Tensor src, Tensor(a!) dst, int channels, float wire_us) -> ()");
@@ -1486,6 +1578,8 @@ TORCH_LIBRARY_IMPL(alphago_amd, CUDA, m) {
   m.impl("policy_head_soft_pass", &policy_head_soft_pass);
   m.impl("policy_value_pass_head", &policy_value_pass_head);
   m.impl("gpool_bwd_add_masked", &gpool_bwd_add_masked);
+  m.impl("gpool_bwd_add_masked_dp", &gpool_bwd_add_masked_dp);
+  m.impl("score_out", &score_out);
   m.impl("head_logits", &head_logits);
   m.impl("head_backward", &head_backward);
   m.impl("head_backward_add", &head_backward_add);

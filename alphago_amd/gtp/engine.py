@@ -90,6 +90,7 @@ class GTPEngine(object):
             "time_left": self._time_left,
             "printsgf": lambda a: gamestate_to_sgf(self.state),
             "ownership": self._ownership,
+            "estimate_score": self._estimate_score,
         }
 
     # ------------------------------------------------------------- commands
@@ -233,6 +234,23 @@ class GTPEngine(object):
         own = net.eval_ownership(self.state)
         rows = [" ".join("%+.2f" % float(own[x, y]) for x in range(self.size)) for y in reversed(range(self.size))]
         return "\n" + "\n".join(rows)
+
+    def _score_net(self):
+        """The player's dual net when it has the score head (looked up as ``_ownership_net`` does), else None."""
+        p = self.player
+        for cand in (p, getattr(p, "policy", None), getattr(getattr(p, "search", None), "policy", None)):
+            if cand is not None and getattr(cand, "has_score", False):
+                return cand
+        return None
+
+    def _estimate_score(self, a):
+        """The net's estimate of the final margin of the current position, komi included, in final_score's
+        form with one decimal: ``B+12.5`` / ``W+3.0``."""
+        net = self._score_net()
+        if net is None:
+            raise ValueError("no score head")
+        sc = float(net.eval_score(self.state))
+        return "%s+%.1f" % ("B" if sc >= 0 else "W", abs(sc))
 
     def _final_score(self, a):
         w = self.state.get_winner()

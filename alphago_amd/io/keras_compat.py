@@ -103,8 +103,9 @@ def model_from_keras_json(spec: str):
 def pv_spec(net: PolicyValueNet) -> Dict:
     """The dual net's architecture (it is no Keras Sequential: a spec key of its own, ``pv_model``);
     ``residual: 1`` only for a residual trunk, ``ownership: 1`` only with the ownership head,
-    ``gpool: k`` only with pooling branches and ``pass_head: 1`` only with the pass head, so the spec of a
-    plain net is what it always was."""
+    ``gpool: k`` only with pooling branches, ``pass_head: 1`` only with the pass head and ``score_head: 1``
+    (``score_dense`` when it is not 64) only with the score head, so the spec of a plain net is what it always
+    was."""
     return dict(net.arch)
 
 
@@ -130,6 +131,9 @@ def _weights_in_order(net) -> List[Tuple[str, List[torch.Tensor]]]:
             out.append(("gpool_dense_%d" % i, [g]))
         if getattr(net, "pass_head", False):  # one more entry after the gpool entries
             out.append(("pass_dense_1", [net.pass_w, net.pass_b]))
+        if getattr(net, "score_head", False):  # two more entries, last of all
+            out.append(("score_dense_1", [net.sc1_w, net.sc1_b]))
+            out.append(("score_dense_2", [net.sc2_w, net.sc2_b]))
         return out
     names = _layer_names(net)
     out = []

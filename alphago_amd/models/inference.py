@@ -569,21 +569,35 @@ class HipPolicyValueInference(HipTrunkInference):
     ``policy_value_pass_head`` takes the head's place (with ``ownership=True`` it fills ``own`` too), both
     inside the captured graph.  The output rows are (B, S*S + 2), the S*S + 1 probabilities (the pass last)
     and the value; ``split_outputs`` and ``evaluate`` return ``probs`` of shape (n, S*S + 1).  ``pass_head``
-    on the engine tells search to take the pass prior from the last column."""
+    on the engine tells search to take the pass prior from the last column.
+
+    ``score=True`` (a net with the score head only; off by default): per bucket, inside the captured graph,
+    ``gpool_fwd`` (the pass head's, run once for both), ``dense_f32`` (upre = P sc1_w + sc1_b) and ``score_out``
+    in forward mode fill the bucket's ``score`` (B,) in units of S points; ``score_view`` gives the device rows
+    of a submission in points, in the mover's frame, komi included.
+
+    ``score_utility = lam > 0`` implies ``score=True``; the value column of the output rows then holds the
+    utility (v + lam * tanh(score / (2 S))) / (1 + lam), still in [-1, 1], written by ``score_out`` on the device
+    inside the graph, so the search and the C++ forest need no change.  Root values and the resign threshold
+    then speak of this utility, not of the win/loss value.  ``lam`` has no tuned value.  With ``lam`` = 0
+    nothing extra is launched and the rows keep their bits."""
 
     dual = True
 
-    def __init__(self, net: PolicyValueNet, device, ownership: bool = False, **kw):
+    def __init__(self, net: PolicyValueNet, device, ownership: bool = False, score: bool = False,
+                 score_utility: float = 0.0, **kw):
         if kw.get("symmetries", "none") != "none":
             raise ValueError("the dual (policy + value) engine does not ensemble over symmetries yet: "
                              "symmetries must be \"none\", not %r" % (kw["symmetries"],))
         if ownership and not getattr(net, "ownership", False):
             raise ValueError("ownership=True needs a PolicyValueNet with the ownership head (ownership=1)")
+        self.score_utility, self.score = _check_score_options(net, score, score_utility)
         self.ownership = bool(ownership)
         self.pass_head = bool(getattr(net, "pass_head", False))
         self.vhead = None
         self.ohead = None
         self.phead = None
+        self.shead = None
         super().__init__(net, device, **kw)
 
     def _after_sync(self):
@@ -605,6 +619,17 @@ class HipPolicyValueInference(HipTrunkInference):
                 self.phead = [torch.zeros(2, self.Fp, device=self.device), torch.zeros(1, device=self.device)]
             self.phead[0][:, :self.F].copy_(n.pass_w.detach().view(2, self.F))
             self.phead[1].copy_(n.pass_b.detach().view(-1))
+        if self.score:
+            if self.shead is None:  # [sc1_w zero-padded (2 Fp, D), sc1_b (D), sc2_w (D), sc2_b (1)], allocated once
+                D = n.score_dense
+                self.shead = [torch.zeros(2 * self.Fp, D, device=self.device), torch.zeros(D, device=self.device),
+                              torch.zeros(D, device=self.device), torch.zeros(1, device=self.device)]
+            w1 = n.sc1_w.detach()
+            self.shead[0][:self.F].copy_(w1[:self.F])
+            self.shead[0][self.Fp:self.Fp + self.F].copy_(w1[self.F:])
+            self.shead[1].copy_(n.sc1_b.detach().view(-1))
+            self.shead[2].copy_(n.sc2_w.detach().view(-1))
+            self.shead[3].copy_(n.sc2_b.detach().view(-1))
 
     @property
     def NE(self) -> int:
@@ -614,9 +639,12 @@ class HipPolicyValueInference(HipTrunkInference):
     def _alloc_outputs(self, bk):
         SS = self.S * self.S
         bk.probs = torch.zeros((bk.B, self.NE), device=self.device)
-        if self.pass_head:
+        if self.pass_head or self.score:
             bk.ps_P = torch.zeros((bk.B, 2, self.Fp), device=self.device)
             bk.ps_arg = torch.zeros((bk.B, self.Fp), dtype=torch.int32, device=self.device)
+        if self.score:
+            bk.sc_up = torch.zeros((bk.B, self.shead[1].numel()), device=self.device)
+            bk.score = torch.zeros((bk.B,), device=self.device)
         bk.z = torch.zeros((bk.B, SS), device=self.device)
         if self.ownership:
             bk.own = torch.zeros((bk.B, SS), device=self.device)
@@ -639,6 +667,12 @@ class HipPolicyValueInference(HipTrunkInference):
             ops.policy_value_head(y, self.head_w, self.head_b, vw, vb, bk.probs, bk.z, self.S, legal=bk.legal)
         ops.dense_f32(bk.z, w1, bk.h, bias=b1)
         ops.value_out(bk.h, w2.view(-1), b2, bk.values)
+        if self.score:
+            if not self.pass_head:
+                ops.gpool_fwd(y, bk.ps_P, bk.ps_arg, self.S)
+            ops.dense_f32(bk.ps_P.view(bk.B, -1), self.shead[0], bk.sc_up, bias=self.shead[1])
+            util = dict(value=bk.values, utility=self.score_utility) if self.score_utility else {}
+            ops.score_out(bk.sc_up, self.shead[2], self.shead[3], bk.score, **util)
         bk.out[:, :NE].copy_(bk.probs)
         bk.out[:, NE].copy_(bk.values)
 
@@ -664,10 +698,34 @@ class HipPolicyValueInference(HipTrunkInference):
             raise RuntimeError("nothing submitted yet")
         return bk.own[:n]
 
+    def score_view(self, handle=None):
+        """Device rows (n,) of the score head for the last submission (or ``handle``'s bucket, valid until it is
+        submitted again): points in the mover's frame, komi included."""
+        if not self.score:
+            raise RuntimeError("this engine was built without score=True")
+        if handle is not None:
+            bk, n = handle[0], handle[1]
+        elif self._last_sub is not None:
+            bk, n = self._last_sub
+        else:
+            raise RuntimeError("nothing submitted yet")
+        return bk.score[:n] * float(self.S)
+
     @torch.no_grad()
     def evaluate(self, planes, legal=None, slot: int = 0):
         """As HipTrunkInference.evaluate; returns (probs (n, S*S), with the pass head (n, S*S + 1), values (n,))."""
         return self.split_outputs(super().evaluate(planes, legal, slot))
+
+
+def _check_score_options(net, score, score_utility):
+    """(lam, score) of the dual engines' ``score`` / ``score_utility`` options: a utility implies the score."""
+    lam = float(score_utility)
+    if lam < 0:
+        raise ValueError("score_utility must be >= 0, not %r" % (score_utility,))
+    score = bool(score) or lam > 0
+    if score and not getattr(net, "score_head", False):
+        raise ValueError("score=True / score_utility > 0 need a PolicyValueNet with the score head (score_head=1)")
+    return lam, score
 
 
 class _TorchSymmetries:
@@ -778,7 +836,8 @@ class TorchValueInference(_TorchSymmetries):
 class TorchPolicyValueInference:
     """CPU / fp32 oracle of the dual net: TorchPolicyInference._plain's and TorchValueInference's op
     sequences on one shared trunk output.  ``evaluate`` returns (probs (n, S*S), values (n,)); with the pass
-    head the rows have S*S + 1 entries, the pass last and always legal."""
+    head the rows have S*S + 1 entries, the pass last and always legal.  ``score`` / ``score_utility`` as on
+    HipPolicyValueInference: ``score_view`` in points, the value column as the utility when ``lam`` > 0."""
 
     supports_encoded = False
     needs_ladder = False
@@ -786,7 +845,7 @@ class TorchPolicyValueInference:
     symmetries = "none"
 
     def __init__(self, net: PolicyValueNet, device="cpu", symmetries: str = "none", symmetry_seed: int = 0,
-                 ownership: bool = False):
+                 ownership: bool = False, score: bool = False, score_utility: float = 0.0):
         if _check_symmetries(symmetries) != "none":
             raise ValueError("the dual (policy + value) engine does not ensemble over symmetries yet: "
                              "symmetries must be \"none\", not %r" % (symmetries,))
@@ -795,7 +854,9 @@ class TorchPolicyValueInference:
         self.net, self.device = net, torch.device(device)
         self.ownership = bool(ownership)
         self.pass_head = bool(getattr(net, "pass_head", False))
+        self.score_utility, self.score = _check_score_options(net, score, score_utility)
         self._own = None
+        self._score = None
 
     def sync_weights(self):
         pass
@@ -808,13 +869,27 @@ class TorchPolicyValueInference:
             raise RuntimeError("nothing submitted yet")
         return self._own
 
+    def score_view(self, handle=None):
+        """(n,) score rows of the last evaluate: points in the mover's frame, komi included."""
+        if not self.score:
+            raise RuntimeError("this engine was built without score=True")
+        if self._score is None:
+            raise RuntimeError("nothing submitted yet")
+        return self._score
+
     @torch.no_grad()
     def evaluate(self, planes, legal=None, slot: int = 0):
         x = torch.as_tensor(planes).to(self.device)
-        if self.ownership:
+        if self.ownership or self.score:
             h = self.net.trunk.forward_torch(x.float())
             logits, values = self.net.heads_torch(h)
-            self._own = self.net.ownership_torch(h)
+            if self.ownership:
+                self._own = self.net.ownership_torch(h)
+            if self.score:
+                self._score = self.net.score_torch(h)
+                if self.score_utility:
+                    lam = self.score_utility
+                    values = (values + lam * torch.tanh(self._score / (2.0 * self.net.board))) / (1.0 + lam)
         else:
             logits, values = self.net.logits_value_torch(x.float())
         if legal is not None:
@@ -827,7 +902,7 @@ class TorchPolicyValueInference:
 
 def _torch_kw(kw):
     """The engine keywords the torch engines take too (feature_list etc. are unused: CPU featurizer path)."""
-    return {k: v for k, v in kw.items() if k in ("symmetries", "symmetry_seed", "ownership")}
+    return {k: v for k, v in kw.items() if k in ("symmetries", "symmetry_seed", "ownership", "score", "score_utility")}
 
 
 def make_policy_inference(net, device, **kw):

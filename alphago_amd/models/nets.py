@@ -74,6 +74,13 @@ def he_uniform_(net: nn.Module, generator=None) -> nn.Module:
             g.zero_()
         if getattr(net, "pass_head", False):  # the last linear map of its branch: the pass logit starts at pass_b
             net.pass_w.zero_()
+        if getattr(net, "score_head", False):
+            # the ReLU layer gets its He bound (Keras layout: fan_in = rows), drawn last of all, so that the other
+            # tensors get the values they get in a net without the head; the output layer gets zero: a fresh head
+            # predicts sc2_b = 0 and sends no gradient into the trunk
+            bound = (3.0 / net.sc1_w.shape[0]) ** 0.5
+            net.sc1_w.uniform_(-bound, bound, generator=generator)
+            net.sc2_w.zero_()
     return net
 
 
@@ -286,11 +293,24 @@ class PolicyValueNet(nn.Module):
         z[b]       = [1x1 policy head logits (NP), z_pass[b]]     (NP + 1 entries, the pass last)
 
     ``pass_w`` is drawn after every other parameter (``trunk.gpool_w`` included) and zeroed by ``he_uniform_``;
-    a net without the head draws what it always drew."""
+    a net without the head draws what it always drew.
+
+    ``score_head``: an estimate of the score lead of the player to move (``sc1_w`` (2F, D), ``sc1_b`` (D),
+    ``sc2_w`` (D, 1), ``sc2_b`` (1), Keras Dense layouts, D = ``score_dense``), kept in ``arch`` only when set
+    (``score_dense`` only when it is not 64).  With P the pooled vector above:
+
+        u[b]     = relu(P[b].reshape(2F) @ sc1_w + sc1_b)
+        s[b]     = u[b] @ sc2_w + sc2_b
+        score[b] = S * s[b]                       (points, mover's frame, komi included)
+
+    The unit of ``s`` (S points, 19 on a 19 x 19 board) is a definition, chosen so that ``s`` is O(1).  The four
+    tensors are drawn after every other parameter (``pass_w`` included); ``he_uniform_`` draws ``sc1_w`` at its
+    He bound, last of all, and zeroes ``sc2_w``: a fresh head predicts ``sc2_b`` = 0 and sends no gradient into
+    the trunk."""
 
     def __init__(self, input_dim: int = 49, board: int = 19, filters_per_layer: int = 192, layers: int = 12,
                  dense: int = 256, residual: int = 0, ownership: int = 0, gpool: int = 0, pass_head: int = 0,
-                 **kwargs):
+                 score_head: int = 0, score_dense: int = 64, **kwargs):
         super().__init__()
         widths = [int(kwargs.get("filter_width_%d" % i, 5 if i == 1 else 3)) for i in range(1, layers + 1)]
         self.arch = dict(input_dim=input_dim, board=board, filters_per_layer=filters_per_layer, layers=layers,
@@ -307,6 +327,14 @@ class PolicyValueNet(nn.Module):
         if pass_head:
             self.arch["pass_head"] = 1
         self.pass_head = bool(pass_head)
+        self.score_head = bool(score_head)
+        self.score_dense = int(score_dense)
+        if score_head:
+            if self.score_dense % 8 or not 8 <= self.score_dense <= 512:
+                raise ValueError("score_dense must be a multiple of 8 in 8..512, not %d" % self.score_dense)
+            self.arch["score_head"] = 1
+            if self.score_dense != 64:
+                self.arch["score_dense"] = self.score_dense
         self.ownership = bool(ownership)
         self.board = board
         self.trunk = ConvStack(input_dim, filters_per_layer, layers, widths, residual=bool(residual),
@@ -330,6 +358,13 @@ class PolicyValueNet(nn.Module):
             self.pass_w = nn.Parameter(torch.empty(2 * filters_per_layer, 1))
             self.pass_b = nn.Parameter(torch.zeros(1))
             keras_uniform_(self.pass_w)
+        if score_head:  # after the pass head: every other tensor draws what it draws without the score head
+            self.sc1_w = nn.Parameter(torch.empty(2 * filters_per_layer, self.score_dense))
+            self.sc1_b = nn.Parameter(torch.zeros(self.score_dense))
+            self.sc2_w = nn.Parameter(torch.empty(self.score_dense, 1))
+            self.sc2_b = nn.Parameter(torch.zeros(1))
+            keras_uniform_(self.sc1_w)
+            keras_uniform_(self.sc2_w)
 
     @property
     def input_dim(self):
@@ -346,20 +381,38 @@ class PolicyValueNet(nn.Module):
         tot += len(self.trunk.gpool_blocks) * 2.0 * 2 * cin * cin  # the gates: Dense(2F -> F) per branch block
         if self.pass_head:
             tot += 2.0 * 2 * cin  # the pass logit: Dense(2F -> 1)
+        if self.score_head:  # Dense(2F -> D) with its bias, the ReLU'd Dense(D -> 1) with its bias
+            sd = self.score_dense
+            tot += 2.0 * 2 * cin * sd + sd + 2.0 * sd + 1
         return tot + (3 if self.ownership else 2) * (2.0 * s2 * cin) + 2.0 * s2 * d + 2.0 * d
+
+    @staticmethod
+    def pooled_torch(h: torch.Tensor) -> torch.Tensor:
+        """(B, 2F) mean and max of the trunk output (B, F, S, S) over the board, the max gathered at the lowest
+        pixel index attaining it: fp32 sums of a bf16 trunk, fp64 when given fp64."""
+        B, C = h.shape[:2]
+        flat = h.reshape(B * C, -1)
+        flat = flat if flat.dtype == torch.float64 else flat.float()  # fp32 sums of a bf16 trunk; an fp64 oracle stays fp64
+        mean = flat.sum(1) * torch.tensor(1.0 / flat.shape[1], dtype=torch.float32).to(flat.dtype)
+        mx = flat.gather(1, first_argmax(flat.detach())[:, None])[:, 0]
+        return torch.cat([mean.view(B, C), mx.view(B, C)], 1)
 
     def pass_logit_torch(self, h: torch.Tensor) -> torch.Tensor:
         """(B,) pass logit from the trunk output (B, F, S, S): mean and max over the board (the max gathered at
         the lowest pixel index attaining it), then the dense layer ``pass_w``, ``pass_b``."""
         if not self.pass_head:
             raise ValueError("this PolicyValueNet has no pass head (pass_head=1)")
-        B, C = h.shape[:2]
-        flat = h.reshape(B * C, -1)
-        flat = flat if flat.dtype == torch.float64 else flat.float()  # fp32 sums of a bf16 trunk; an fp64 oracle stays fp64
-        mean = flat.sum(1) * torch.tensor(1.0 / flat.shape[1], dtype=torch.float32).to(flat.dtype)
-        mx = flat.gather(1, first_argmax(flat.detach())[:, None])[:, 0]
-        P = torch.cat([mean.view(B, C), mx.view(B, C)], 1)
+        P = self.pooled_torch(h)
         return (P @ self.pass_w.to(P.dtype)).squeeze(1) + self.pass_b.to(P.dtype)
+
+    def score_torch(self, h: torch.Tensor) -> torch.Tensor:
+        """(B,) score lead of the player to move in points (komi included) from the trunk output (B, F, S, S):
+        the pass head's pooling, Dense(2F -> D) + ReLU, Dense(D -> 1), times S."""
+        if not self.score_head:
+            raise ValueError("this PolicyValueNet has no score head (score_head=1)")
+        P = self.pooled_torch(h)
+        u = torch.relu(P @ self.sc1_w.to(P.dtype) + self.sc1_b.to(P.dtype))
+        return ((u @ self.sc2_w.to(P.dtype)).squeeze(1) + self.sc2_b.to(P.dtype)) * self.board
 
     def policy_logits_torch(self, h: torch.Tensor) -> torch.Tensor:
         """Policy logits from the trunk output, in its dtype: (B, S*S) of the 1x1 head, with the pass head

@@ -206,7 +206,11 @@ class CNNPolicyValue(_NetWrapper):
         super().__init__(feature_list, device=device, **kwargs)
 
     def _make_engine(self):
-        return make_policy_value_inference(self.model, self.device, **self._engine_kw())
+        kw = self._engine_kw()
+        lam = getattr(self, "_score_utility", 0.0)
+        if lam:  # the default engine is built exactly as before
+            kw["score_utility"] = lam
+        return make_policy_value_inference(self.model, self.device, **kw)
 
     # ---------------------------------------------------------- persistence
     def save_model(self, json_file: str, weights_file: Optional[str] = None) -> None:
@@ -287,10 +291,51 @@ class CNNPolicyValue(_NetWrapper):
     def eval_ownership(self, state) -> np.ndarray:
         return self.batch_eval_ownership([state])[0]
 
+    # ---------------------------------------------------------------- score
+    @property
+    def has_score(self) -> bool:
+        return bool(getattr(self.model, "score_head", False))
+
+    def set_score_utility(self, lam: float) -> None:
+        """Search on the utility (v + lam * tanh(score / (2 S))) / (1 + lam) instead of the value from now on
+        (see models/inference.py): the engine's value column, hence root values and the resign threshold, then
+        speak of this utility.  ``lam`` = 0 restores the pure value.  ``lam`` has no tuned value.  The engine
+        is rebuilt on its next use."""
+        lam = float(lam)
+        if lam < 0:
+            raise ValueError("score_utility must be >= 0, not %r" % lam)
+        if lam and not self.has_score:
+            raise ValueError("score_utility needs a net with the score head (init-model pv --score-head)")
+        self._score_utility = lam
+        self._engine = None
+
+    def batch_eval_score(self, states) -> List[float]:
+        """Per state the score head's estimate of the final margin in points, komi included, + = Black (the
+        head's mover's-frame output times ``current_player``).  Runs on a second engine built on first use
+        with ``score=True``; the search engine stays as it is."""
+        if not self.has_score:
+            raise ValueError("this net has no score head")
+        if not states:
+            return []
+        self._check_states(states)
+        if getattr(self, "_score_engine", None) is None:
+            self._score_engine = make_policy_value_inference(self.model, self.device, score=True,
+                                                             **self._engine_kw())
+        eng = self._score_engine
+        planes = self.preprocessor.states_to_uint8(states)
+        eng.evaluate(np.asarray(planes, dtype=np.uint8))
+        sc = eng.score_view().float().cpu().numpy()
+        return [float(sc[i]) * float(st.current_player) for i, st in enumerate(states)]
+
+    def eval_score(self, state) -> float:
+        return self.batch_eval_score([state])[0]
+
     def refresh(self) -> None:
         super().refresh()
         if getattr(self, "_own_engine", None) is not None:
             self._own_engine.sync_weights()
+        if getattr(self, "_score_engine", None) is not None:
+            self._score_engine.sync_weights()
 
     # ---------------------------------------------------------------- split
     def split(self):
@@ -300,6 +345,9 @@ class CNNPolicyValue(_NetWrapper):
         if getattr(self.model, "ownership", False):
             raise ValueError("split(): a net with the ownership head has no (policy, value) form: the pair "
                              "cannot carry the third head")
+        if getattr(self.model, "score_head", False):
+            raise ValueError("split(): a net with the score head has no (policy, value) form: the pair cannot "
+                             "carry the score head")
         if self.model.trunk.residual:
             raise ValueError("split(): a residual trunk has no single-head form (the Keras Sequential of "
                              "CNNPolicy / CNNValue cannot express a skip connection)")

@@ -494,6 +494,40 @@ def gpool_bwd_add_masked(dpass, pass_w, argmax, y, dz, S: int):
     return dz
 
 
+def gpool_bwd_add_masked_dp(dp, argmax, y, dz, S: int, dpass=None, pass_w=None):
+    """The pooling gradient of a general ``dp`` (B, 2, C) fp32 (the score head's), accumulated into the top
+    layer's ``dz`` where ``y`` > 0.  With inv = float32(1 / S*S) and
+
+        q  = dp[b, 0, c] * inv + (p == argmax[b, c] ? dp[b, 1, c] : 0)
+        r0 = (dpass[b] * pass_w[0, c]) * inv
+        r  = p == argmax[b, c] ? fma(dpass[b], pass_w[1, c], r0) : r0
+
+    (``r`` is ``gpool_bwd_add_masked``'s addend with that kernel's bits, taken along in the same pass when
+    ``dpass`` / ``pass_w`` are given), add = r + q, or q alone, and dz[b, p, c] = bf16(float(dz[b, p, c]) + add).
+    Every product and sum is an fp32 rounding of its own, in the order written (the kernel keeps the compiler from contracting them); the one
+    fused multiply-add is the one ``gpool_bwd_add_masked`` executes.  Interior only; elements with ``y`` <= 0
+    keep their bits, and so do elements whose addend is zero."""
+    _ops().gpool_bwd_add_masked_dp(dp, argmax, y, dz, S, gpool_inv(S), dpass, pass_w)
+    return dz
+
+
+def score_out(upre, w2, b2, s, target=None, valid=None, weight=None, loss=None, abserr=None, du=None, dout=None,
+              grad_scale: float = 1.0, delta: float = 1.0, value=None, utility: float = 0.0):
+    """The score head's output layer: u = max(upre, 0), s = u . w2 + b2 per board (``upre`` (B, D) fp32, D a
+    multiple of 8 in 8..512).  Rounding order of the dot product: lane i of the board's wave accumulates
+    fmaf(u[j], w2[j], acc) over j = i, i + 64, ... ascending from 0; the 64 lane sums meet in an xor butterfly
+    with offsets 32, 16, 8, 4, 2, 1; ``b2`` is added last.  No atomics: two runs give the same bits.
+
+    With ``target`` (B,) fp32 in the unit of ``s``: e = s - t, ``loss`` = Huber_delta(e) (0.5 e^2 if |e| <= delta,
+    else delta (|e| - 0.5 delta)), ``abserr`` = |e|, g = grad_scale * valid[b] * weight[b] * clamp(e, -delta, delta),
+    ``du`` = (upre > 0 ? g * w2 : 0) and ``dout`` (B, D + 1) = [g * u | g], the per-board rows ``head_grad_sums``
+    turns into [d w2 | d b2].  ``value`` (B,) with ``utility`` = lam: rewritten in place as
+    (value + lam * tanh(s / 2)) / (1 + lam), the search utility of the inference engines."""
+    _ops().score_out(upre, w2, b2, s, target, valid, weight, loss, abserr, du, dout, float(grad_scale), float(delta),
+                     value, float(utility))
+    return s
+
+
 def pack_weights(ws, wf, wd=()):
     _ops().pack_weights(list(ws), list(wf), list(wd))
 

@@ -185,11 +185,17 @@ class SelfPlayWriter(object):
     the final map of the row's game (``GameState.get_ownership``, the map ``get_winner`` scores by)
     times the row's player to move, so +1 means "mine".  ``ownership_valid`` (N,) uint8: 1 for rows of
     games that ended by two passes; a resigned or capped game is not settled, its rows are all zero and
-    marked 0.  Off (the default): the file holds exactly the five datasets above."""
+    marked 0.  Off (the default): the file holds exactly the five datasets above.
+
+    ``score=True`` adds two datasets for the dual net's score head.  ``score`` (N,) float32: the row's player
+    to move times (sum of the game's final ``get_ownership`` map - komi), the margin of the map ``get_winner``
+    scores by, in points in the mover's frame.  ``score_valid`` (N,) uint8: ``ownership_valid``'s rule, 1 for
+    rows of games that ended by two passes; other rows are 0 and marked 0.  Off (the default): no such
+    datasets."""
 
     def __init__(self, h5_path: str, sgf_dir: Optional[str], features: Sequence[str] = VALUE_FEATURES,
                  size: int = 19, positions_per_game: int = 0, seed: int = 0, threads: int = 16,
-                 ownership: bool = False):
+                 ownership: bool = False, score: bool = False):
         self.pre = Preprocess(list(features))
         self.size = size
         self.sgf_dir = sgf_dir
@@ -211,6 +217,10 @@ class SelfPlayWriter(object):
         self.own: List[np.ndarray] = []
         self.own_valid: List[np.ndarray] = []
         self.own_positions = 0  # rows with a valid ownership map
+        self.score = bool(score)
+        self.sc: List[np.ndarray] = []
+        self.sc_valid: List[np.ndarray] = []
+        self.score_positions = 0  # rows with a valid score
         self.games = self.positions = 0
         self.winners = {go.BLACK: 0, go.WHITE: 0, 0: 0}
         self.lengths: List[int] = []
@@ -260,6 +270,14 @@ class SelfPlayWriter(object):
                 self.own_positions += len(keep)
             self.own.append(rows.astype(np.int8))
             self.own_valid.append(np.full(len(keep), 1 if scored else 0, np.uint8))
+        if self.score:
+            rows = np.zeros(len(keep), np.float32)
+            if scored:  # the position after the replayed moves is the game's last
+                margin = float(np.asarray(st.get_ownership(), np.int64).sum()) - float(r.komi)  # + = Black
+                rows = (margin * np.array([r.players[k] for k in keep], np.float64)).astype(np.float32)
+                self.score_positions += len(keep)
+            self.sc.append(rows)
+            self.sc_valid.append(np.full(len(keep), 1 if scored else 0, np.uint8))
         self.games += 1
         self.positions += len(keep)
         self.winners[r.winner] = self.winners.get(r.winner, 0) + 1
@@ -284,6 +302,10 @@ class SelfPlayWriter(object):
             own.finish()
             self.w.create_dataset("ownership_valid",
                                   data=np.concatenate(self.own_valid) if self.own_valid else np.zeros(0, np.uint8))
+        if self.score:
+            self.w.create_dataset("score", data=np.concatenate(self.sc) if self.sc else np.zeros(0, np.float32))
+            self.w.create_dataset("score_valid",
+                                  data=np.concatenate(self.sc_valid) if self.sc_valid else np.zeros(0, np.uint8))
         self.w.close()
         os.replace(self.tmp, self.path)
         return self.positions
@@ -291,11 +313,17 @@ class SelfPlayWriter(object):
 
 def merge_selfplay_files(paths: List[str], outfile: str, block_rows: int = 4096) -> int:
     """Concatenate per-rank self-play files; game ids are offset so they stay unique.  The ownership
-    datasets are carried when every input has them; inputs of which only some do are refused."""
-    has_own = []
+    datasets are carried when every input has them; inputs of which only some do are refused.  The score
+    datasets (``score``, ``score_valid``) follow the same all-or-none rule."""
+    has_own, has_sc = [], []
     for pth in paths:
         with H5File(pth) as f:
             has_own.append("ownership" in f and "ownership_valid" in f)
+            has_sc.append("score" in f and "score_valid" in f)
+    if any(has_sc) and not all(has_sc):
+        raise ValueError("only some of the files hold score datasets (%s do not): merge files written with the "
+                         "same --score setting" % ", ".join(p for p, h in zip(paths, has_sc) if not h))
+    carry_sc = bool(has_sc) and all(has_sc)
     if any(has_own) and not all(has_own):
         raise ValueError("only some of the files hold ownership datasets (%s do not): merge files written with "
                          "the same --ownership setting"
@@ -314,6 +342,9 @@ def merge_selfplay_files(paths: List[str], outfile: str, block_rows: int = 4096)
         own_rows: List[np.ndarray] = []
         if carry_own:
             cols["ownership_valid"] = []
+        if carry_sc:  # after the ownership entries, the writer's order
+            cols["score"] = []
+            cols["score_valid"] = []
         goff = 0
         for pth in paths:
             with H5File(pth) as f:
@@ -332,7 +363,7 @@ def merge_selfplay_files(paths: List[str], outfile: str, block_rows: int = 4096)
                 total += ds.shape[0]
         st.finish()
         for k, v in cols.items():
-            if k != "ownership_valid":
+            if k not in ("ownership_valid", "score", "score_valid"):
                 w.create_dataset(k, data=np.concatenate(v))
         if carry_own:
             own = w.stream_dataset("ownership", own_rows[0].shape[1:], np.int8, chunk_rows=STATE_CHUNK_ROWS,
@@ -341,6 +372,9 @@ def merge_selfplay_files(paths: List[str], outfile: str, block_rows: int = 4096)
                 own.append(rows)
             own.finish()
             w.create_dataset("ownership_valid", data=np.concatenate(cols["ownership_valid"]))
+        if carry_sc:
+            w.create_dataset("score", data=np.concatenate(cols["score"]).astype(np.float32))
+            w.create_dataset("score_valid", data=np.concatenate(cols["score_valid"]))
     os.replace(tmp, outfile)
     return total
 
@@ -468,6 +502,10 @@ def selfplay_cli(argv=None):
     p.add_argument("--ownership", action="store_true",
                    help="also write ownership / ownership_valid: the final territory map of each scored game in the "
                         "mover's frame, the target of the dual net's ownership head (init-model pv --ownership)")
+    p.add_argument("--score", action="store_true",
+                   help="also write score / score_valid: the final margin of each scored game in points in the "
+                        "mover's frame, komi included, the target of the dual net's score head (init-model pv "
+                        "--score-head)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--no-sgf", action="store_true")
     p.add_argument("--progress-every", type=int, default=0, help="print a progress line every N search rounds")
@@ -493,7 +531,7 @@ def selfplay_cli(argv=None):
     sgf = None if a.no_sgf else os.path.join(a.out_directory, "sgf", "rank%d" % env.rank)
     wkw = {"features": list(policy.preprocessor.feature_list)} if dual else {}  # the dual net's own planes
     writer = SelfPlayWriter(h5, sgf, size=S, positions_per_game=a.positions_per_game,
-                            seed=a.seed * 1009 + env.rank, ownership=a.ownership, **wkw)
+                            seed=a.seed * 1009 + env.rank, ownership=a.ownership, score=a.score, **wkw)
     stats: List[RoundStats] = []
     t0 = time.perf_counter()
     play_selfplay(policy, value, a.games, a.concurrent, cfg, size=S, komi=a.komi, max_moves=a.max_moves or None,
@@ -509,6 +547,8 @@ def selfplay_cli(argv=None):
              "endings": dict(writer.endings)}
     if a.ownership:
         local["ownership_positions"] = writer.own_positions
+    if a.score:
+        local["score_positions"] = writer.score_positions
     every = agdist.all_gather_object(local)
     if env.world_size > 1:
         agdist.barrier()
@@ -525,6 +565,8 @@ def selfplay_cli(argv=None):
                "endings": {k: sum(e["endings"][k] for e in every) for k in every[0]["endings"]}}
     if a.ownership:  # positions whose game was scored: the rows with a valid ownership map
         summary["ownership_positions"] = sum(e["ownership_positions"] for e in every)
+    if a.score:  # the rows with a valid score
+        summary["score_positions"] = sum(e["score_positions"] for e in every)
     summary["leaf_evals_per_s"] = round(summary["leaf_evals"] / max(summary["seconds"], 1e-9), 1)
     if env.is_main:
         with open(os.path.join(a.out_directory, "selfplay_summary.json"), "w") as f:

@@ -1303,6 +1303,22 @@ def _pv_targets(targets, ownership: bool = False):
     return targets[0], targets[1], None
 
 
+def _pv_score_target(targets, score_head: bool):
+    """(targets without the fourth slot, score): a 4-tuple (pi, z, own_or_None, (score_t, score_valid)) carries
+    the score target -- ``score_t`` (B,) in points in the mover's frame, komi included, ``score_valid`` (B,)
+    marking the boards of scored games; pairs and triples mean what they always meant (score = None)."""
+    if not (isinstance(targets, (tuple, list)) and len(targets) == 4):
+        return targets, None
+    if not score_head:
+        raise ValueError("a target 4-tuple (pi, z, own, (score_t, score_valid)) needs a net with the score head "
+                         "(score_head=1)")
+    sc = targets[3]
+    if not isinstance(sc, (tuple, list)) or len(sc) != 2:
+        raise ValueError("the score target is a pair (score_t (B,), score_valid (B,))")
+    base = (targets[0], targets[1]) if targets[2] is None else (targets[0], targets[1], targets[2])
+    return base, (sc[0], sc[1])
+
+
 def pass_target_rows(moves: torch.Tensor, NP: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(B, NP + 1) one-hot rows of hard move targets for a net with the pass head: a move of -1 (a pass) has
     its 1 at column NP.  The rows take the soft-target path, which moves them with the board."""
@@ -1366,17 +1382,34 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
     The metric sums are the same; policy loss and top-1 now count pass rows.  A net without the head
     launches exactly the kernels above.
 
+    A net with the score head (``PolicyValueNet(score_head=1)``) takes a fourth target slot,
+    ``(pi_or_moves, z, own_or_None, (score_t, score_valid))``: ``score_t`` (B,) fp32 is the final margin in
+    points in the mover's frame, komi included (the trainer divides by S), ``score_valid`` (B,) marks the boards
+    of scored games.  The loss gains ``score_coef`` * (1 / B_global) sum_b valid_b w_b Huber_delta(s_b - t_b / S);
+    ``score_coef`` = 1.0 and ``score_delta`` = 1.0 (S points) are conventional starting points, not tuned.  The
+    score does not move with ``sym``.  Per step: ``gpool_fwd(Y[L-1])`` once (shared with the pass head),
+    ``dense_f32`` (upre = P sc1_w + sc1_b), ``score_out``, ``dense_f32`` twice (d sc1_w = P^T du,
+    dP = du sc1_w^T), then ``gpool_bwd_add_masked_dp`` as the last accumulation into dZ[L-1] -- with the pass
+    head's term in the same pass, in ``gpool_bwd_add_masked``'s place -- and two ``head_grad_sums`` calls
+    (``sc1_b`` from du, ``sc2_w | sc2_b`` from the partial rows).  The four tensors follow the pass entries in
+    the flat parameters.  ``step`` / ``evaluate`` append two sums: the Huber loss over valid boards and
+    |e| * S over valid boards, the absolute error in points.  A pair or triple trains without the score term,
+    zeroes the four gradients and reports 0 for both.  A net without the head launches exactly the kernels above.
+
     fp8: the head writes the bf16 dZ only (``_top_e5m2_fusable`` is False: a sum of two heads cannot
     be accumulated in e5m2), so an fp8 backward works through the unfused ``quantize_bf8`` pass over
     the summed dZ[L-1], the policy trainer's path.  Graph mode and the regularised head options
     (``ent_coef``, ``kl_coef``, ``collect_*``, ``policy_loss='bce'``) are refused."""
 
     def __init__(self, net, batch: int, lr: float = 0.003, decay: float = 0.0, value_coef: float = 1.0,
-                 own_coef: float = 1.0, **kw):
+                 own_coef: float = 1.0, score_coef: float = 1.0, score_delta: float = 1.0, **kw):
         self.value_coef = float(value_coef)
         self.own_coef = float(own_coef)
+        self.score_coef = float(score_coef)    # 1.0: a conventional starting point, not tuned
+        self.score_delta = float(score_delta)  # Huber threshold in units of S points; 1.0 is not tuned either
         self.has_own = bool(getattr(net, "ownership", False))
         self.has_pass = bool(getattr(net, "pass_head", False))
+        self.has_score = bool(getattr(net, "score_head", False))
         super().__init__(net, batch, lr, decay, **kw)
 
     def _head_named_params(self):
@@ -1387,15 +1420,35 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
             named += [("ohead_w", n.ohead_w), ("ohead_b", n.ohead_b)]
         if self.has_pass:  # after the ownership entries
             named += [("pass_w", n.pass_w), ("pass_b", n.pass_b)]
+        if self.has_score:  # after the pass entries
+            named += [("sc1_w", n.sc1_w), ("sc1_b", n.sc1_b), ("sc2_w", n.sc2_w), ("sc2_b", n.sc2_b)]
         return named
 
     def _init_head(self):
         super()._init_head()
         B, NP, dev = self.batch, self.S * self.S, self.device
-        if self.has_pass:
+        if self.has_pass or self.has_score:  # the pooled trunk output, shared by both heads
             F, Fp = self.F, self.Fp
             self._ps_P = torch.zeros(B, 2, Fp, device=dev)
             self._ps_arg = torch.zeros(B, Fp, dtype=torch.int32, device=dev)
+        if self.has_score:
+            SD = self.net.score_dense
+            self._sc_up = torch.zeros(B, SD, device=dev)
+            self._sc_s = torch.zeros(B, device=dev)
+            self._sc_t = torch.zeros(B, device=dev)
+            self._sc_valid = torch.zeros(B, device=dev)
+            self._sc_loss = torch.zeros(B, device=dev)
+            self._sc_abs = torch.zeros(B, device=dev)
+            self._sc_du = torch.zeros(B, SD, device=dev)
+            self._sc_dout = torch.zeros(B, SD + 1, device=dev)
+            self._sc_dP = torch.zeros(B, 2, Fp, device=dev)
+            # dense_f32 reads a (2 Fp, D) weight: the flat views, or zero-padded scratch (repack) when F < Fp
+            if F == Fp:
+                self._sc_w1, self._sc_dw1 = self.fp.views["sc1_w"], self.fp.grad_views["sc1_w"]
+            else:
+                self._sc_w1 = torch.zeros(2 * Fp, SD, device=dev)
+                self._sc_dw1 = torch.zeros(2 * Fp, SD, device=dev)
+        if self.has_pass:
             self._ps_d = torch.zeros(B, device=dev)
             self._ps_dpw = torch.zeros(B, 2 * F + 1, device=dev)
             self._ps_rows = torch.zeros(B, NP + 1, device=dev)
@@ -1425,6 +1478,10 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
         super().repack(bf16)
         if self.has_pass and self.F < self.Fp:  # the pass head's zero-padded weight copy
             self._ps_w[:, :self.F].copy_(self.fp.views["pass_w"].view(2, self.F))
+        if self.has_score and self.F < self.Fp:  # the score head's zero-padded first layer
+            w = self.fp.views["sc1_w"]
+            self._sc_w1[:self.F].copy_(w[:self.F])
+            self._sc_w1[self.Fp:self.Fp + self.F].copy_(w[self.F:])
 
     def enable_graphs(self, on: bool = True) -> None:
         if on:
@@ -1463,11 +1520,14 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
         self._check_plain()
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError(_PV_NO_GRAPH)
+        targets, score = _pv_score_target(targets, self.has_score)
         pi, z, own = _pv_targets(targets, self.has_own)
         if z.numel() != self.batch:
             raise ValueError("outcomes must hold %d entries, got %d" % (self.batch, z.numel()))
         if own is not None:
             self._check_own(own)
+        if score is not None:
+            self._check_score(score)
         if self.has_pass:
             pi = self._pi_rows = self._pass_pi(pi)  # converted once per step: _head_train takes these rows
         super()._forward_for_head(planes, pi, sym)
@@ -1477,6 +1537,49 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
         if tuple(own[0].shape) != (self.batch, NP) or own[1].numel() != self.batch:
             raise ValueError("the ownership target is (own_t (%d, %d), own_valid (%d,)), got %s and %s"
                              % (self.batch, NP, self.batch, tuple(own[0].shape), tuple(own[1].shape)))
+
+    def _check_score(self, score) -> None:
+        if score[0].numel() != self.batch or score[1].numel() != self.batch:
+            raise ValueError("the score target is (score_t (%d,), score_valid (%d,)), got %s and %s"
+                             % (self.batch, self.batch, tuple(score[0].shape), tuple(score[1].shape)))
+
+    def _score_forward(self, score, pooled: bool) -> None:
+        """upre = P sc1_w + sc1_b from the pooled trunk output (``pooled``: gpool_fwd already ran this step) and
+        the target in units of S points."""
+        if not pooled:
+            ops.gpool_fwd(self.Y[-1], self._ps_P, self._ps_arg, self.S)
+        ops.dense_f32(self._ps_P.view(self.batch, -1), self._sc_w1, self._sc_up, bias=self.fp.views["sc1_b"])
+        self._sc_t.copy_(score[0].view(-1))
+        self._sc_t.div_(float(self.S))
+        self._sc_valid.copy_(score[1].view(-1))
+
+    def _score_metric_vectors(self):
+        """(valid_b * Huber_b, valid_b * |e_b| * S): the loss in the head's unit, the absolute error in points."""
+        return self._sc_loss * self._sc_valid, self._sc_abs * self._sc_valid * float(self.S)
+
+    def _score_train(self, score, gscale, weight) -> None:
+        """The score head's forward, loss and backward; the last accumulation into dZ[L-1] (the pass head's
+        pooling gradient rides along) and the head's four gradients."""
+        B, F, Fp = self.batch, self.F, self.Fp
+        v, gv = self.fp.views, self.fp.grad_views
+        self._score_forward(score, pooled=self.has_pass)
+        ops.score_out(self._sc_up, v["sc2_w"].view(-1), v["sc2_b"], self._sc_s, target=self._sc_t,
+                      valid=self._sc_valid, weight=weight, loss=self._sc_loss, abserr=self._sc_abs, du=self._sc_du,
+                      dout=self._sc_dout, grad_scale=gscale * self.score_coef, delta=self.score_delta)
+        P = self._ps_P.view(B, -1)
+        ops.dense_f32(P, self._sc_du, self._sc_dw1, trans_a=True)  # d sc1_w = P^T du
+        if F < Fp:
+            gv["sc1_w"][:F].copy_(self._sc_dw1[:F])
+            gv["sc1_w"][F:].copy_(self._sc_dw1[Fp:Fp + F])
+        ops.dense_f32(self._sc_du, self._sc_w1, self._sc_dP.view(B, -1), trans_b=True)  # dP = du sc1_w^T
+        ops.gpool_bwd_add_masked_dp(self._sc_dP, self._ps_arg, self.Y[-1], self.DZ[-1], self.S,
+                                    dpass=self._ps_d if self.has_pass else None,
+                                    pass_w=self._ps_w if self.has_pass else None)
+        self._smetric_sums = torch.empty(2, device=self.device)
+        sl, sa = self._score_metric_vectors()
+        ops.head_grad_sums(self._sc_du, sl, sa, gv["sc1_b"], self._smetric_sums)
+        so, sn = self.fp.segments["sc2_w"]
+        ops.head_grad_sums(self._sc_dout, sl, sa, self.fp.grad[so:so + sn + 1], torch.empty(2, device=self.device))
 
     def _own_forward(self, own, sym, weight, gscale):
         """value_own_head in head_logits' place: z, own, the per-board ownership loss / agreement and dlo."""
@@ -1500,6 +1603,7 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
         ops.dense_f32(self.z, v["fc1_w"], self.h, bias=v["fc1_b"])  # h = z W1 + b1
 
     def _head_train(self, targets, gscale, weight, sym=None):
+        targets, score = _pv_score_target(targets, self.has_score)
         pi, z, own = _pv_targets(targets, self.has_own)
         v, gv = self.fp.views, self.fp.grad_views
         if self.has_pass:  # (B, S*S + 1) rows, hard moves included (_forward_for_head made them)
@@ -1546,10 +1650,21 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
             else:  # a pair: no ownership term
                 self._ometric_sums = torch.zeros(2, device=self.device)
                 self.fp.grad[oo:oo + on + 1].zero_()
+        if self.has_score:
+            # 6 (before 5's sums, in 5's accumulation's place). the score head; its gpool_bwd_add_masked_dp is
+            #    the last accumulation into dZ[L-1] and carries the pass head's term
+            if score is not None:
+                self._score_train(score, gscale, weight)
+            else:  # a pair or triple: no score term
+                self._smetric_sums = torch.zeros(2, device=self.device)
+                so = self.fp.segments["sc1_w"][0]
+                eo, en = self.fp.segments["sc2_b"]
+                self.fp.grad[so:eo + en].zero_()
         if self.has_pass:
             # 5. the pass head: its pooling's ReLU'-masked gradient into dZ[L-1], last of the accumulations,
             #    and [d pass_w | d pass_b] from the per-board partial rows
-            ops.gpool_bwd_add_masked(self._ps_d, self._ps_w, self._ps_arg, self.Y[-1], self.DZ[-1], self.S)
+            if not (self.has_score and score is not None):
+                ops.gpool_bwd_add_masked(self._ps_d, self._ps_w, self._ps_arg, self.Y[-1], self.DZ[-1], self.S)
             po, pn = self.fp.segments["pass_w"]
             ops.head_grad_sums(self._ps_dpw, self.loss, self.correct, self.fp.grad[po:po + pn + 1],
                                torch.empty(2, device=self.device))
@@ -1566,6 +1681,8 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
         m = (self._metric_sums[0], self._metric_sums[1], self._vmetric_sums[0], self._vmetric_sums[1])
         if self.has_own:
             m += (self._ometric_sums[0], self._ometric_sums[1])
+        if self.has_score:
+            m += (self._smetric_sums[0], self._smetric_sums[1])
         return m
 
     @torch.no_grad()
@@ -1579,11 +1696,15 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
 
     @torch.no_grad()
     def evaluate(self, planes: torch.Tensor, targets):
-        """The four metric sums (six for a net with the ownership head) without an update (validation)."""
+        """The four metric sums (six for a net with the ownership head, two more for one with the score head)
+        without an update (validation)."""
         self._check_plain()
+        targets, score = _pv_score_target(targets, self.has_score)
         pi, z, own = _pv_targets(targets, self.has_own)
         if own is not None:
             self._check_own(own)
+        if score is not None:
+            self._check_score(score)
         if self.has_pass:
             pi = self._pass_pi(pi)
         pl, pc = super().evaluate(planes, pi)  # leaves the trunk output in Y[-1]
@@ -1599,6 +1720,16 @@ class HipPolicyValueTrainer(HipPolicyTrainer):
             if own is not None:
                 ol, oa = self._own_metric_vectors()
                 m += (ol.sum(), oa.sum())
+            else:
+                m += (torch.zeros((), device=self.device), torch.zeros((), device=self.device))
+        if self.has_score:
+            if score is not None:
+                self._score_forward(score, pooled=False)
+                ops.score_out(self._sc_up, v["sc2_w"].view(-1), v["sc2_b"], self._sc_s)
+                e = self._sc_s - self._sc_t
+                d = self.score_delta
+                hub = torch.where(e.abs() <= d, 0.5 * e * e, d * (e.abs() - 0.5 * d))
+                m += ((hub * self._sc_valid).sum(), (e.abs() * self._sc_valid).sum() * float(self.S))
             else:
                 m += (torch.zeros((), device=self.device), torch.zeros((), device=self.device))
         return m
@@ -1782,7 +1913,9 @@ class TorchPolicyValueTrainer(_TorchTrainerBase):
     """Autograd twin of HipPolicyValueTrainer: mean over the global batch of the policy CE (hard or soft
     targets, TorchPolicyTrainer's expressions) + ``value_coef`` * (v - z)^2 on one trunk output; for a net
     with the ownership head and a target triple also ``own_coef`` * valid_b * mean_p (own - own_t)^2 (the
-    target moved with the board by ``sym``).  ``own_coef`` defaults to 1.0, untuned."""
+    target moved with the board by ``sym``).  ``own_coef`` defaults to 1.0, untuned.  For a net with the score
+    head and a target 4-tuple also ``score_coef`` * valid_b * Huber_delta(score_torch(h) / S - score_t / S), which
+    does not move with ``sym``; ``score_coef`` = 1.0 and ``score_delta`` = 1.0 are untuned starting points."""
 
     policy_loss = "ce"
     ent_coef = 0.0
@@ -1792,19 +1925,24 @@ class TorchPolicyValueTrainer(_TorchTrainerBase):
 
     def __init__(self, net, batch: int, lr: float = 0.003, decay: float = 0.0, device=None, dtype=torch.float32,
                  iterations: int = 0, optimizer: str = "sgd", momentum: float = 0.0, nesterov: bool = False,
-                 value_coef: float = 1.0, own_coef: float = 1.0):
+                 value_coef: float = 1.0, own_coef: float = 1.0, score_coef: float = 1.0, score_delta: float = 1.0):
         self.value_coef = float(value_coef)
         self.own_coef = float(own_coef)
+        self.score_coef = float(score_coef)    # 1.0: a conventional starting point, not tuned
+        self.score_delta = float(score_delta)  # Huber threshold in units of S points, not tuned either
         self.has_own = bool(getattr(net, "ownership", False))
         self.has_pass = bool(getattr(net, "pass_head", False))
+        self.has_score = bool(getattr(net, "score_head", False))
         named = _trunk_named(net.trunk) + [(n, getattr(net, n)) for n in (
             "head_w", "head_b", "vhead_w", "vhead_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b") +
-            (("ohead_w", "ohead_b") if self.has_own else ()) + (("pass_w", "pass_b") if self.has_pass else ())]
+            (("ohead_w", "ohead_b") if self.has_own else ()) + (("pass_w", "pass_b") if self.has_pass else ()) +
+            (("sc1_w", "sc1_b", "sc2_w", "sc2_b") if self.has_score else ())]
         self._setup(net, batch, lr, decay, device, dtype, iterations, named, optimizer, momentum, nesterov)
 
     def _loss(self, planes, targets, sym, weight):
         if self.policy_loss != "ce" or self.ent_coef or self.kl_coef or self.collect_stats or self.collect_probs:
             raise ValueError(_PV_REFUSED)
+        targets, score = _pv_score_target(targets, self.has_score)
         pi, z, own = _pv_targets(targets, self.has_own)
         if self.has_pass:  # logits of S*S + 1 entries: rows with the pass last, hard moves as one-hot rows
             NP = self.net.board ** 2
@@ -1849,12 +1987,25 @@ class TorchPolicyValueTrainer(_TorchTrainerBase):
             self._olast = ((oerr * own_valid).detach(), (own_agreement_share(o.detach(), own_t) * own_valid))
         elif self.has_own:
             self._olast = (torch.zeros_like(err.detach()), torch.zeros_like(err.detach()))
+        if score is not None:
+            S = float(self.net.board)
+            sv = score[1].to(v.dtype).view(-1)
+            e = self.net.score_torch(h).to(v.dtype) / S - score[0].to(v.dtype).view(-1) / S
+            d = self.score_delta
+            hub = torch.where(e.abs() <= d, 0.5 * e * e, d * (e.abs() - 0.5 * d))
+            sw = sv if weight is None else sv * weight
+            obj = obj + self.score_coef * (hub * sw).sum() / norm
+            self._slast = ((hub * sv).detach(), (e.abs() * sv * S).detach())
+        elif self.has_score:
+            self._slast = (torch.zeros_like(err.detach()), torch.zeros_like(err.detach()))
         return obj, per, correct
 
     def _metrics(self, pl, pc):
         m = (pl, pc, self._vlast[0].sum(), self._vlast[1].sum())
         if self.has_own:
             m += (self._olast[0].sum(), self._olast[1].sum())
+        if self.has_score:
+            m += (self._slast[0].sum(), self._slast[1].sum())
         return m
 
     def step(self, planes, targets, sym=None, weight=None, rows=None):
@@ -1892,14 +2043,14 @@ def make_policy_trainer(net: PolicyNet, batch: int, lr: float, decay: float = 0.
 def make_policy_value_trainer(net, batch: int, lr: float, decay: float = 0.0, backend: str = "auto", device=None,
                               **kw):
     """The dual net's trainer: HipPolicyValueTrainer on a GPU, TorchPolicyValueTrainer otherwise
-    (``value_coef`` and ``own_coef`` go to both)."""
+    (``value_coef``, ``own_coef``, ``score_coef`` and ``score_delta`` go to both)."""
     dev = torch.device(device) if device is not None else agdist.env().device
     if backend == "auto":
         backend = "hip" if dev.type == "cuda" else "torch"
     if backend == "hip":
         return HipPolicyValueTrainer(net, batch, lr, decay, device=dev, **kw)
     tkw = _torch_kw(kw)
-    for k in ("value_coef", "own_coef"):
+    for k in ("value_coef", "own_coef", "score_coef", "score_delta"):
         if k in kw:
             tkw[k] = kw[k]
     return TorchPolicyValueTrainer(net, batch, lr, decay, device=dev, **tkw)

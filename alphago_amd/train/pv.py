@@ -15,11 +15,17 @@ A model with the ownership head (``init-model pv --ownership``) also reads ``own
 ``ownership_valid`` (``selfplay-mcts --ownership``) and adds ``--ownership-coef`` times the mean squared
 error of the ownership head against the final territory map, over the positions of scored games.
 
+A model with the score head (``init-model pv --score-head``) also reads ``score`` and ``score_valid``
+(``selfplay-mcts --score``) and adds ``--score-coef`` times the Huber loss (threshold S points) of the head
+against the final margin in units of S points, over the positions of scored games.  The score does not move
+with the board.
+
 D4 augmentation goes through the input pack's ``sym``: the soft head moves the distribution with the
 board, the ownership head moves its target the same way, and the outcome is invariant.  The output
 directory holds ``metadata.json`` (per-epoch ``loss``, ``acc``, ``value_loss``, ``value_acc`` and their
 ``val_`` forms; with the ownership head also ``own_loss`` and ``own_acc``, means over the positions with
-a valid ownership row), ``shuffle.npz`` and ``weights.{epoch:05d}.hdf5`` per epoch, as ``train-sl``
+a valid ownership row; with the score head also ``score_loss`` and ``score_mae``, the latter in points, means
+over the positions with a valid score), ``shuffle.npz`` and ``weights.{epoch:05d}.hdf5`` per epoch, as ``train-sl``
 writes them.
 
 Out of scope here: checkpoint / exact resume (``--weights`` restarts from a weights file with a fresh
@@ -45,6 +51,7 @@ from .sl import MetadataWriter
 
 _KEYS = ("loss", "acc", "value_loss", "value_acc")
 _OWN_KEYS = ("own_loss", "own_acc")
+_SCORE_KEYS = ("score_loss", "score_mae")
 
 
 class _PVParser(argparse.ArgumentParser):
@@ -74,6 +81,9 @@ def _parser():
     p.add_argument("--ownership-coef", type=float, default=1.0,
                    help="weight of the ownership MSE (models with the ownership head); 1.0 is a conventional "
                         "starting point, not a tuned value")
+    p.add_argument("--score-coef", type=float, default=1.0,
+                   help="weight of the score head's Huber loss (models with the score head); 1.0 is a conventional "
+                        "starting point, not a tuned value")
     p.add_argument("--targets", default="pi", choices=["pi", "played"],
                    help="pi: the search's visit distribution (soft-target head, default); played: the move played")
     p.add_argument("--no-symmetries", action="store_true", help="disable random D4 augmentation")
@@ -98,11 +108,13 @@ def _pad(t: torch.Tensor, B: int, fill) -> torch.Tensor:
     return torch.cat([t, torch.full((B - t.shape[0],) + tuple(t.shape[1:]), fill, dtype=t.dtype, device=t.device)])
 
 
-def trainer_kwargs(args, ownership: bool) -> dict:
+def trainer_kwargs(args, ownership: bool, score: bool = False) -> dict:
     """The keyword arguments make_policy_value_trainer gets for the parsed command line."""
     kw = {"value_coef": args.value_coef}
     if ownership:
         kw["own_coef"] = args.ownership_coef
+    if score:
+        kw["score_coef"] = args.score_coef
     if args.precision != "bf16":
         kw["precision"] = args.precision
     if args.fp8_backward:
@@ -132,6 +144,13 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
                                  % args.train_data)
             own = np.asarray(f["ownership"].read()).astype(np.int8)
             own_valid = np.asarray(f["ownership_valid"].read()).astype(np.float32)
+        score = score_valid = None
+        if getattr(net, "score_head", False):
+            if "score" not in f or "score_valid" not in f:
+                raise ValueError("%s has no 'score' / 'score_valid' datasets, which a model with the score head "
+                                 "trains on: write the records with selfplay-mcts --score" % args.train_data)
+            score = np.asarray(f["score"].read()).astype(np.float32)
+            score_valid = np.asarray(f["score_valid"].read()).astype(np.float32)
     n_total = states.shape[0]
     if states.shape[1] != model.preprocessor.output_dim or states.shape[2] != S:
         raise ValueError("dataset rows are %s, the model expects (%d, %d, %d)"
@@ -141,6 +160,9 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
     if own is not None and (own.shape != (n_total, S * S) or own_valid.shape != (n_total,)):
         raise ValueError("ownership / ownership_valid do not match states: %s, %s for %d positions"
                          % (own.shape, own_valid.shape, n_total))
+    if score is not None and (score.shape != (n_total,) or score_valid.shape != (n_total,)):
+        raise ValueError("score / score_valid do not match states: %s, %s for %d positions"
+                         % (score.shape, score_valid.shape, n_total))
     perm = np.random.default_rng(args.seed).permutation(n_total)
     n_train = int(args.train_val_test[0] * n_total)
     n_val = int(args.train_val_test[1] * n_total)
@@ -158,9 +180,11 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
                          value_coef=args.value_coef)
     if own is not None:
         meta.metadata.update(ownership_coef=args.ownership_coef)
+    if score is not None:
+        meta.metadata.update(score_coef=args.score_coef)
 
     B = args.minibatch
-    kw = trainer_kwargs(args, own is not None)
+    kw = trainer_kwargs(args, own is not None, score is not None)
     trainer = make_policy_value_trainer(net, B, args.learning_rate, args.decay, backend=args.backend, device=dev, **kw)
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed * 1000 + rank)
@@ -179,18 +203,27 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
             tgt = _pad(pass_target_rows(torch.from_numpy(moves[idx]).to(dev), S * S), B, 0.0)
         else:
             tgt = _pad(torch.from_numpy(moves[idx]).to(dev), B, -1)
+        ownt = None
         if own is not None:  # padding rows are invalid: no ownership term
             ot = _pad(torch.from_numpy(own[idx]).to(dev), B, 0)
             ov = _pad(torch.from_numpy(own_valid[idx]).to(dev), B, 0.0)
-            return planes, (tgt, zt, (ot, ov))
+            ownt = (ot, ov)
+        if score is not None:  # the fourth slot; padding rows are invalid here too
+            sct = _pad(torch.from_numpy(score[idx]).to(dev), B, 0.0)
+            scv = _pad(torch.from_numpy(score_valid[idx]).to(dev), B, 0.0)
+            return planes, (tgt, zt, ownt, (sct, scv))
+        if ownt is not None:
+            return planes, (tgt, zt, ownt)
         return planes, (tgt, zt)
 
     steps = max(1, len(my_train) // B)
     for epoch in range(args.epochs):
         t0 = time.perf_counter()
         order = order_rng.permutation(my_train)
-        nm = 6 if own is not None else 4
-        sums = torch.zeros(nm + 1, device=dev, dtype=torch.float64)  # the metric sums, then the valid ownership rows
+        no = 6 if own is not None else 4  # the score head's two sums follow the ownership head's
+        nm = no + (2 if score is not None else 0)
+        # the metric sums, then the valid ownership rows and the valid score rows
+        sums = torch.zeros(nm + 2, device=dev, dtype=torch.float64)
         for s in range(steps):
             idx = order[s * B:(s + 1) * B]
             if len(idx) < B:  # fewer positions than one minibatch: wrap around
@@ -201,14 +234,19 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
             sums[:nm] += torch.stack([m.double() for m in trainer.step(planes, tgt, sym)])
             if own is not None:
                 sums[nm] += tgt[2][1].double().sum()
+            if score is not None:
+                sums[nm + 1] += tgt[3][1].double().sum()
         agdist.all_reduce_sum_(sums)
         seen = steps * B * world
         logs = {k: float(v) / seen for k, v in zip(_KEYS, sums)}
         if own is not None:
             logs.update({k: float(v) / max(1.0, float(sums[nm])) for k, v in zip(_OWN_KEYS, sums[4:6])})
+        if score is not None:
+            logs.update({k: float(v) / max(1.0, float(sums[nm + 1])) for k, v in zip(_SCORE_KEYS, sums[no:no + 2])})
         if n_val > 0:
             vs = torch.zeros(5, device=dev, dtype=torch.float64)
             vo = torch.zeros(3, device=dev, dtype=torch.float64)
+            vsc = torch.zeros(3, device=dev, dtype=torch.float64)
             for i in range(0, len(my_val), B):
                 idx = my_val[i:i + B]
                 planes, tgt = batch(idx)
@@ -223,12 +261,18 @@ def run_training(cmd_line_args: Optional[List[str]] = None):
                 if own is not None:
                     vo[:2] += m[4:6]
                     vo[2] += tgt[2][1].double().sum()
+                if score is not None:
+                    vsc[:2] += m[no:no + 2]
+                    vsc[2] += tgt[3][1].double().sum()
             agdist.all_reduce_sum_(vs)
             n = max(1.0, float(vs[4]))
             logs.update({"val_" + k: float(v) / n for k, v in zip(_KEYS, vs[:4])})
             if own is not None:
                 agdist.all_reduce_sum_(vo)
                 logs.update({"val_" + k: float(v) / max(1.0, float(vo[2])) for k, v in zip(_OWN_KEYS, vo[:2])})
+            if score is not None:
+                agdist.all_reduce_sum_(vsc)
+                logs.update({"val_" + k: float(v) / max(1.0, float(vsc[2])) for k, v in zip(_SCORE_KEYS, vsc[:2])})
         dt = time.perf_counter() - t0
         if env.is_main:
             ep = meta.on_epoch_end(logs)
